@@ -17,11 +17,17 @@ every collective of the N-rank code path on a process group of one (RCCL by defa
 takes and how much memory it needs can be measured on a one-GPU box; the line says `"as_rank": "r:N"` and its `value` is what the
 N-GPU job would report if this rank were its slowest.
 
-`value` is the HBM-resident figure (the bench contract: inputs resident when the timed region starts).  SURVEY 8(d)
-also wants the figure with the H2D copy inside: `pcie_inclusive` (one step through leon_dna_encode_batch, reads in
-pageable host memory) is measured in every default N = 1 run, beside `verify` (checksum of block checksums), `decode`
-(the whole file back through the device decoder, compared with the input) and `end_to_end` (`leon -c -lossless` and
-`leon -d -test-file` on a FASTQ in /dev/shm) -- none of them is ever `value`; --quick skips them.
+`value` is the HBM-resident figure (the bench contract: inputs resident when the timed region starts).  A plain run does
+only what that figure needs: set-up, the warm-up steps, the timed steps, the outputs (--dump-outputs DIR) and the line.
+--full adds everything else, none of it ever `value`: SURVEY 8(d)'s figure with the H2D copy inside (`pcie_inclusive`:
+one step through leon_dna_encode_batch, reads in pageable host memory), `verify` (checksum of block checksums), `decode`
+(the whole file back through the device decoder, compared with the input), `streams`, `end_to_end` (`leon -c -lossless`
+and `leon -d -test-file` on a FASTQ in a RAM-backed temporary directory), `structured`, `other_configs` and
+`cpu_baseline`; --full --quick keeps only `cpu_baseline` of them.
+
+--dump-outputs DIR: after the timed steps, what the last one handed its caller (the blocks through the sink, the dictionary
+stream from leon_dna_finish) as DIR/<name>.npy, float64 / float32, sampled with a fixed seed (OutputDump); the inputs are
+the same from run to run, so two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -68,11 +74,16 @@ def parse():
                     help="N > 1: how a batch's walk is divided among the ranks -- `block`: every rank walks the reads of its own block range (no exchange); "
                          "`anchor`: rank r walks the r-th slice of the batch's reads sorted by anchor address and the walk events reach the rank that codes the "
                          "read's block through one all-to-all per batch (leon_dna_set_exchange); auto = anchor")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside `value`: pcie_inclusive, verify, decode, streams, "
+                         "end_to_end, structured, other_configs, cpu_baseline (a plain run: set-up, warm-up, the timed steps, the line)")
     ap.add_argument("--quick", action="store_true",
-                    help="only the timed steps, roofline and cpu_baseline: skip pcie_inclusive / verify / decode / streams / end_to_end")
-    ap.add_argument("--decode", action="store_true", help="(always on at N = 1 unless --quick) decode the whole file on the device and compare it with the input")
-    ap.add_argument("--verify", action="store_true", help="(always on unless --quick) one more UNTIMED step whose sink hashes every block")
-    ap.add_argument("--host-input", action="store_true", help="(always on at N = 1 unless --quick) one step through leon_dna_encode_batch, PCIe included")
+                    help="with --full: only the timed steps, roofline and cpu_baseline: skip pcie_inclusive / verify / decode / streams / end_to_end / structured / other_configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step handed its caller (blocks, dictionary stream; a fixed, seeded sample) as DIR/<name>.npy")
+    ap.add_argument("--decode", action="store_true", help="(always on with --full at N = 1 unless --quick) decode the whole file on the device and compare it with the input")
+    ap.add_argument("--verify", action="store_true", help="(always on with --full unless --quick) one more UNTIMED step whose sink hashes every block")
+    ap.add_argument("--host-input", action="store_true", help="(always on with --full at N = 1 unless --quick) one step through leon_dna_encode_batch, PCIe included")
     ap.add_argument("--e2e-reads", type=int, default=int(os.environ.get("LEON_BENCH_E2E_READS", 10_000_000)),
                     help="reads of the FASTQ that `end_to_end` takes through the leon CLI (0 = skip)")
     ap.add_argument("--other-configs", default=os.environ.get("LEON_BENCH_OTHER_CONFIGS"),
@@ -81,10 +92,13 @@ def parse():
     ap.add_argument("--structured-reads", type=int, default=int(os.environ.get("LEON_BENCH_STRUCTURED_READS", 10_000_000)),
                     help="reads of the `structured` entry: a file with repeats, duplicates, coverage skew and ragged lengths in genome-position order (0 = skip)")
     ap.add_argument("--streams", action="store_true",
-                    help="(always on at N = 1 unless --quick) also time the kernels of the streams either side of the DNA stream on device-resident synthetic data: the header "
+                    help="(always on with --full at N = 1 unless --quick) also time the kernels of the streams either side of the DNA stream on device-resident synthetic data: the header "
                          "stream (records + range coder, 10 M SRA-style headers) and the lossy quality smoothing (the workload's reads); "
                          "reported as `streams`, never as value")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def gen_genome(G, device):
@@ -348,6 +362,61 @@ def walk_source_id():
     for f in ("dna_kernels.hip", "leon_device.h"):
         h.update(open(os.path.join(ROOT, "leon_amd", "csrc", f), "rb").read())
     return h.hexdigest()[:16]
+
+
+class OutputDump:
+    """--dump-outputs: what the timed path handed its caller in the last step -- every block (id, payload, reads) through the sink,
+    the dictionary stream and its anchor count from leon_dna_finish -- as .npy files, counts and sizes in float64, bytes in float32.
+    The payloads are sampled with a fixed seed (a 100 M-read step hands over 0.74 GB): every block's size and reads, its bytes at the
+    same PER_BLOCK relative positions (a range coder's output differs from the first differing symbol on), WHOLE_BLOCKS blocks whole (at
+    most WHOLE_BYTES bytes of them); the dictionary stream whole up to DICT_BYTES bytes, else at DICT_BYTES fixed relative positions.
+    At most ~40 MB in all.  take() runs inside the timed step (a few microseconds per block); write() after it."""
+    SEED = 20240601
+    PER_BLOCK = 256
+    SAMPLE_BUDGET = 16 << 20            # bytes of block_byte_samples.npy at most
+    WHOLE_BLOCKS = 8
+    WHOLE_BYTES = 4 << 20
+    DICT_BYTES = 2 << 20
+
+    def __init__(self, n_blocks):
+        rng = np.random.default_rng(self.SEED)
+        per = max(8, min(self.PER_BLOCK, self.SAMPLE_BUDGET // 4 // max(n_blocks, 1)))
+        self.frac = np.sort(rng.random(per))
+        self.frac[0] = 0.0                                     # the first byte always
+        self.whole_ids = {int(b) for b in rng.choice(n_blocks, min(self.WHOLE_BLOCKS, n_blocks), replace=False)} if n_blocks else set()
+        self.dict_frac = np.sort(rng.random(self.DICT_BYTES))
+        self.blocks, self.whole = [], {}
+
+    def take(self, block_id, p, size, n_reads):
+        """one block as the sink receives it: p = the payload (the sink's uint8 pointer, or an address)"""
+        sample = np.full(len(self.frac), -1.0, dtype=np.float32)
+        if size:
+            view = np.frombuffer((ctypes.c_char * size).from_address(ctypes.cast(p, ctypes.c_void_p).value), dtype=np.uint8)
+            sample[:] = view[(self.frac * size).astype(np.int64)]
+            if block_id in self.whole_ids:
+                self.whole[block_id] = ctypes.string_at(p, size)
+        self.blocks.append((block_id, size, n_reads, sample))
+
+    def write(self, out_dir, dict_stream, n_anchors):
+        os.makedirs(out_dir, exist_ok=True)
+        blocks = sorted(self.blocks, key=lambda b: b[0])
+        whole = b"".join(self.whole[b] for b in sorted(self.whole))[:self.WHOLE_BYTES]
+        d = np.frombuffer(dict_stream, dtype=np.uint8)
+        if len(d) > self.DICT_BYTES:
+            d = d[(self.dict_frac * len(d)).astype(np.int64)]
+        arrays = {
+            "block_ids": np.array([b[0] for b in blocks], dtype=np.float64),
+            "block_bytes": np.array([b[1] for b in blocks], dtype=np.float64),
+            "block_reads": np.array([b[2] for b in blocks], dtype=np.float64),
+            "block_byte_samples": np.stack([b[3] for b in blocks]) if blocks else np.zeros((0, len(self.frac)), dtype=np.float32),
+            "whole_block_ids": np.array(sorted(self.whole), dtype=np.float64),
+            "whole_blocks": np.frombuffer(whole, dtype=np.uint8).astype(np.float32),
+            "dictionary_info": np.array([len(dict_stream), n_anchors], dtype=np.float64),
+            "dictionary": d.astype(np.float32),
+        }
+        for name, arr in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), arr)
+        return {"dir": out_dir, "files": len(arrays), "bytes": int(sum(arr.nbytes for arr in arrays.values())), "blocks": len(blocks)}
 
 
 class Watch:
@@ -622,9 +691,23 @@ def main():
         acc["host_reset_ms"], acc["host_encode_calls_ms"] = (t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3
         return acc
 
-    def step():
+    dump = OutputDump(n_blocks) if a.dump_outputs and is_root else None
+
+    def dump_sink(user, block_id, p, size, n_reads):
+        payload[0] += size
+        payload[1] += 1
+        try:
+            dump.take(int(block_id), p, int(size), int(n_reads))
+        except Exception:                                        # noqa: BLE001 -- a non-zero return fails the step (LEON_E_SINK)
+            import traceback
+            traceback.print_exc()
+            return 1
+        return 0
+    dump_cb = capi.SINK(dump_sink)
+
+    def step(the_sink=cb):
         payload[0] = payload[1] = 0
-        acc = encode_stream(cb)
+        acc = encode_stream(the_sink)
         t0 = time.perf_counter()
         d_size, na = ctx.finish(copy=False)                  # the stream stays in the context, as for a C caller
         acc["host_finish_ms"] = (time.perf_counter() - t0) * 1e3
@@ -662,8 +745,8 @@ def main():
     times, walk_ms, walk_n, dev_ms, chain_ms, emul_ms, stage = [], [], [], [], [], [], None
     sync()
     t_begin = t_prev = time.perf_counter()
-    for _ in range(a.steps):
-        dict_bytes, n_anchors, acc = step()
+    for i in range(a.steps):
+        dict_bytes, n_anchors, acc = step(dump_cb if dump is not None and i == a.steps - 1 else cb)
         now = time.perf_counter()
         times.append(now - t_prev)
         t_prev = now
@@ -689,7 +772,13 @@ def main():
     ms_per_step = total_s / a.steps * 1e3
     value = n_total * L / 1e6 / (total_s / a.steps)
 
-    extras = not a.quick
+    outputs = None
+    if dump is not None:                                         # leon_dna_finish again: the last step's stream, still in the context
+        dstream, na_d = ctx.finish()
+        outputs = dump.write(a.dump_outputs, dstream, na_d)
+        del dstream
+
+    extras = a.full and not a.quick
     verify = None
     if a.verify or extras:
         import hashlib
@@ -812,7 +901,7 @@ def main():
     decode = guarded(do_decode) if (a.decode or extras) and world == 1 else None
     streams = guarded(lambda: bench_streams(ctx, capi, reads, offsets, n_total, device)) if (a.streams or extras) and world == 1 else None
     e2e = guarded(lambda: end_to_end(min(a.e2e_reads, n_total), device)) if extras and world == 1 and rank == 0 and a.e2e_reads > 0 else None
-    cpu = guarded(lambda: cpu_baseline(ctx, reads, a.cpu_sample)) if rank == 0 and world == 1 and a.cpu_sample > 0 else None
+    cpu = guarded(lambda: cpu_baseline(ctx, reads, a.cpu_sample)) if a.full and rank == 0 and world == 1 and a.cpu_sample > 0 else None
     # a file with real-genome structure in genome-position order, and BASELINE's other single-GPU configurations: each with a context of its own
     structured = None
     if extras and world == 1 and not as_rank and a.structured_reads > 0:
@@ -843,7 +932,8 @@ def main():
     if is_root:
         out = {
             "metric": "compressed input MB/s (DNA encode path)", "value": round(value, 1), "unit": "MB/s",
-            "n_gpus": pg_world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 2),
+            "n_gpus": pg_world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 2), "full": a.full,
+            **({"outputs": outputs} if outputs else {}),
             **({"as_rank": as_rank, "as_rank_note": "ONE process in the seat of rank %d of a %d-rank job (leon_dna_set_shard): `value` and `ms_per_step` are the wall time "
                                                      "MINUS what this process did in the other ranks' stead (ms_emulated: their slices of the walk, their window look-ups), and at least the seat's dictionary chain (rank 0's) -- what that job would "
                                                      "report if this rank were its slowest, not a measured %d-GPU figure; host threads for the blocks' chains as on a node that grants every rank this box's CPUs (LEON_RC_HOST_THREADS=%s)" % (rank, world, world, os.environ.get("LEON_RC_HOST_THREADS"))} if as_rank else {}),

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT
 cd $R
 O=gpurun_out/r3z
 mkdir -p $O
-timeout -k 10 500 python bench.py > $O/bench_default_100M.json 2> $O/bench_default.err || exit 1
+timeout -k 10 500 python bench.py --full > $O/bench_default_100M.json 2> $O/bench_default.err || exit 1
 timeout -k 10 300 python bench.py --reads 10000000 --steps 5 --warmup 2 --cpu-sample 0 --quick > $O/bench_config2_10M.json 2> $O/cfg2.err || exit 1
 LEON_BENCH_K=63 LEON_BENCH_L=250 timeout -k 10 300 python bench.py --reads 20000000 --steps 3 --warmup 1 --cpu-sample 0 --quick > $O/bench_k63_L250_20M.json 2> $O/k63.err || exit 1
 cd /tmp && export TMPDIR=/tmp

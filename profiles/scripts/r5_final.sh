@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT
 cd $R
 O=gpurun_out/r5f
 mkdir -p $O
-timeout -k 10 600 python bench.py > $O/bench_default_100M.json 2> $O/bench_default.err || exit 1
+timeout -k 10 600 python bench.py --full > $O/bench_default_100M.json 2> $O/bench_default.err || exit 1
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -- python3 $R/bench.py --steps 3 --warmup 1 --cpu-sample 0 --quick > $R/$O/bench_under_rocprof_100M.json 2> $R/$O/prof.err || exit 1
 DECODE=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_sorted -- python3 $R/profiles/scripts/structured_case.py 10000000 sorted > $R/$O/structured_sorted_10M_under_rocprof.json 2> $R/$O/prof_sorted.err || exit 1

@@ -107,3 +107,55 @@ def test_watch_names_the_collective_and_exits(tmp_path):
     script = "import sys\nsys.path.insert(0, %r)\nimport bench\nw = bench.Watch(0, None)\nwith w('broadcast (x)'):\n    raise RuntimeError('boom')\n" % ROOT
     p = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, timeout=60)
     assert p.returncode == 3 and "broadcast (x)" in p.stderr and "boom" in p.stderr
+
+
+def test_output_dump_samples_blocks_and_dictionary_within_64_mb(tmp_path):
+    """bench.OutputDump (--dump-outputs): float64 counts and sizes, float32 bytes; the same blocks in any delivery order give the same
+    files; the per-block samples are the payload's bytes; at the largest shape (configuration #5's 10 000 blocks) under 64 MB"""
+    rng = np.random.default_rng(5)
+    blocks = {b: rng.integers(0, 256, int(rng.integers(1, 5000)), dtype=np.uint8) for b in range(40)}
+    blocks[7] = np.zeros(0, dtype=np.uint8)                     # an empty block
+    dstream = rng.integers(0, 256, 3 << 20, dtype=np.uint8).tobytes()
+
+    import ctypes
+    from leon_amd import capi
+
+    def run(order, out):
+        d = bench.OutputDump(len(blocks))
+        sink = capi.SINK(lambda user, bid, p, size, nreads: (d.take(int(bid), p, int(size), int(nreads)), 0)[1])    # as the library calls it
+        for b in order:
+            assert sink(None, b, ctypes.cast(blocks[b].ctypes.data, ctypes.POINTER(ctypes.c_uint8)), len(blocks[b]), 100 + b) == 0
+        return d.write(str(out), dstream, 12345)
+    info = run(range(40), tmp_path / "a")
+    run(reversed(range(40)), tmp_path / "b")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert info["files"] == len(names) == 8
+    for n in names:
+        a, b = np.load(str(tmp_path / "a" / n)), np.load(str(tmp_path / "b" / n))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    got = {n[:-4]: np.load(str(tmp_path / "a" / n)) for n in names}
+    assert got["block_ids"].tolist() == list(range(40)) and got["block_reads"].tolist() == [100 + b for b in range(40)]
+    assert got["block_bytes"].tolist() == [len(blocks[b]) for b in range(40)]
+    d = bench.OutputDump(len(blocks))
+    for b in range(40):
+        want = blocks[b][(d.frac * len(blocks[b])).astype(np.int64)] if len(blocks[b]) else np.full(len(d.frac), -1)
+        assert np.array_equal(got["block_byte_samples"][b], want), b
+    whole = np.concatenate([blocks[int(b)] for b in got["whole_block_ids"]]).astype(np.float32)
+    assert len(got["whole_block_ids"]) == 8 and np.array_equal(got["whole_blocks"], whole)
+    assert got["dictionary_info"].tolist() == [3 << 20, 12345] and got["dictionary"].size == bench.OutputDump.DICT_BYTES
+    # worst case: 10 000 blocks of 600 KB and a 200 MB dictionary stream
+    big = bench.OutputDump(10000)
+    one = np.full(600_000, 3, dtype=np.uint8)
+    for b in range(10000):
+        big.take(b, one.ctypes.data, len(one), 50000)
+    info = big.write(str(tmp_path / "c"), b"\1" * (200 << 20), 1)
+    assert info["bytes"] < 64 << 20
+    assert sum(os.path.getsize(str(tmp_path / "c" / n)) for n in os.listdir(tmp_path / "c")) < 64 << 20
+
+
+def test_bench_options():
+    """--full and --dump-outputs exist; --steps below 1 is refused before anything is set up"""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and "--steps" in p.stderr

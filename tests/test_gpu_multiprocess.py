@@ -34,7 +34,8 @@ def _bench(world, extra_env=None, extra_args=(), launcher=True):
     env.update(extra_env or {})
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(v, None)
-    args = ["bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "0", "--reads", str(READS), "--cpu-sample", "0", "--e2e-reads", "0"] + list(extra_args)
+    args = ["bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "0", "--reads", str(READS), "--cpu-sample", "0", "--e2e-reads", "0",
+            "--full"] + list(extra_args)
     if world == 1 or not launcher:
         cmd = [sys.executable] + args
     else:
@@ -69,13 +70,13 @@ def test_two_and_three_process_runs_reproduce_the_single_process_stream():
 
 
 def test_default_bench_line_fills_every_key():
-    """the driver's `python bench.py` line: value beside the H2D-inclusive figure, verify, decode, end_to_end, roofline and
+    """the `python bench.py --full` line: value beside the H2D-inclusive figure, verify, decode, end_to_end, roofline and
     cpu_baseline -- none of them null at N = 1 (small sizes here; the keys and their checks are what is tested)"""
     env = dict(os.environ)
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(v, None)
     cmd = [sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--reads", "1000000", "--batch-reads", "400000", "--cpu-sample", "100000",
-           "--e2e-reads", "200000", "--other-configs", "200000:31:150,100000:63:250"]
+           "--e2e-reads", "200000", "--other-configs", "200000:31:150,100000:63:250", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-4000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -101,6 +102,45 @@ def test_default_bench_line_fills_every_key():
     # the same file as ONE batch: same bytes
     one = _bench(1, extra_args=("--reads", "1000000"))
     assert one["verify"]["blocks_sha256"] == line["verify"]["blocks_sha256"] and one["verify"]["dict_sha256"] == line["verify"]["dict_sha256"]
+
+
+def test_plain_run_is_lean_and_dumps_the_last_steps_outputs(tmp_path):
+    """a plain `bench.py --gpus 1 --steps N --warmup W` run: N timed steps and the line, nothing of --full; --dump-outputs DIR writes what
+    the last step handed its caller (blocks, dictionary stream) as float32 / float64 .npy files, under 64 MB, the same from run to run"""
+    import numpy as np
+    env = dict(os.environ)
+    for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LEON_BENCH_AS_RANK"):
+        env.pop(v, None)
+    dirs, lines = [tmp_path / "a", tmp_path / "b"], []
+    for d in dirs:
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--reads", str(READS), "--dump-outputs", str(d)]
+        p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-4000:]
+        out = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and len(line["step_ms_rank0"]) == 3 and line["full"] is False
+    assert line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True and line["unit"] == "MB/s"
+    for key in ("pcie_inclusive", "decode", "verify", "streams", "end_to_end", "structured", "other_configs", "cpu_baseline"):
+        assert line[key] is None, key
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and all(n.endswith(".npy") for n in names)
+    arr = {n[:-4]: np.load(str(dirs[0] / n)) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in arr.values())
+    assert sum(v.nbytes for v in arr.values()) < 64 << 20 and line["outputs"]["files"] == len(names)
+    for n in names:
+        assert np.array_equal(arr[n[:-4]], np.load(str(dirs[1] / n))), n
+    # what the caller received: every block once, its reads, the payload bytes and anchors the line counts
+    assert arr["block_ids"].tolist() == list(range(READS // 50000)) and arr["block_reads"].sum() == READS
+    assert arr["block_bytes"].sum() + arr["dictionary_info"][0] == line["rank0"]["payload_bytes"]
+    assert arr["dictionary_info"][1] == line["rank0"]["anchors"] and arr["dictionary"].size > 0
+    # the blocks kept whole start with the byte the per-block sample took first
+    at = 0
+    for bid in arr["whole_block_ids"].astype(int):
+        assert arr["whole_blocks"][at] == arr["block_byte_samples"][bid][0]
+        at += int(arr["block_bytes"][bid])
+    assert at == arr["whole_blocks"].size
 
 
 def test_a_rank_that_never_arrives_ends_the_job_by_name():

@@ -15,6 +15,19 @@ def _lib(name):
     return p if os.path.isabs(p) and os.path.exists(p) else None
 
 
+def _without_aslr():
+    """the prefix that starts a child with its address space unrandomised (setarch -R: a personality flag of that child alone), or [].
+    ThreadSanitizer expects the executable and the libraries in fixed ranges; where the kernel randomises mmap with more bits than it was
+    built for (vm.mmap_rnd_bits = 32), a position-independent executable lands outside them and TSan stops at start-up with "unexpected
+    memory mapping" before the program runs (newer TSan runtimes re-execute themselves without ASLR for this; this toolchain's does not)."""
+    import platform
+    import shutil
+    cmd = ["setarch", platform.machine(), "-R"]
+    if shutil.which("setarch") and subprocess.run(cmd + ["true"], capture_output=True).returncode == 0:
+        return cmd
+    return []
+
+
 def test_host_decoders_under_asan_ubsan(tmp_path):
     asan, ubsan = _lib("libasan.so"), _lib("libubsan.so")
     if not asan or not ubsan:
@@ -42,11 +55,12 @@ def test_dictionary_chain_worker_under_sanitizers(tmp_path, san):
     exe = str(tmp_path / "chain_san")
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=" + san, "-fno-omit-frame-pointer", "-o", exe,
                            os.path.join(ROOT, "profiles", "scripts", "chain_ab", "ab_new.cpp"), "-lpthread"])
+    prefix = _without_aslr() if san == "thread" else []
     seen = {}
     # ~1.9 M symbols each: 58 segments round a ring of 8 buffers several times, inside the default 512, and with one helper whose five
     # spares do most of the work (the look-ahead never leaves the low-water zone of a ring of 64)
     for n, k, ring, helpers, spares in ((60000, 31, "8", "3", "3"), (30000, 63, "8", "3", "3"), (60000, 31, "512", "3", "3"), (60000, 31, "64", "1", "5")):
-        r = subprocess.run([exe, str(n), str(k)], capture_output=True, text=True, timeout=600,
+        r = subprocess.run(prefix + [exe, str(n), str(k)], capture_output=True, text=True, timeout=600,
                            env=dict(os.environ, LEON_CHAIN_RING=ring, LEON_CHAIN_HELPERS=helpers, LEON_CHAIN_SPARES=spares,
                                     TSAN_OPTIONS="halt_on_error=1", ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1"))
         out = r.stdout + r.stderr
