@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -257,6 +258,85 @@ struct Upload {
 };
 constexpr uint32_t kRbHostChainsErr = 500;   // slot of the pinned read-back words (h_rb, 512 of them) the host chains' first chunk brings the modelers' error flag to
 int ensure_cub(leon_dna_ctx* c, size_t bytes) { HIPCHK(c, c->cub_tmp.ensure(bytes)); return LEON_OK; }
+// a rocPRIM call in its two steps: asked for the work space it needs, then run in c->cub_tmp grown to that
+template <typename F> int run_prim(leon_dna_ctx* c, F&& call) {
+    size_t bytes = 0;
+    HIPCHK(c, call(nullptr, bytes));
+    if (int rc = ensure_cub(c, bytes)) return rc;
+    HIPCHK(c, call(c->cub_tmp.p, bytes));
+    return LEON_OK;
+}
+
+// The batch buffers of a stage, sized by the stage and by leon_dna_reserve alike.
+int ensure_pack_bufs(leon_dna_ctx* c, uint64_t n, uint64_t n_slots) {
+    HIPCHK(c, c->packed.ensure((n_slots * 2 + 16) * 4)); HIPCHK(c, c->nmask.ensure((n_slots + 4) * 4));   // (wave loads reach 12 dwords past a pass start)
+    HIPCHK(c, c->rlen.ensure(n * 4)); HIPCHK(c, c->ncount.ensure(n * 4));
+    return LEON_OK;
+}
+int ensure_resolve_bufs(leon_dna_ctx* c, uint64_t n, uint64_t W) {
+    HIPCHK(c, c->status.ensure(n));
+    HIPCHK(c, c->hit_pos.ensure(n * 4)); HIPCHK(c, c->hit_slot.ensure(n * 4));
+    HIPCHK(c, c->cand_pos.ensure(n * 4)); HIPCHK(c, c->cand_slot.ensure(n * 4));
+    HIPCHK(c, c->anchor_pos.ensure(n * 4)); HIPCHK(c, c->anchor_addr.ensure(n * 4));
+    HIPCHK(c, c->flags.ensure(n)); HIPCHK(c, c->sort_key.ensure(n * 8));
+    HIPCHK(c, c->ins_flag.ensure(W * 4)); HIPCHK(c, c->rank.ensure(W * 4));
+    HIPCHK(c, c->ulist0.ensure(W * 4)); HIPCHK(c, c->ulist1.ensure(W * 4));
+    return LEON_OK;
+}
+int ensure_block_bufs(leon_dna_ctx* c, uint64_t nbl) {                  // the blocks' symbol ranges and payload offsets
+    HIPCHK(c, c->blk_begin.ensure((nbl + 1) * 8)); HIPCHK(c, c->out_off.ensure((nbl + 1) * 8));
+    HIPCHK(c, c->out_size.ensure(nbl * 8)); HIPCHK(c, c->dst_off.ensure((nbl + 1) * 8));
+    return LEON_OK;
+}
+int ensure_rc_bufs(leon_dna_ctx* c, uint64_t nbl, uint64_t n_syms) {     // k_rc_encode's output and models
+    HIPCHK(c, c->rc_out.ensure(3 * n_syms + 72 * (nbl + 1)));
+    HIPCHK(c, c->rc_scratch.ensure(rc_model_scratch_bytes(nbl)));
+    return LEON_OK;
+}
+// the pinned buffer the payloads of a launch cross to: `want` bytes when it holds fewer than `need`
+int ensure_host_payload(leon_dna_ctx* c, size_t need, size_t want) {
+    if (need <= c->h_payload_cap) return LEON_OK;
+    if (c->h_payload) HIPCHK(c, hipHostFree(c->h_payload));
+    c->h_payload = nullptr; c->h_payload_cap = 0;
+    HIPCHK(c, hipHostMalloc(&c->h_payload, want, hipHostMallocDefault));
+    c->h_payload_cap = want;
+    return LEON_OK;
+}
+
+// Where rank `rank` of `world` begins its share of a batch of n_blocks blocks: the share is the contiguous range of whole blocks
+// [block_start(rank), block_start(rank + 1)), all of them when world is 1.
+uint64_t block_start(uint64_t n_blocks, uint64_t rank, uint64_t world) { return rank * (n_blocks / world) + std::min(rank, n_blocks % world); }
+// this context's rank's share of a batch of n reads: blocks [lb0, lb0 + nbl), reads [r0, r0 + nl)
+struct Share { uint64_t lb0, nbl, r0, nl; };
+Share share_of(const leon_dna_ctx* c, uint64_t n) {
+    const uint64_t rpb = c->cfg.reads_per_block, n_blocks = (n + rpb - 1) / rpb;
+    const uint64_t lb0 = block_start(n_blocks, c->shard_rank, c->shard_world), lb1 = block_start(n_blocks, c->shard_rank + 1, c->shard_world);
+    const uint64_t r0 = std::min(n, lb0 * rpb), r1 = std::min(n, lb1 * rpb);
+    return {lb0, lb1 - lb0, r0, r1 - r0};
+}
+
+// The walk's path cache: a 64-byte bucket per ~8 solid k-mers (the bloom's size says how many), at most 2^27 = 8 GiB; 0: none.  Not for a job of
+// three ranks or more: the walkers of one genome region are spread over all ranks' slices, a rank's cache would cost as much as it saves.
+uint64_t walk_cache_buckets(const leon_dna_ctx* c) {
+    uint64_t buckets = 1024;
+    while (buckets < c->cfg.bloom_tai / 12 / 8 && buckets < (1ull << 27)) buckets <<= 1;
+    return c->B.n_hash == 7 && c->shard_world <= 2 ? buckets : 0;
+}
+
+// pair i of a batch's event pairs (c->pack_ev, c->chain_ev), created the first time a batch needs it
+int event_pair(leon_dna_ctx* c, std::vector<hipEvent_t>& ev, uint32_t i) {
+    while (ev.size() < 2 * (size_t)(i + 1)) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); ev.push_back(e); }
+    return LEON_OK;
+}
+float ms_since(std::chrono::steady_clock::time_point t) { return (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
+// the time inside event pairs [e0, e1)
+float pairs_ms(const std::vector<hipEvent_t>& ev, uint32_t e0, uint32_t e1) {
+    float t = 0;
+    for (uint32_t e = e0; e < e1; e++) { float v = 0; (void)hipEventElapsedTime(&v, ev[2 * e], ev[2 * e + 1]); t += v; }
+    return t;
+}
+
+const char* const kPoisonedNote = " (stream poisoned: leon_dna_reset_stream to go on)";
 
 }  // namespace
 
@@ -421,6 +501,94 @@ int rc_blocks_on_host(leon_dna_ctx* c, const uint8_t* d_syms, const uint64_t* d_
         fprintf(stderr, "[leon rc host] %llu blocks, %llu symbols, %u chunks, %u threads, launches enqueued at %.1f ms:", (unsigned long long)nbl, (unsigned long long)n_syms, n_chunks, n_thr, t_enqueued);
         for (uint32_t ch = 0; ch < n_chunks; ch++) fprintf(stderr, " chunk %u in host memory at %.1f ms, coded at %.1f;", ch, t_copied[ch], t_coded[ch]);
         fprintf(stderr, " done at %.1f ms\n", ms_now());
+    }
+    return LEON_OK;
+}
+
+// A share's coded blocks, in block order: block b's sizes[b] bytes are hb_coders[b]'s (host chains) or at h_payload + dst[b].
+struct CodedBlocks {
+    bool host_chains = false; uint64_t n_syms = 0, payload_bytes = 0;
+    std::vector<uint64_t> sizes, dst;
+};
+
+// The block-coding tail of a stream, the DNA stream's and the header stream's: the share's symbols, counted then emitted by `symbols`
+// (nullptr: the count pass; the counts, then the offsets, in c->sym_off indexed from the share's first read), cut into blocks, the blocks'
+// chains coded on host cores or by k_rc_encode, the payloads brought to host memory.  ev[6] / [7] / [8]: symbols / range coder / D2H done.
+int code_blocks(leon_dna_ctx* c, const Share& sh, const std::function<void(uint8_t* syms)>& symbols, uint32_t small_sizes, bool counts_apart,
+                const char* unit, CodedBlocks& out) {
+    hipStream_t s = c->stream;
+    const uint64_t rpb = c->cfg.reads_per_block, nl = sh.nl, nbl = sh.nbl;
+    HIPCHK(c, c->sym_off.ensure((nl + 1) * 8));
+    uint64_t* const sym_off = c->sym_off.as<uint64_t>();
+    HIPCHK(c, hipMemsetAsync(sym_off + nl, 0, 8, s));
+    symbols(nullptr);
+    if (int rc = run_prim(c, [&](void* t, size_t& b) { return prim::ExclusiveSum(t, b, sym_off, sym_off, nl + 1, s); })) return rc;
+    uint64_t max_block_syms = 0; unsigned long long* d_max = reinterpret_cast<unsigned long long*>(c->counters.as<uint32_t>() + 8);
+    HIPCHK(c, hipMemsetAsync(d_max, 0, 8, s));
+    launch_max_block_syms(s, sym_off, nl, rpb, nbl, d_max);
+    HIPCHK(c, hipMemcpyAsync(&out.n_syms, sym_off + nl, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(&max_block_syms, d_max, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const uint64_t n_syms = out.n_syms;
+    HIPCHK(c, c->syms.ensure(n_syms * 2 + 256));
+    symbols(c->syms.as<uint8_t>());
+    if (int rc = ensure_block_bufs(c, nbl)) return rc;
+    launch_block_ranges(s, sym_off, nl, rpb, nbl, c->blk_begin.as<uint64_t>(), c->out_off.as<uint64_t>());
+    HIPCHK(c, hipEventRecord(c->ev[6], s));
+
+    // ---- range coder ----
+    out.sizes.assign(nbl, 0); out.dst.assign(nbl + 1, 0);
+    out.host_chains = rc_on_host(nbl, n_syms, max_block_syms, c->shard_world);
+    if (out.host_chains) {
+        // a small launch: the chains run on host cores, from the modelers' records (host_blocks.h)
+        const int rc = rc_blocks_on_host(c, c->syms.as<uint8_t>(), c->blk_begin.as<uint64_t>(), nbl, n_syms, small_sizes, N_SMALL_MODELS);
+        if (rc == 1) out.host_chains = false;                    // (no room for the records: the device's coder)
+        else if (rc) return rc;
+    }
+    if (out.host_chains) {
+        HIPCHK(c, hipEventRecord(c->ev[7], s));
+        for (uint64_t b = 0; b < nbl; b++) out.sizes[b] = c->hb_coders[b].size();
+    } else {
+        if (int rc = ensure_rc_bufs(c, nbl, n_syms)) return rc;
+        HIPCHK(c, hipMemsetAsync(c->errflag.p, 0, 4, s));
+        launch_rc_encode(s, c->syms.as<uint8_t>(), c->blk_begin.as<uint64_t>(), nbl, c->rc_out.as<uint8_t>(), c->out_off.as<uint64_t>(),
+                         c->out_size.as<uint64_t>(), c->rc_scratch.as<uint32_t>(), c->errflag.as<int>(), max_block_syms, small_sizes, counts_apart);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->ev[7], s));
+        int errflag = 0;
+        HIPCHK(c, hipMemcpyAsync(out.sizes.data(), c->out_size.p, nbl * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&errflag, c->errflag.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        if (errflag == 3) return fail(c, LEON_E_STATE, "a numeric value's byte count above 8 in the symbol stream (internal error)");   // (counts_apart only)
+        if (errflag) return fail(c, LEON_E_OVERFLOW, errflag == 2 ? std::string("a ") + unit + " block has 2^32 symbols or more"
+                                                                  : std::string("range coder output exceeded its 3 bytes/symbol bound"));
+    }
+    for (uint64_t b = 0; b < nbl; b++) out.dst[b + 1] = out.dst[b] + out.sizes[b];
+    const uint64_t payload_bytes = out.payload_bytes = out.dst[nbl];
+    if (!out.host_chains) {
+        // ---- gather + D2H ----
+        HIPCHK(c, c->payload.ensure(payload_bytes + 16));
+        HIPCHK(c, hipMemcpyAsync(c->dst_off.p, out.dst.data(), (nbl + 1) * 8, hipMemcpyHostToDevice, s));
+        launch_gather_payload(s, c->rc_out.as<uint8_t>(), c->out_off.as<uint64_t>(), c->dst_off.as<uint64_t>(), c->out_size.as<uint64_t>(),
+                              nbl, c->payload.as<uint8_t>());
+        if (int rc = ensure_host_payload(c, payload_bytes + 16, payload_bytes + payload_bytes / 4 + 4096)) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->h_payload, c->payload.p, payload_bytes, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(c, hipEventRecord(c->ev[8], s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return LEON_OK;
+}
+
+// Leon::writeBlock, in block order, the batch's first block numbered first_block; a sink that refuses one poisons the stream
+int deliver_blocks(leon_dna_ctx* c, const CodedBlocks& out, const Share& sh, uint64_t n, uint64_t first_block, leon_block_sink sink, void* user) {
+    const uint64_t rpb = c->cfg.reads_per_block;
+    for (uint64_t b = 0; b < sh.nbl; b++) {
+        const uint32_t nr = (uint32_t)std::min<uint64_t>(rpb, n - (sh.lb0 + b) * rpb);
+        const uint8_t* pay = out.host_chains ? c->hb_coders[b].data() : (const uint8_t*)c->h_payload + out.dst[b];
+        if (sink(user, first_block + sh.lb0 + b, pay, out.sizes[b], nr)) {
+            c->poisoned = true;                                  // the caller holds part of the batch's blocks
+            return fail(c, LEON_E_SINK, "block sink returned non-zero");
+        }
     }
     return LEON_OK;
 }
@@ -625,8 +793,584 @@ int leon_dna_bloom_contains(leon_dna_ctx* c, const uint64_t* kmers, uint64_t n, 
 }
 
 // ------------------------------------------------------------------------------------------------ encode
+// reads [0, group_end(a)) are packed (and, through the host entry point, uploaded) together: the first resolution window
+// alone, so that the device and the dictionary chain start at once, then groups of 8 windows
+// (the first window itself is short -- first_window() reads -- so that the first anchors reach the host chain, the longest
+// single piece of a step, a few milliseconds after the call starts; the result does not depend on where windows end)
+static uint64_t first_window(uint64_t window) { return std::min<uint64_t>(window, 1ull << 17); }
+static uint64_t group_end(uint64_t a, uint64_t n, uint64_t window) {
+    if (a == 0) return std::min(n, first_window(window));
+    // (resident input used to pack everything that was left in one go: 9.6 ms at 100 M reads between the first window and the
+    // second, during which the dictionary chain ran out of the first window's anchors and idled)
+    return std::min(n, a + 8 * std::min<uint64_t>(window, 1ull << 20));
+}
+
+namespace {
+
+// The encode path's knobs -- measurement aids and test hooks: any values give the same bytes --, read at the start of every batch
+// (the tests change them inside one process).
+struct EncodeKnobs {
+    uint32_t rounds_ahead, rounds_max;   // LEON_RESOLVE_ROUNDS=a[:m]: fixpoint rounds launched ahead (1..32, default 3) / at most (..62, default 9)
+    uint32_t chain_chunk;                // LEON_CHAIN_CHUNK: reads per k_chain_seq (<= 2^CHAIN_LOG2): the tests' way onto the chunk-by-chunk path
+    bool xch_lookups, walk_cache;        // LEON_XCH_LOOKUPS=0: a job's window look-ups not shared out among its ranks; LEON_WALK_CACHE=0: no path cache
+    long walk_cache_log2, walk_hop_log2; // LEON_WALK_CACHE_LOG2: log2 of the cache's buckets (10..31, else sized by the bloom); LEON_WALK_HOP_LOG2 (1..8, 4)
+    bool trace_step, trace_resolve, trace_chain;   // LEON_TRACE_STEP / _RESOLVE / _CHAIN, on stderr: host time of a batch's first milestones /
+                                                   //   what a read costs k_lookup_cand by its outcome / the sequential passes
+};
+long env_num(const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; }
+EncodeKnobs read_encode_knobs() {
+    const char* rounds = getenv("LEON_RESOLVE_ROUNDS");
+    const long ahead = env_num("LEON_RESOLVE_ROUNDS", 0), most = rounds && strchr(rounds, ':') ? atol(strchr(rounds, ':') + 1) : 0;
+    const long chunk = env_num("LEON_CHAIN_CHUNK", 0), hop = env_num("LEON_WALK_HOP_LOG2", 4);
+    EncodeKnobs K{};
+    K.rounds_ahead = ahead >= 1 && ahead <= 32 ? (uint32_t)ahead : 3u;
+    K.rounds_max = std::max<uint32_t>(K.rounds_ahead, most >= 1 && most <= 62 ? (uint32_t)most : 9u);
+    K.chain_chunk = chunk >= 1 && chunk <= (1l << CHAIN_LOG2) ? (uint32_t)chunk : 1u << CHAIN_LOG2;
+    K.xch_lookups = env_num("LEON_XCH_LOOKUPS", 1) != 0; K.walk_cache = env_num("LEON_WALK_CACHE", 1) != 0;
+    K.walk_cache_log2 = env_num("LEON_WALK_CACHE_LOG2", 0); K.walk_hop_log2 = hop >= 1 && hop <= 8 ? hop : 4;
+    K.trace_step = getenv("LEON_TRACE_STEP"); K.trace_resolve = getenv("LEON_TRACE_RESOLVE"); K.trace_chain = getenv("LEON_TRACE_CHAIN");
+    return K;
+}
+
+// One call of leon_dna_encode_batch on its way through the stages (each returns LEON_OK or the batch's error), and what they hand one another.
+struct EncodeBatch {
+    leon_dna_ctx* const c;
+    const uint8_t* const d_bases; const uint64_t* const d_off; const uint64_t n, first_read_index; const leon_block_sink sink; void* const user;
+    Upload* const up; const uint64_t* const up_off;   // the host entry point's upload of the bases and the caller's offsets (nullptr: device input)
+    const uint64_t* const walk_keys = c->walk_keys;   // leon_dna_debug_walk_order's: THIS batch only, whatever becomes of it
+    const EncodeKnobs knobs = read_encode_knobs();
+    const std::chrono::steady_clock::time_point t_enter = std::chrono::steady_clock::now();
+    const hipStream_t s = c->stream;
+    const uint32_t rpb = c->cfg.reads_per_block, k = c->cfg.kmer_size;
+    uint64_t n_blocks = 0, off_first = 0, off_last = 0, n_slots = 0, W = 0, KW = 0;   // W: reads per resolution window, KW: words per anchor k-mer
+    ReadsDev R{}; ResolveDev V{};
+    uint64_t packed_upto = 0; uint32_t n_pack_ev = 0;   // the pack: reads [0, packed_upto), between n_pack_ev pairs of c->pack_ev
+    // the anchor resolution: list counts ([0], [1]) and lists, the counts of a window's rounds, LEON_TRACE_RESOLVE's counts
+    static constexpr uint32_t kRoundsMore = 2, kHist = 64;
+    uint32_t* counters = nullptr; uint32_t* lists[2] = {nullptr, nullptr}; uint32_t* d_hist = nullptr; unsigned long long* d_trace = nullptr;
+    size_t scan_tmp = 0;                     // work space of the window scans
+    struct Pending { int buf = -1; uint64_t n = 0; } pending;      // a window's new anchors on their way to pinned memory
+    int anchor_buf = 0; bool share_lookups = false;
+    uint32_t hint = 0;                       // grid-size hint of a window's first round (any size is correct: grid-stride loops)
+    uint32_t n_chain_ev = 0;                 // pairs of c->chain_ev around the sequential passes
+    float lk_call_ms = 0, lk_emul_ms = 0;    // the shared look-ups' gathers / emulated runs
+    // this rank's share and its walk; divided by anchor: where the slices begin, where each rank's reads begin, a slice's words by destination
+    Share sh{}; uint64_t nl_bases = 0; bool by_anchor = false;
+    WalkCache wc{nullptr, 0, 28, 0};
+    std::vector<uint64_t> slice_at, rank_r0, send_counts, send_at; size_t scan_n = 0;
+    void mark(const char* what) const {
+        if (knobs.trace_step) fprintf(stderr, "[leon step] %-34s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count());
+    }
+    float ms(int a, int b) const { float v = 0; (void)hipEventElapsedTime(&v, c->ev[a], c->ev[b]); return v; }
+    // ---- everything that may fail before the stream changes: the offsets checked, the reads' 32-base slots counted and scanned,
+    // the first window's reads packed, the resolution's buffers ----
+    int start() {
+        c->stats = leon_dna_stats{}; c->walk_keys = nullptr;
+        HIPCHK(c, hipMemcpyAsync(c->h_rb + 0, d_off, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(c->h_rb + 1, d_off + n, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, spin_sync(s));
+        off_first = c->h_rb[0]; off_last = c->h_rb[1];
+        if (off_last < off_first) return fail(c, LEON_E_INVALID, "offsets are not monotonic");
+        n_blocks = (n + rpb - 1) / rpb;
+        HIPCHK(c, hipEventRecord(c->ev[0], s));
+        // ---- pack ----
+        HIPCHK(c, c->slot_off.ensure((n + 1) * 8));
+        uint64_t* slot_off = c->slot_off.as<uint64_t>();
+        HIPCHK(c, hipMemsetAsync(c->counters.as<uint32_t>() + 4, 0, 4, s));
+        launch_read_slots(s, d_off, n, slot_off, c->counters.as<uint32_t>() + 4);
+        if (int rc = run_prim(c, [&](void* t, size_t& b) { return prim::ExclusiveSum(t, b, slot_off, slot_off, n + 1, s); })) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->h_rb + 0, slot_off + n, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(c->h_rb + 1, c->counters.as<uint32_t>() + 4, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, spin_sync(s));
+        n_slots = c->h_rb[0];
+        if ((uint32_t)c->h_rb[1]) return fail(c, LEON_E_INVALID, "offsets are not monotonic (or a read is longer than 2^31 bases)");
+        mark("offsets checked, slots scanned");
+        if (int rc = ensure_pack_bufs(c, n, n_slots)) return rc;
+        HIPCHK(c, hipMemsetAsync(c->packed.as<uint32_t>() + n_slots * 2, 0, 64, s));
+        if (int rc = pack_next_group()) return rc;               // the first window's reads
+        HIPCHK(c, hipEventRecord(c->ev[1], s));
+        // ---- anchor resolution: its buffers ----
+        R = reads_view(c, d_off, n);
+        W = std::min<uint64_t>(c->cfg.resolve_window, n);
+        if (int rc = ensure_resolve_bufs(c, n, W)) return rc;
+        V.status = c->status.as<uint8_t>(); V.hit_pos = c->hit_pos.as<uint32_t>(); V.hit_slot = c->hit_slot.as<uint32_t>();
+        V.cand_pos = c->cand_pos.as<uint32_t>(); V.cand_slot = c->cand_slot.as<uint32_t>();
+        V.anchor_pos = c->anchor_pos.as<int32_t>(); V.anchor_addr = c->anchor_addr.as<uint32_t>(); V.flags = c->flags.as<uint8_t>();
+        V.sort_key = c->sort_key.as<uint64_t>(); V.ins_flag = c->ins_flag.as<uint32_t>();
+        counters = c->counters.as<uint32_t>(); lists[0] = c->ulist0.as<uint32_t>(); lists[1] = c->ulist1.as<uint32_t>();
+        HIPCHK(c, prim::ExclusiveSum(nullptr, scan_tmp, V.ins_flag, c->rank.as<uint32_t>(), W, s));
+        return ensure_cub(c, scan_tmp);
+    }
+    // The first resolution window's reads are packed first, later groups right before their first window: the host thread that codes the
+    // dictionary stream (the longest single piece of a step) gets its first anchors ~25 ms earlier, and with host input the upload of a
+    // group overlaps the resolution of the groups before it.
+    int pack_next_group() {
+        const uint64_t a = packed_upto, b = group_end(a, n, c->cfg.resolve_window);
+        if (up) {
+            // the group's last base, from the caller's offsets: checked before it is waited for (whatever the entries between
+            // the group boundaries are, the device checks them one by one and refuses the batch)
+            const uint64_t want = up_off[b];
+            if (want < up_off[0] || want > up_off[n] || want < up_off[a]) return fail(c, LEON_E_INVALID, "offsets are not monotonic");
+            while (up->bytes_done.load(std::memory_order_acquire) < want - up_off[0] && !up->failed.load()) std::this_thread::yield();
+            if (up->failed.load()) return fail(c, LEON_E_HIP, "upload of the read bases failed");
+        }
+        if (int rc = event_pair(c, c->pack_ev, n_pack_ev)) return rc;
+        HIPCHK(c, hipEventRecord(c->pack_ev[2 * n_pack_ev], s));
+        launch_pack(s, d_bases, d_off + a, c->slot_off.as<uint64_t>() + a, b - a, c->packed.as<uint32_t>(), c->nmask.as<uint32_t>(),
+                    c->rlen.as<uint32_t>() + a, c->ncount.as<uint32_t>() + a);
+        HIPCHK(c, hipEventRecord(c->pack_ev[2 * n_pack_ev + 1], s));
+        n_pack_ev++;
+        packed_upto = b;
+        return LEON_OK;
+    }
+    // Host round trips: a wait costs 20-40 us and the stage used to make ~6 per window (580 per 100 M reads: the window's first count,
+    // one per fixpoint round, the insert count, the new anchors' copy).  Now two: the rounds are launched AHEAD of their counts -- the
+    // kernels take the list lengths from device memory, an empty list costs a launch that finds nothing to do -- three at once, then two
+    // at a time for the few windows that need more, with every round's count copied to a small history that comes back with the
+    // next wait; and a window's new anchors travel to pinned memory behind the kernels and are handed to the dictionary chain at
+    // the NEXT window's first wait (the first window's at once: the chain, the longest piece of a step, starts with them).
+    int resolve() {
+        KW = kmer_words(k);
+        HIPCHK(c, c->round_hist.ensure(kHist * 4)); d_hist = c->round_hist.as<uint32_t>();
+        if (c->h_anchor_cap < W * 8 * KW) {
+            for (auto& b : c->h_anchor) { if (b) HIPCHK(c, hipHostFree(b)); b = nullptr; }
+            c->h_anchor_cap = 0;
+            for (auto& b : c->h_anchor) HIPCHK(c, hipHostMalloc((void**)&b, W * 8 * KW + 64, hipHostMallocDefault));
+            c->h_anchor_cap = W * 8 * KW;
+        }
+        if (knobs.trace_resolve) { HIPCHK(c, c->resolve_trace.ensure(12 * 8)); d_trace = c->resolve_trace.as<unsigned long long>(); HIPCHK(c, hipMemsetAsync(d_trace, 0, 12 * 8, s)); }
+        // the look-ups shared out among the ranks of a job (leon_dna_set_gather; LEON_XCH_EMULATE plays the other ranks)
+        share_lookups = c->shard_world > 1 && knobs.xch_lookups && ((c->xch_mode == LEON_XCH_BY_ANCHOR && c->gather_fn) || c->xch_mode == LEON_XCH_EMULATE);
+        hint = (uint32_t)std::min<uint64_t>(W, 1u << 20);
+        for (uint64_t w0 = 0, w1 = 0; w0 < n; w0 = w1) {
+            w1 = std::min(n, w0 + (w0 == 0 ? first_window(W) : W));
+            if (int rc = resolve_window(w0, w1)) return rc;
+            while (w1 < n && packed_upto < std::min(n, w1 + W)) { if (int rc = pack_next_group()) return rc; }   // the next window's reads
+            c->stats.resolve_windows++;
+        }
+        if (pending.buf >= 0) { HIPCHK(c, spin_sync(s)); hand_over(); }
+        if (knobs.trace_resolve) {
+            unsigned long long t[12];
+            HIPCHK(c, hipMemcpy(t, d_trace, sizeof t, hipMemcpyDeviceToHost));
+            const char* cls[3] = {"found an anchor of the dictionary", "went on to propose its own", "no anchor at all"};
+            for (int j = 0; j < 3; j++)
+                if (t[4 * j]) fprintf(stderr, "[leon resolve] k_lookup_cand, reads that %-34s: %10llu reads, per read %.1f filter probes, %.1f dictionary probes behind a filter maybe, %.1f k-mers through the bloom\n",
+                                      cls[j], t[4 * j], (double)t[4 * j + 1] / t[4 * j], (double)t[4 * j + 2] / t[4 * j], (double)t[4 * j + 3] / t[4 * j]);
+        }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->ev[2], s));
+        mark("resolution launched to its end");
+        return LEON_OK;
+    }
+    // one window [w0, w1): look-ups, fixpoint rounds (and the sequential pass behind them), the settled anchors to the dictionary
+    int resolve_window(uint64_t w0, uint64_t w1) {
+        if (int rc = dict_reserve(c, c->n_keys + (w1 - w0))) return rc;
+        HIPCHK(c, hipMemsetAsync(counters, 0, 8, s));
+        HIPCHK(c, hipMemsetAsync(c->wbits.p, 0, (1ull << WBITS_LOG2) / 8, s));
+        HIPCHK(c, hipMemsetAsync(c->pbits.p, 0, (1ull << WBITS_LOG2) / 8, s));
+        if (!share_lookups) launch_lookup_cand(s, R, c->B, c->d_rv16, c->D, V, w0, w1, first_read_index, lists[0], counters, d_trace);
+        else if (int rc = look_up_shared(w0, w1)) return rc;
+        HIPCHK(c, hipMemcpyAsync(d_hist, counters, 4, hipMemcpyDeviceToDevice, s));         // hist[0]: the window's unresolved reads
+        uint32_t cnt0 = 0;
+        if (int rc = fixpoint_rounds(w0, w1, cnt0)) return rc;
+        hint = std::max<uint32_t>(2 * cnt0, 4096);
+        if (cnt0 > 0) { if (int rc = settle(w0, w1)) return rc; }
+        launch_finalize_reads(s, R, c->D, V, w0, w1);
+        return LEON_OK;
+    }
+    // The window's look-ups divided among the ranks (leon_dna_set_gather): rank r takes the r-th run of P reads, everybody learns what
+    // everybody found from ONE all-gather of a word per read -- the caller's -- and makes the other runs' results its own (k_lookup_apply):
+    // every rank's dictionary goes on holding every proposal, as if it had looked everything up.
+    int look_up_shared(uint64_t w0, uint64_t w1) {
+        const uint32_t Wn = c->shard_world; const uint64_t P = (w1 - w0 + Wn - 1) / Wn;
+        auto run_of = [&](uint32_t r, uint64_t& a, uint64_t& b) { a = std::min(w1, w0 + (uint64_t)r * P); b = std::min(w1, a + P); };
+        HIPCHK(c, c->xch_res.ensure((uint64_t)Wn * P * 8)); uint64_t* xres = c->xch_res.as<uint64_t>();
+        uint64_t s0 = 0, s1 = 0; run_of(c->shard_rank, s0, s1);
+        launch_lookup_cand(s, R, c->B, c->d_rv16, c->D, V, s0, s1, first_read_index, lists[0], counters, d_trace, xres, w0, false);
+        HIPCHK(c, hipStreamSynchronize(s));
+        const auto t_l0 = std::chrono::steady_clock::now();
+        if (c->xch_mode == LEON_XCH_BY_ANCHOR) {
+            if (c->gather_fn(c->gather_user, xres, P * 8, Wn)) return fail(c, LEON_E_STATE, "the gather callback returned non-zero");
+            HIPCHK(c, hipSetDevice(c->device));               // (the callback may have changed the thread's device)
+            lk_call_ms += ms_since(t_l0);
+        } else {                                              // no other rank present: their runs computed here, leaving nothing but their words
+            for (uint32_t r = 0; r < Wn; r++) {
+                if (r == c->shard_rank) continue;
+                uint64_t a = 0, b = 0; run_of(r, a, b);
+                launch_lookup_cand(s, R, c->B, c->d_rv16, c->D, V, a, b, first_read_index, lists[0], counters, nullptr, xres, w0, true);
+            }
+            HIPCHK(c, hipStreamSynchronize(s));
+            lk_emul_ms += ms_since(t_l0);
+        }
+        launch_lookup_apply(s, R, c->D, V, w0, w1, s0, s1, first_read_index, xres, lists[0], counters);
+        return LEON_OK;
+    }
+    // The rounds are NOT asked to finish: their count is the longest chain of reads each waiting for the one before it, which no valid
+    // input bounds (reads in genome-position order make one chain of a whole window).  After knobs.rounds_ahead rounds -- more while the
+    // list keeps halving, knobs.rounds_max at most -- what is left goes, in read order, through the exact sequential pass (chain_tail).
+    // cnt0: the reads the window's look-ups left unresolved.
+    int fixpoint_rounds(uint64_t w0, uint64_t w1, uint32_t& cnt0) {
+        int cur = 0;
+        uint32_t n_hist = 1;
+        bool first_wait = true;
+        // (Fewer rounds ahead for a file whose last window left the sequential pass most of its list -- position-sorted reads -- were
+        // measured and are slower: rounds 2 and 3 settle the reads that contain round 1's inserters, 15 M of a sorted 100 M-read
+        // file's, in 180 ms; the sequential pass takes 18 ns for each of them.  1 929 ms against 1 838 for the stage.)
+        for (uint32_t ahead = knobs.rounds_ahead;; ahead = kRoundsMore) {
+            for (uint32_t r = 0; r < ahead && n_hist < kHist; r++) {
+                const int nxt = cur ^ 1;
+                const uint32_t h = std::max<uint32_t>(hint >> (2 * (n_hist - 1) < 31 ? 2 * (n_hist - 1) : 31), 4096);
+                HIPCHK(c, hipMemsetAsync(counters + nxt, 0, 4, s));
+                launch_check(s, R, c->D, V, first_read_index, lists[cur], counters + cur, h, lists[nxt], counters + nxt);
+                HIPCHK(c, hipMemcpyAsync(d_hist + n_hist, counters + nxt, 4, hipMemcpyDeviceToDevice, s));
+                launch_reset_tent(s, c->D, V, lists[cur], counters + cur, h);
+                launch_propose(s, c->D, V, first_read_index, lists[nxt], counters + nxt, h);
+                cur = nxt; n_hist++;
+            }
+            HIPCHK(c, hipMemcpyAsync(c->h_rb + 8, d_hist, n_hist * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipMemcpyAsync(c->h_rb + 1, c->D.err, 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, spin_sync(s));
+            if (first_wait) { hand_over(); first_wait = false; }
+            if (const int derr = (int)(uint32_t)c->h_rb[1]) {
+                HIPCHK(c, hipMemsetAsync(c->D.err, 0, 4, s));
+                return fail(c, LEON_E_STATE, derr == 2 ? "the look-ups gathered from the other ranks do not fit this rank's reads or dictionary (were all ranks fed the same batches?)"
+                                                       : "anchor dictionary: a two-word key stayed half-written (a stalled wave); batch abandoned");
+            }
+            const uint32_t* hist = reinterpret_cast<const uint32_t*>(c->h_rb + 8);
+            cnt0 = hist[0];
+            for (uint32_t r = 1; r < n_hist; r++)
+                if (hist[r - 1] > 0 && hist[r] >= hist[r - 1]) return fail(c, LEON_E_STATE, "anchor resolution made no progress (internal error)");
+            const uint32_t cnt = hist[n_hist - 1];
+            // more rounds only while they pay: the list at least halved in the last round and the budget is not spent
+            const bool halving = n_hist >= 2 && 2ull * hist[n_hist - 1] <= hist[n_hist - 2];
+            if (cnt == 0 || !halving || n_hist - 1 >= knobs.rounds_max || n_hist + kRoundsMore > kHist) {
+                for (uint32_t r = 1; r < n_hist; r++) if (hist[r - 1] > 0) c->stats.resolve_rounds++;
+                return cnt ? chain_tail(cnt, w0, w1, lists[cur ^ 1]) : LEON_OK;
+            }
+        }
+    }
+    // ---- the exact sequential pass behind the rounds (dna_kernels.hip, k_chain_*): the `left` reads the rounds did not settle ----
+    int chain_tail(uint32_t left, uint64_t w0, uint64_t w1, uint32_t* clist) {
+        if (int rc = event_pair(c, c->chain_ev, n_chain_ev)) return rc;
+        HIPCHK(c, hipEventRecord(c->chain_ev[2 * n_chain_ev], s));
+        // in read order: flags over the window, their ranks (a read's chain index), the compacted list
+        uint32_t* rank = c->rank.as<uint32_t>();
+        launch_chain_flags(s, V, w0, w1, V.ins_flag);
+        HIPCHK(c, prim::ExclusiveSum(c->cub_tmp.p, scan_tmp, V.ins_flag, rank, w1 - w0, s));
+        launch_chain_compact(s, V, w0, w1, rank, clist);
+        const uint32_t CH = knobs.chain_chunk;
+        unsigned long long* d_ctrace = nullptr;
+        if (knobs.trace_chain) { HIPCHK(c, c->chain_trace.ensure(8 * 8)); d_ctrace = c->chain_trace.as<unsigned long long>(); HIPCHK(c, hipMemsetAsync(d_ctrace, 0, 8 * 8, s)); }
+        for (uint32_t c0 = 0; c0 < left; c0 += CH) {
+            const uint32_t nc = std::min(CH, left - c0), nG = (nc + 63) / 64;
+            // a later chunk: tent still names reads of the chunk before (settled now) -- cleared, and what is left proposes again
+            if (c0) launch_chain_repropose(s, c->D, V, first_read_index, clist + (c0 - CH), left - (c0 - CH), clist + c0, left - c0);
+            HIPCHK(c, c->chain_cnt.ensure((uint64_t)nc * 4)); HIPCHK(c, c->chain_own.ensure((uint64_t)nc * 4));
+            HIPCHK(c, c->chain_ins.ensure(((uint64_t)nG + 1) * 8)); HIPCHK(c, c->chain_rows.ensure(((uint64_t)nG + 1) * 8));
+            HIPCHK(c, c->chain_dep.ensure((uint64_t)nc * 8)); HIPCHK(c, c->chain_xdep.ensure((uint64_t)nc * 8));
+            HIPCHK(c, c->chain_om.ensure((uint64_t)nG * 64 * 8)); HIPCHK(c, c->chain_late.ensure((uint64_t)nG * 8));
+            uint64_t* rows = c->chain_rows.as<uint64_t>();
+            uint32_t* cnt = c->chain_cnt.as<uint32_t>(); uint32_t* own = c->chain_own.as<uint32_t>();
+            unsigned long long* om = c->chain_om.as<unsigned long long>(); unsigned long long* late = c->chain_late.as<unsigned long long>();
+            unsigned long long* dep = c->chain_dep.as<unsigned long long>(); unsigned long long* xdep = c->chain_xdep.as<unsigned long long>();
+            size_t rows_tmp = 0;
+            HIPCHK(c, prim::ExclusiveSum(nullptr, rows_tmp, rows, rows, nG + 1, s));
+            if (rows_tmp > c->cub_tmp.cap) { HIPCHK(c, hipStreamSynchronize(s)); if (int rc = ensure_cub(c, std::max(rows_tmp, scan_tmp))) return rc; }
+            launch_chain_prep(s, false, R, c->D, V, first_read_index, w0, clist + c0, nc, c0, rank, cnt, own, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+            launch_chain_tables(s, cnt, own, nc, rows, om, late);
+            HIPCHK(c, prim::ExclusiveSum(c->cub_tmp.p, rows_tmp, rows, rows, nG + 1, s));
+            HIPCHK(c, hipMemcpyAsync(c->h_rb + 0, rows + nG, 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, spin_sync(s));
+            const uint64_t total_rows = c->h_rb[0];
+            HIPCHK(c, c->chain_ent.ensure(std::max<uint64_t>(total_rows, 1) * 64 * 4)); uint32_t* ent = c->chain_ent.as<uint32_t>();
+            launch_chain_prep(s, true, R, c->D, V, first_read_index, w0, clist + c0, nc, c0, rank, cnt, own, rows, ent, om, late, dep, xdep);
+            if (launch_chain_seq(s, nc, cnt, own, dep, xdep, rows, ent, c->chain_ins.as<unsigned long long>(), d_ctrace))
+                return fail(c, LEON_E_HIP, "the sequential resolution pass could not be launched (its LDS request was refused)");
+            launch_chain_apply(s, c->D, V, first_read_index, clist + c0, nc, c->chain_ins.as<unsigned long long>(), k);
+            HIPCHK(c, hipGetLastError());
+        }
+        // (the rounds end with every tent they touched cleared; so must this: a tent that still named a settled read would block whoever
+        // proposes the key in a later window)
+        { const uint32_t c_last = (left - 1) / CH * CH; launch_chain_repropose(s, c->D, V, first_read_index, clist + c_last, left - c_last, nullptr, 0); }
+        HIPCHK(c, hipEventRecord(c->chain_ev[2 * n_chain_ev + 1], s));
+        n_chain_ev++;
+        c->stats.resolve_chain_reads += left; c->stats.resolve_chain_windows++;
+        if (knobs.trace_chain) {
+            unsigned long long t[8];
+            HIPCHK(c, hipStreamSynchronize(s));
+            HIPCHK(c, hipMemcpy(t, d_ctrace, sizeof t, hipMemcpyDeviceToHost));
+            float cms = 0; (void)hipEventElapsedTime(&cms, c->chain_ev[2 * n_chain_ev - 2], c->chain_ev[2 * n_chain_ev - 1]);
+            fprintf(stderr, "[leon chain] window [%llu, %llu): %u reads left by the rounds; %llu steps of 64, %.2f ballot iterations and %.1f entry rows per step, %llu inserters; %.2f ms; per step the settler waited %.0f (tester: %.0f), settled + published %.0f ticks of s_memtime\n",
+                    (unsigned long long)w0, (unsigned long long)w1, left, t[0], t[0] ? (double)t[1] / t[0] : 0.0, t[0] ? (double)t[2] / t[0] : 0.0, t[3], cms,
+                    t[0] ? (double)t[4] / t[0] : 0.0, t[0] ? (double)t[5] / t[0] : 0.0, t[0] ? (double)t[6] / t[0] : 0.0);
+        }
+        return LEON_OK;
+    }
+    // the window's settled reads: their final positions, the new anchors' addresses and k-mers, and those k-mers on their way to the
+    // host thread coding the dictionary stream
+    int settle(uint64_t w0, uint64_t w1) {
+        launch_final_pos(s, R, c->D, V, w0, w1, first_read_index);
+        launch_ins_flags(s, V, w0, w1);
+        HIPCHK(c, prim::ExclusiveSum(c->cub_tmp.p, scan_tmp, V.ins_flag, c->rank.as<uint32_t>(), w1 - w0, s));
+        HIPCHK(c, hipMemcpyAsync(c->h_rb + 0, c->rank.as<uint32_t>() + (w1 - w0 - 1), 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(c->h_rb + 1, V.ins_flag + (w1 - w0 - 1), 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(c->h_rb + 2, c->d_nkeys, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, spin_sync(s));
+        const uint64_t n_new = (uint64_t)(uint32_t)c->h_rb[0] + (uint32_t)c->h_rb[1];   // the window's last read's rank + its flag
+        c->n_keys = c->h_rb[2];
+        if (c->n_anchors + n_new > 0xFFFFFFFFull) return fail(c, LEON_E_OVERFLOW, "more than 2^32 anchors");
+        if ((c->n_anchors + n_new) * 8 * KW > c->anchor_kmers.cap) {      // grow, keeping what is there
+            TmpBuf nb;
+            HIPCHK(c, nb.ensure(std::max<uint64_t>((c->n_anchors + n_new) * 2, 1024) * 8 * KW));
+            if (c->n_anchors) HIPCHK(c, hipMemcpyAsync(nb.p, c->anchor_kmers.p, c->n_anchors * 8 * KW, hipMemcpyDeviceToDevice, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+            std::swap(static_cast<DevBuf&>(nb).p, c->anchor_kmers.p);        // nb now holds the old buffer and releases it
+            std::swap(static_cast<DevBuf&>(nb).cap, c->anchor_kmers.cap);
+        }
+        launch_assign_addr(s, c->D, V, w0, w1, c->rank.as<uint32_t>(), c->n_anchors, c->anchor_kmers.as<uint64_t>(), k);
+        if (n_new && c->shard_rank == 0 && !(c->cfg.flags & LEON_F_DICT_ON_DEVICE)) {   // the window's new anchors, for the host thread coding the dictionary stream
+            HIPCHK(c, hipMemcpyAsync(c->h_anchor[anchor_buf], c->anchor_kmers.as<uint64_t>() + c->n_anchors * KW, n_new * 8 * KW, hipMemcpyDeviceToHost, s));
+            pending.buf = anchor_buf; pending.n = n_new;
+            anchor_buf ^= 1;
+            if (w0 == 0) {
+                HIPCHK(c, spin_sync(s));
+                hand_over();
+                mark("first window's anchors to the chain");
+            }
+        }
+        c->n_anchors += n_new;
+        return LEON_OK;
+    }
+    void hand_over() {                              // (called right after a wait: the copy has landed)
+        if (pending.buf < 0) return;
+        std::vector<uint64_t> fresh(c->h_anchor[pending.buf], c->h_anchor[pending.buf] + pending.n * KW);
+        c->anchor_worker->push(std::move(fresh));
+        pending.buf = -1;
+    }
+    // ---- this rank's share of the batch: a contiguous range of whole blocks (all of it when not sharded) ----
+    int take_share() {
+        sh = share_of(c, n);
+        uint64_t off_r0 = off_first, off_r1 = off_last;
+        if (c->shard_world > 1) {
+            HIPCHK(c, hipMemcpy(&off_r0, d_off + sh.r0, 8, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(&off_r1, d_off + sh.r0 + sh.nl, 8, hipMemcpyDeviceToHost));
+        }
+        nl_bases = off_r1 - off_r0;
+        R.ev_origin = sh.r0;
+        c->stats.n_reads = sh.nl; c->stats.n_bases = nl_bases; c->stats.n_blocks = sh.nbl; c->stats.n_anchors = c->n_anchors;
+        c->last_n = n; c->last_bases = nl_bases; c->last_d_bases = d_bases; c->last_d_off = d_off;
+        by_anchor = c->shard_world > 1 && c->xch_mode != LEON_XCH_OFF;
+        return LEON_OK;
+    }
+    // ---- walk: the events of the share's reads, walked here (walk_share) or divided among the ranks by anchor (walk_by_anchor) ----
+    int walk() {
+        HIPCHK(c, c->events.ensure(nl_bases + 16));
+        HIPCHK(c, hipMemsetAsync(c->events.p, 0, nl_bases + 16, s));
+        start_walk_cache();
+        HIPCHK(c, c->perm.ensure(n * 4));
+        hipLaunchKernelGGL(k_iota, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 8192)), dim3(256), 0, s, c->perm.as<uint32_t>(), n);
+        return by_anchor ? walk_by_anchor() : walk_share();
+    }
+    // the walk's path cache (walk_cache_buckets), at most an eighth of the free device memory; EMPTY again at every batch -- what a batch's
+    // walkers learn from the bloom is shared among THEM, a later batch (or a bench step) starts cold
+    void start_walk_cache() {
+        uint64_t buckets = knobs.walk_cache ? walk_cache_buckets(c) : 0;
+        if (!buckets) return;
+        if (knobs.walk_cache_log2 >= 10 && knobs.walk_cache_log2 <= 31) buckets = 1ull << knobs.walk_cache_log2;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) while (buckets > 1024 && buckets * 64 > c->wcache.cap && buckets * 64 > free_b / 8) buckets >>= 1;
+        if (c->wcache.ensure(buckets * 64) != hipSuccess) { (void)hipGetLastError(); return; }
+        wc.slots = c->wcache.as<uint64_t>(); wc.bucket_mask = buckets - 1; wc.hop_shift = 32 - knobs.walk_hop_log2;
+        launch_walk_cache_init(s, wc, k);
+    }
+    int walk_share() {
+        // ---- sort the share's reads by (anchor address, strand) ----
+        const uint64_t r0 = sh.r0, nl = sh.nl;
+        HIPCHK(c, c->sort_key2.ensure(nl * 8)); HIPCHK(c, c->perm2.ensure(nl * 4));
+        // (measurement hook: another order of the reads in the walk changes which lanes share bloom sectors, never the bytes --
+        // events are indexed by read position)
+        const uint64_t* walk_key = walk_keys ? walk_keys + r0 : V.sort_key + r0;
+        const unsigned key_bits = walk_keys ? 48u : 33u;
+        auto sort = [&](void* t, size_t& b) { return prim::SortPairs(t, b, walk_key, c->sort_key2.as<uint64_t>(), c->perm.as<uint32_t>() + r0, c->perm2.as<uint32_t>(), nl, 0, key_bits, s); };
+        if (int rc = run_prim(c, sort)) return rc;
+        HIPCHK(c, hipEventRecord(c->ev[3], s));
+        // ---- walk ----
+        HIPCHK(c, hipEventRecord(c->ev[4], s));
+        launch_walk(s, R, c->B, c->d_rv16, V.anchor_pos, V.flags, c->perm2.as<uint32_t>(), nl, c->events.as<uint8_t>(), nullptr, wc);
+        HIPCHK(c, hipEventRecord(c->ev[5], s));
+        c->stats.walk_launches = 1; c->stats.walk_reads = nl;
+        return LEON_OK;
+    }
+    // ---- the walk divided by anchor (leon_dna_set_exchange): ALL of the batch's reads sorted by anchor address, cut into `world` slices of
+    // equal size; this rank walks its slice into a buffer of its own and what it found goes to the ranks that code the reads' blocks, as
+    // (place in that rank's event buffer, byte) words grouped by destination ----
+    int walk_by_anchor() {
+        const uint32_t Wd = c->shard_world, me = c->shard_rank;
+        if (Wd + 2 > 4096 / 8) return fail(c, LEON_E_INVALID, "set_exchange: world too large");
+        if (int rc = cut_slices()) return rc;
+        HIPCHK(c, hipMemsetAsync(c->errflag.as<int>() + 1, 0, 4, s));
+        const auto t_x0 = std::chrono::steady_clock::now();     // (ms_exchange: everything of the division that is not the slice's walk itself)
+        if (int rc = walk_slice(me, true)) return rc;
+        HIPCHK(c, hipStreamSynchronize(s));
+        float walk_own = 0; (void)hipEventElapsedTime(&walk_own, c->ev[4], c->ev[5]);
+        c->stats.xch_words_sent = send_at[Wd];
+        if (c->xch_mode == LEON_XCH_BY_ANCHOR) {
+            const uint64_t* d_recv = nullptr; uint64_t recv_total = 0;
+            const auto t_call = std::chrono::steady_clock::now();
+            if (c->xch_fn(c->xch_user, c->xch_send.as<uint64_t>(), send_counts.data(), Wd, &d_recv, &recv_total))
+                return fail(c, LEON_E_STATE, "the exchange callback returned non-zero");
+            c->stats.ms_exchange_call = ms_since(t_call);
+            if (recv_total && !d_recv) return fail(c, LEON_E_STATE, "the exchange callback returned no buffer");
+            c->stats.xch_words_received = recv_total;
+            HIPCHK(c, hipSetDevice(c->device));                   // (the callback may have changed the thread's device)
+            launch_ev_scatter(s, d_recv, recv_total, c->events.as<uint8_t>(), nl_bases, c->errflag.as<int>() + 1);
+            HIPCHK(c, hipStreamSynchronize(s));                   // the caller's buffer is free again when this call returns
+            c->stats.ms_exchange = ms_since(t_x0) - walk_own;
+        } else {
+            // no other rank present: this context plays them all, one slice after the other, and keeps what is meant for its own rank
+            auto keep_own = [&] { launch_ev_scatter(s, c->xch_send.as<uint64_t>() + send_at[me], send_counts[me], c->events.as<uint8_t>(), nl_bases, c->errflag.as<int>() + 1);
+                                  c->stats.xch_words_received += send_counts[me]; };
+            keep_own();
+            HIPCHK(c, hipStreamSynchronize(s));
+            c->stats.ms_exchange = ms_since(t_x0) - walk_own;
+            const auto t_e0 = std::chrono::steady_clock::now();
+            for (uint32_t sl = 0; sl < Wd; sl++) {
+                if (sl == me) continue;
+                if (int rc = walk_slice(sl, false)) return rc;
+                keep_own();
+            }
+            HIPCHK(c, hipStreamSynchronize(s));
+            c->stats.ms_emulated = ms_since(t_e0);
+        }
+        // (the window look-ups shared out among the ranks, earlier in this call: their gathers and, emulated, the other ranks' runs)
+        c->stats.ms_exchange_call += lk_call_ms; c->stats.ms_exchange += lk_call_ms; c->stats.ms_gather_call = lk_call_ms;
+        c->stats.ms_emulated += lk_emul_ms; c->stats.ms_emulated_lookups = lk_emul_ms;
+        HIPCHK(c, hipEventRecord(c->ev[9], s));                  // the symbols stage begins here
+        int xerr = 0;
+        HIPCHK(c, hipMemcpy(&xerr, c->errflag.as<int>() + 1, 4, hipMemcpyDeviceToHost));
+        if (xerr) return fail(c, LEON_E_STATE, "the exchange delivered a word that lies outside this rank's blocks");
+        return LEON_OK;
+    }
+    // the batch's reads sorted by anchor and cut into slices: slice_at, rank_r0, and the work space of the slices' scans
+    int cut_slices() {
+        const uint32_t Wd = c->shard_world;
+        HIPCHK(c, c->sort_key2.ensure(n * 8)); HIPCHK(c, c->perm2.ensure(n * 4));
+        auto sort = [&](void* t, size_t& b) { return prim::SortPairs(t, b, V.sort_key, c->sort_key2.as<uint64_t>(), c->perm.as<uint32_t>(), c->perm2.as<uint32_t>(), n, 0, 33, s); };
+        if (int rc = run_prim(c, sort)) return rc;
+        unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(c->counters.as<uint32_t>() + 10);
+        launch_lower_bound(s, c->sort_key2.as<uint64_t>(), n, 1ull << 32, d_cnt);            // reads without an anchor sort last: nothing to walk
+        HIPCHK(c, hipMemcpyAsync(c->h_rb + 0, d_cnt, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, spin_sync(s));
+        const uint64_t n_anch = c->h_rb[0];
+        // the slices: equal WEIGHT (a read 1, an anchor group's first read SLICE_GROUP_WEIGHT more), the same cuts on every rank
+        HIPCHK(c, c->xch_slot.ensure(n * 4)); HIPCHK(c, c->xch_off.ensure((n + 1) * 8));
+        HIPCHK(c, prim::ExclusiveSum(nullptr, scan_n, c->xch_off.as<uint64_t>(), c->xch_off.as<uint64_t>(), n + 1, s));
+        if (int rc = ensure_cub(c, scan_n)) return rc;
+        HIPCHK(c, c->xch_split.ensure((Wd + 1) * 8));
+        launch_slice_weights(s, c->sort_key2.as<uint64_t>(), n_anch, c->xch_off.as<uint64_t>());
+        HIPCHK(c, prim::ExclusiveSum(c->cub_tmp.p, scan_n, c->xch_off.as<uint64_t>(), c->xch_off.as<uint64_t>(), n_anch + 1, s));
+        launch_slice_splits(s, c->xch_off.as<uint64_t>(), n_anch, Wd, c->xch_split.as<unsigned long long>());
+        HIPCHK(c, hipMemcpyAsync(c->h_rb + 0, c->xch_split.p, (Wd + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipEventRecord(c->ev[3], s));
+        HIPCHK(c, spin_sync(s));
+        slice_at.assign(c->h_rb, c->h_rb + Wd + 1);
+        // where each rank's reads begin in file order, for the words' grouping
+        rank_r0.resize(Wd + 1);
+        for (uint32_t d = 0; d <= Wd; d++) rank_r0[d] = std::min<uint64_t>(n, block_start(n_blocks, d, Wd) * rpb);
+        send_counts.assign(Wd, 0);
+        send_at.assign(Wd + 1, 0);
+        return LEON_OK;
+    }
+    // one slice: walked into xch_events, its words formed in xch_send (grouped by destination; send_at[d] = where rank d's begin)
+    int walk_slice(uint32_t sl, bool timed) {
+        const uint32_t Wd = c->shard_world;
+        const uint64_t s0 = slice_at[sl], s1 = slice_at[sl + 1], ns = s1 - s0;
+        const uint32_t* slice = c->perm2.as<uint32_t>() + s0;
+        HIPCHK(c, c->xch_evoff.ensure((ns + 1) * 8));
+        uint64_t* evoff = c->xch_evoff.as<uint64_t>();
+        HIPCHK(c, hipMemsetAsync(c->xch_slot.p, 0xFF, n * 4, s));
+        launch_slice_reads(s, R, slice, ns, evoff, c->xch_slot.as<uint32_t>());
+        if (int rc = run_prim(c, [&](void* t, size_t& b) { return prim::ExclusiveSum(t, b, evoff, evoff, ns + 1, s); })) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->h_rb + 0, evoff + ns, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, spin_sync(s));
+        const uint64_t slice_bases = c->h_rb[0];
+        HIPCHK(c, c->xch_events.ensure(slice_bases + 16));
+        HIPCHK(c, hipMemsetAsync(c->xch_events.p, 0, slice_bases + 16, s));
+        if (timed) HIPCHK(c, hipEventRecord(c->ev[4], s));
+        launch_walk(s, R, c->B, c->d_rv16, V.anchor_pos, V.flags, slice, ns, c->xch_events.as<uint8_t>(), evoff, wc);
+        if (timed) { HIPCHK(c, hipEventRecord(c->ev[5], s)); c->stats.walk_launches = 1; c->stats.walk_reads = ns; }
+        launch_ev_words(s, R, c->xch_slot.as<uint32_t>(), evoff, c->xch_events.as<uint8_t>(), n, rpb, n_blocks, Wd, c->xch_off.as<uint64_t>(), nullptr);
+        HIPCHK(c, prim::ExclusiveSum(c->cub_tmp.p, scan_n, c->xch_off.as<uint64_t>(), c->xch_off.as<uint64_t>(), n + 1, s));
+        for (uint32_t d = 0; d <= Wd; d++) HIPCHK(c, hipMemcpyAsync(c->h_rb + 1 + d, c->xch_off.as<uint64_t>() + rank_r0[d], 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, spin_sync(s));
+        for (uint32_t d = 0; d <= Wd; d++) send_at[d] = c->h_rb[1 + d];
+        for (uint32_t d = 0; d < Wd; d++) send_counts[d] = send_at[d + 1] - send_at[d];
+        HIPCHK(c, c->xch_send.ensure(send_at[Wd] * 8 + 64));
+        launch_ev_words(s, R, c->xch_slot.as<uint32_t>(), evoff, c->xch_events.as<uint8_t>(), n, rpb, n_blocks, Wd, c->xch_off.as<uint64_t>(),
+                        c->xch_send.as<uint64_t>());
+        HIPCHK(c, hipGetLastError());
+        return LEON_OK;
+    }
+    // ---- symbols, range coder, D2H: the share's blocks ----
+    int code(CodedBlocks& out) {
+        HIPCHK(c, c->prev.ensure(n * 8));
+        HIPCHK(c, c->nerr.ensure(sh.nl * 8));                      // (two words per read: error positions, chunks that hold events)
+        launch_prev_anchored(s, V.anchor_pos, n, rpb, sh.lb0, sh.nbl, c->prev.as<int64_t>());
+        auto symbols = [&](uint8_t* syms) {
+            launch_symbols(s, R, V.anchor_pos, V.anchor_addr, V.flags, c->prev.as<int64_t>(), c->events.as<uint8_t>(), sh.r0, sh.nl,
+                           c->sym_off.as<uint64_t>(), c->nerr.as<uint32_t>(), syms);
+        };
+        return code_blocks(c, sh, symbols, SMALL_SIZES_DNA, true, "read", out);
+    }
+    // The batch's end, on each of its three ways out: the stats up to event last_ev -- 2: nothing of the batch is this rank's to walk or code;
+    // 5: the rank's slice walked and delivered, none of the blocks is its own; 8: `out` coded --, the blocks to the sink, the stream moved on.
+    int finish(int last_ev, const CodedBlocks* out = nullptr) {
+        leon_dna_stats& st = c->stats;
+        const float pack2 = pairs_ms(c->pack_ev, 1, n_pack_ev);   // the part of the pack stage that ran inside the resolution loop
+        st.ms_pack = ms(0, 1) + pack2; st.ms_resolve = ms(1, 2) - pack2; st.ms_resolve_chain = pairs_ms(c->chain_ev, 0, n_chain_ev);
+        if (last_ev >= 5) { st.ms_sort = ms(2, 3); st.ms_walk = ms(4, 5); }
+        if (out) {
+            st.n_symbols = out->n_syms; st.payload_bytes = out->payload_bytes;
+            st.ms_symbols = by_anchor ? ms(9, 6) : ms(5, 6); st.ms_rangecoder = ms(6, 7); st.ms_d2h = ms(7, 8);
+        }
+        st.ms_total = ms(0, last_ev);
+        if (out) { if (int rc = deliver_blocks(c, *out, sh, n, c->next_block, sink, user)) return rc; }
+        c->next_read += n;
+        c->next_block += n_blocks;
+        if (n % rpb) c->partial_seen = true;
+        c->poisoned = false;
+        return LEON_OK;
+    }
+};
+
+
+}  // namespace
+
 static int encode_batch_impl(leon_dna_ctx* c, const uint8_t* d_bases, const uint64_t* d_off, uint64_t n,
-                             uint64_t first_read_index, leon_block_sink sink, void* user, Upload* up, const uint64_t* up_off);
+                             uint64_t first_read_index, leon_block_sink sink, void* user, Upload* up, const uint64_t* up_off) {
+    if (!c) return LEON_E_INVALID;
+    if (c->finished) return fail(c, LEON_E_STATE, "encode_batch after finish");
+    if (first_read_index != c->next_read) return fail(c, LEON_E_STATE, "first_read_index does not continue the stream");
+    if (c->partial_seen && n) return fail(c, LEON_E_STATE, "a batch with a partial block must be the last one");
+    if (n == 0) return LEON_OK;
+    if (!d_bases || !d_off || !sink) return fail(c, LEON_E_INVALID, "null argument");
+    if (n > 0xFFFFFFF0ull) return fail(c, LEON_E_INVALID, "more than 2^32 reads in one batch");
+    HIPCHK(c, hipSetDevice(c->device));
+    EncodeBatch B{c, d_bases, d_off, n, first_read_index, sink, user, up, up_off};
+    if (int rc = B.start()) return rc;
+    c->poisoned = true;             // from here on the dictionary and the dictionary stream change: cleared on success
+    if (int rc = B.resolve()) return rc;
+    if (int rc = B.take_share()) return rc;
+    if (B.sh.nl == 0 && !(B.by_anchor && c->xch_mode == LEON_XCH_BY_ANCHOR)) {   // nothing of this batch is ours to encode (and nobody waits for our slice)
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return B.finish(2);
+    }
+    if (int rc = B.walk()) return rc;
+    if (B.sh.nl == 0) return B.finish(5);                        // our slice is delivered; no block of the batch is ours to code
+    CodedBlocks out;                                             // (the share's blocks: symbols, range coder, D2H)
+    if (int rc = B.code(out)) return rc;
+    return B.finish(8, &out);
+}
 
 // A batch that fails before it has touched the stream (bad arguments, bad offsets, call order) leaves the context as it was.
 // One that fails later -- a HIP error, an internal bound, the sink -- leaves the dictionary, the dictionary-stream thread
@@ -642,666 +1386,13 @@ static int encode_batch_guarded(leon_dna_ctx* c, const uint8_t* d_bases, const u
     }
     for (DevBuf* b : { &c->dc_out, &c->dc_pay, &c->dc_len, &c->dc_pool, &c->dc_scr }) b->release();
     const int rc = encode_batch_impl(c, d_bases, d_off, n, first_read_index, sink, user, up, up_off);
-    if (rc != LEON_OK && c->poisoned) c->err += " (stream poisoned: leon_dna_reset_stream to go on)";
+    if (rc != LEON_OK && c->poisoned) c->err += kPoisonedNote;
     return rc;
 }
 
 int leon_dna_encode_batch_device(leon_dna_ctx* c, const uint8_t* d_bases, const uint64_t* d_off, uint64_t n,
                                  uint64_t first_read_index, leon_block_sink sink, void* user) {
     return encode_batch_guarded(c, d_bases, d_off, n, first_read_index, sink, user, nullptr);
-}
-
-// reads [0, group_end(a)) are packed (and, through the host entry point, uploaded) together: the first resolution window
-// alone, so that the device and the dictionary chain start at once, then groups of 8 windows
-// (the first window itself is short -- first_window() reads -- so that the first anchors reach the host chain, the longest
-// single piece of a step, a few milliseconds after the call starts; the result does not depend on where windows end)
-static uint64_t first_window(uint64_t window) { return std::min<uint64_t>(window, 1ull << 17); }
-static uint64_t group_end(uint64_t a, uint64_t n, uint64_t window, bool /*streamed*/) {
-    if (a == 0) return std::min(n, first_window(window));
-    // (resident input used to pack everything that was left in one go: 9.6 ms at 100 M reads between the first window and the
-    // second, during which the dictionary chain ran out of the first window's anchors and idled)
-    return std::min(n, a + 8 * std::min<uint64_t>(window, 1ull << 20));
-}
-
-static int encode_batch_impl(leon_dna_ctx* c, const uint8_t* d_bases, const uint64_t* d_off, uint64_t n,
-                             uint64_t first_read_index, leon_block_sink sink, void* user, Upload* up, const uint64_t* up_off) {
-    if (!c) return LEON_E_INVALID;
-    if (c->finished) return fail(c, LEON_E_STATE, "encode_batch after finish");
-    if (first_read_index != c->next_read) return fail(c, LEON_E_STATE, "first_read_index does not continue the stream");
-    if (c->partial_seen && n) return fail(c, LEON_E_STATE, "a batch with a partial block must be the last one");
-    if (n == 0) return LEON_OK;
-    if (!d_bases || !d_off || !sink) return fail(c, LEON_E_INVALID, "null argument");
-    if (n > 0xFFFFFFF0ull) return fail(c, LEON_E_INVALID, "more than 2^32 reads in one batch");
-    const uint32_t rpb = c->cfg.reads_per_block, k = c->cfg.kmer_size;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    c->stats = leon_dna_stats{};
-    const uint64_t* const walk_keys = c->walk_keys;              // (leon_dna_debug_walk_order applies to THIS batch only, whatever becomes of it)
-    c->walk_keys = nullptr;
-    static const bool trace_step = getenv("LEON_TRACE_STEP") != nullptr;   // measurement aid: host time of a batch's first milestones, on stderr
-    const auto t_enter = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {
-        if (trace_step) fprintf(stderr, "[leon step] %-34s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count());
-    };
-
-    // ---- sizes ----
-    uint64_t off_first = 0, off_last = 0;
-    HIPCHK(c, hipMemcpyAsync(c->h_rb + 0, d_off, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(c->h_rb + 1, d_off + n, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, spin_sync(s));
-    off_first = c->h_rb[0]; off_last = c->h_rb[1];
-    if (off_last < off_first) return fail(c, LEON_E_INVALID, "offsets are not monotonic");
-    const uint64_t n_bases = off_last - off_first;
-    (void)n_bases;
-    const uint64_t n_blocks = (n + rpb - 1) / rpb;
-
-    HIPCHK(c, hipEventRecord(c->ev[0], s));
-    // ---- pack ----
-    HIPCHK(c, c->slot_off.ensure((n + 1) * 8));
-    HIPCHK(c, hipMemsetAsync(c->counters.as<uint32_t>() + 4, 0, 4, s));
-    launch_read_slots(s, d_off, n, c->slot_off.as<uint64_t>(), c->counters.as<uint32_t>() + 4);
-    size_t tmp_bytes = 0;
-    HIPCHK(c, prim::ExclusiveSum(nullptr, tmp_bytes, c->slot_off.as<uint64_t>(), c->slot_off.as<uint64_t>(), n + 1, s));
-    if (int rc = ensure_cub(c, tmp_bytes)) return rc;
-    HIPCHK(c, prim::ExclusiveSum(c->cub_tmp.p, tmp_bytes, c->slot_off.as<uint64_t>(), c->slot_off.as<uint64_t>(), n + 1, s));
-    uint64_t n_slots = 0;
-    uint32_t bad_offsets = 0;
-    HIPCHK(c, hipMemcpyAsync(c->h_rb + 0, c->slot_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(c->h_rb + 1, c->counters.as<uint32_t>() + 4, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, spin_sync(s));
-    n_slots = c->h_rb[0]; bad_offsets = (uint32_t)c->h_rb[1];
-    if (bad_offsets) return fail(c, LEON_E_INVALID, "offsets are not monotonic (or a read is longer than 2^31 bases)");
-    mark("offsets checked, slots scanned");
-    HIPCHK(c, c->packed.ensure((n_slots * 2 + 16) * 4));     // wave loads reach 12 dwords past a pass start
-    HIPCHK(c, c->nmask.ensure((n_slots + 4) * 4));
-    HIPCHK(c, c->rlen.ensure(n * 4));
-    HIPCHK(c, c->ncount.ensure(n * 4));
-    HIPCHK(c, hipMemsetAsync(c->packed.as<uint32_t>() + n_slots * 2, 0, 64, s));
-    // the first resolution window's reads are packed first, later groups right before their first window: the host thread
-    // that codes the dictionary stream (the longest single piece of a step) gets its first anchors ~25 ms earlier, and
-    // with host input the upload of a group overlaps the resolution of the groups before it
-    uint64_t packed_upto = 0;
-    uint32_t n_pack_ev = 0;
-    auto pack_group = [&]() -> int {
-        const uint64_t a = packed_upto, b = group_end(a, n, c->cfg.resolve_window, up != nullptr);
-        if (up) {
-            // the group's last base, from the caller's offsets: checked before it is waited for (whatever the entries between
-            // the group boundaries are, the device checks them one by one and refuses the batch)
-            const uint64_t want = up_off[b];
-            if (want < up_off[0] || want > up_off[n] || want < up_off[a]) return fail(c, LEON_E_INVALID, "offsets are not monotonic");
-            while (up->bytes_done.load(std::memory_order_acquire) < want - up_off[0] && !up->failed.load()) std::this_thread::yield();
-            if (up->failed.load()) return fail(c, LEON_E_HIP, "upload of the read bases failed");
-        }
-        if (c->pack_ev.size() < 2 * (size_t)(n_pack_ev + 1)) {
-            hipEvent_t e0, e1;
-            HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
-            c->pack_ev.push_back(e0); c->pack_ev.push_back(e1);
-        }
-        HIPCHK(c, hipEventRecord(c->pack_ev[2 * n_pack_ev], s));
-        launch_pack(s, d_bases, d_off + a, c->slot_off.as<uint64_t>() + a, b - a, c->packed.as<uint32_t>(), c->nmask.as<uint32_t>(),
-                    c->rlen.as<uint32_t>() + a, c->ncount.as<uint32_t>() + a);
-        HIPCHK(c, hipEventRecord(c->pack_ev[2 * n_pack_ev + 1], s));
-        n_pack_ev++;
-        packed_upto = b;
-        return LEON_OK;
-    };
-    if (int rc = pack_group()) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[1], s));
-    ReadsDev R = reads_view(c, d_off, n);
-
-    // ---- anchor resolution ----
-    HIPCHK(c, c->status.ensure(n));
-    HIPCHK(c, c->hit_pos.ensure(n * 4)); HIPCHK(c, c->hit_slot.ensure(n * 4));
-    HIPCHK(c, c->cand_pos.ensure(n * 4)); HIPCHK(c, c->cand_slot.ensure(n * 4));
-    HIPCHK(c, c->anchor_pos.ensure(n * 4)); HIPCHK(c, c->anchor_addr.ensure(n * 4));
-    HIPCHK(c, c->flags.ensure(n)); HIPCHK(c, c->sort_key.ensure(n * 8));
-    const uint64_t W = std::min<uint64_t>(c->cfg.resolve_window, n);
-    HIPCHK(c, c->ins_flag.ensure(W * 4)); HIPCHK(c, c->rank.ensure(W * 4));
-    HIPCHK(c, c->ulist0.ensure(W * 4)); HIPCHK(c, c->ulist1.ensure(W * 4));
-    ResolveDev V{};
-    V.status = c->status.as<uint8_t>(); V.hit_pos = c->hit_pos.as<uint32_t>(); V.hit_slot = c->hit_slot.as<uint32_t>();
-    V.cand_pos = c->cand_pos.as<uint32_t>(); V.cand_slot = c->cand_slot.as<uint32_t>();
-    V.anchor_pos = c->anchor_pos.as<int32_t>(); V.anchor_addr = c->anchor_addr.as<uint32_t>(); V.flags = c->flags.as<uint8_t>();
-    V.sort_key = c->sort_key.as<uint64_t>(); V.ins_flag = c->ins_flag.as<uint32_t>();
-    uint32_t* counters = c->counters.as<uint32_t>();            // [0],[1]: list counts
-    uint32_t* lists[2] = { c->ulist0.as<uint32_t>(), c->ulist1.as<uint32_t>() };
-    size_t scan_tmp = 0;
-    HIPCHK(c, prim::ExclusiveSum(nullptr, scan_tmp, V.ins_flag, c->rank.as<uint32_t>(), W, s));
-    if (int rc = ensure_cub(c, scan_tmp)) return rc;
-    c->poisoned = true;             // from here on the dictionary and the dictionary stream change: cleared on success
-    // Host round trips: a wait costs 20-40 us and the stage used to make ~6 per window (580 per 100 M reads: the window's first count,
-    // one per fixpoint round, the insert count, the new anchors' copy).  Now two: the rounds are launched AHEAD of their counts -- the
-    // kernels take the list lengths from device memory, an empty list costs a launch that finds nothing to do -- three at once, then two
-    // at a time for the few windows that need more, with every round's count copied to a small history that comes back with the
-    // next wait; and a window's new anchors travel to pinned memory behind the kernels and are handed to the dictionary chain at
-    // the NEXT window's first wait (the first window's at once: the chain, the longest piece of a step, starts with them).
-    const uint64_t KW = kmer_words(k);                              // 64-bit words per anchor k-mer
-    // The rounds are NOT asked to finish: their count is the longest chain of reads each waiting for the one before it, which no valid
-    // input bounds (reads in genome-position order make one chain of a whole window).  After kRoundsAhead rounds -- more while the
-    // list keeps halving, kRoundsMax at most -- what is left goes, in read order, through the exact sequential pass (chain_tail below).
-    // LEON_RESOLVE_ROUNDS=a[:m]: rounds launched ahead / at most (measurement aid; any values give the same bytes).
-    const uint32_t kRoundsAhead = [] { const char* e = getenv("LEON_RESOLVE_ROUNDS"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 32 ? (uint32_t)v : 3u; }();
-    const uint32_t kRoundsMax = [&] { const char* e = getenv("LEON_RESOLVE_ROUNDS"); const char* q = e ? strchr(e, ':') : nullptr; const int v = q ? atoi(q + 1) : 0;
-                                      return std::max<uint32_t>(kRoundsAhead, v >= 1 && v <= 62 ? (uint32_t)v : 9u); }();
-    constexpr uint32_t kRoundsMore = 2, kHist = 64;
-    HIPCHK(c, c->round_hist.ensure(kHist * 4));
-    uint32_t* d_hist = c->round_hist.as<uint32_t>();
-    if (c->h_anchor_cap < W * 8 * KW) {
-        for (auto& b : c->h_anchor) { if (b) HIPCHK(c, hipHostFree(b)); b = nullptr; }
-        c->h_anchor_cap = 0;
-        for (auto& b : c->h_anchor) HIPCHK(c, hipHostMalloc((void**)&b, W * 8 * KW + 64, hipHostMallocDefault));
-        c->h_anchor_cap = W * 8 * KW;
-    }
-    struct Pending { int buf = -1; uint64_t n = 0; } pending;      // a window's new anchors on their way to pinned memory
-    auto hand_over = [&]() {                                       // (called right after a wait: the copy has landed)
-        if (pending.buf < 0) return;
-        std::vector<uint64_t> fresh(c->h_anchor[pending.buf], c->h_anchor[pending.buf] + pending.n * KW);
-        c->anchor_worker->push(std::move(fresh));
-        pending.buf = -1;
-    };
-    // LEON_TRACE_RESOLVE=1 (measurement aid): what a read costs k_lookup_cand by its outcome, on stderr at the end of the stage
-    static const bool trace_resolve = getenv("LEON_TRACE_RESOLVE") != nullptr;
-    unsigned long long* d_trace = nullptr;
-    if (trace_resolve) { HIPCHK(c, c->resolve_trace.ensure(12 * 8)); d_trace = c->resolve_trace.as<unsigned long long>(); HIPCHK(c, hipMemsetAsync(d_trace, 0, 12 * 8, s)); }
-    // the look-ups shared out among the ranks of a job (leon_dna_set_gather; LEON_XCH_EMULATE plays the other ranks.  LEON_XCH_LOOKUPS=0: off, a measurement aid)
-    static const bool lookups_env_off = [] { const char* e = getenv("LEON_XCH_LOOKUPS"); return e && atoi(e) == 0; }();
-    const uint32_t Wn = c->shard_world;
-    const bool share_lookups = Wn > 1 && !lookups_env_off && ((c->xch_mode == LEON_XCH_BY_ANCHOR && c->gather_fn) || c->xch_mode == LEON_XCH_EMULATE);
-    float lk_call_ms = 0, lk_emul_ms = 0;
-    int anchor_buf = 0;
-    uint32_t hint = (uint32_t)std::min<uint64_t>(W, 1u << 20);      // grid-size hint of a window's first round (any size is correct: grid-stride loops)
-    // ---- the exact sequential pass behind the rounds (dna_kernels.hip, k_chain_*): the `left` reads the rounds did not settle ----
-    static const bool trace_chain = getenv("LEON_TRACE_CHAIN") != nullptr;
-    uint32_t n_chain_ev = 0;
-    auto chain_tail = [&](uint32_t left, uint64_t w0, uint64_t w1, uint32_t* clist) -> int {
-        if (c->chain_ev.size() < 2 * (size_t)(n_chain_ev + 1)) {
-            hipEvent_t e0, e1;
-            HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
-            c->chain_ev.push_back(e0); c->chain_ev.push_back(e1);
-        }
-        HIPCHK(c, hipEventRecord(c->chain_ev[2 * n_chain_ev], s));
-        // in read order: flags over the window, their ranks (a read's chain index), the compacted list
-        uint32_t* rank = c->rank.as<uint32_t>();
-        launch_chain_flags(s, V, w0, w1, V.ins_flag);
-        HIPCHK(c, prim::ExclusiveSum(c->cub_tmp.p, scan_tmp, V.ins_flag, rank, w1 - w0, s));
-        launch_chain_compact(s, V, w0, w1, rank, clist);
-        // (LEON_CHAIN_CHUNK: reads per k_chain_seq, at most the 2^CHAIN_LOG2 its LDS holds a bit for -- a test hook: the path a window of more than
-        // half a million unsettled reads takes, chunk after chunk with tent re-proposed in between, on inputs the oracle codes in seconds;
-        // read at every call: the tests change it inside one process)
-        const uint32_t CH = [] { const char* e = getenv("LEON_CHAIN_CHUNK"); const long v = e ? atol(e) : 0; return v >= 1 && v <= (1l << CHAIN_LOG2) ? (uint32_t)v : 1u << CHAIN_LOG2; }();
-        unsigned long long* d_ctrace = nullptr;
-        if (trace_chain) { HIPCHK(c, c->chain_trace.ensure(8 * 8)); d_ctrace = c->chain_trace.as<unsigned long long>(); HIPCHK(c, hipMemsetAsync(d_ctrace, 0, 8 * 8, s)); }
-        for (uint32_t c0 = 0; c0 < left; c0 += CH) {
-            const uint32_t nc = std::min(CH, left - c0), nG = (nc + 63) / 64;
-            // a later chunk: tent still names reads of the chunk before (settled now) -- cleared, and what is left proposes again
-            if (c0) launch_chain_repropose(s, c->D, V, first_read_index, clist + (c0 - CH), left - (c0 - CH), clist + c0, left - c0);
-            HIPCHK(c, c->chain_cnt.ensure((uint64_t)nc * 4)); HIPCHK(c, c->chain_own.ensure((uint64_t)nc * 4));
-            HIPCHK(c, c->chain_ins.ensure(((uint64_t)nG + 1) * 8)); HIPCHK(c, c->chain_rows.ensure(((uint64_t)nG + 1) * 8));
-            HIPCHK(c, c->chain_dep.ensure((uint64_t)nc * 8)); HIPCHK(c, c->chain_xdep.ensure((uint64_t)nc * 8)); HIPCHK(c, c->chain_om.ensure((uint64_t)nG * 64 * 8)); HIPCHK(c, c->chain_late.ensure((uint64_t)nG * 8));
-            uint64_t* rows = c->chain_rows.as<uint64_t>();
-            unsigned long long* om = c->chain_om.as<unsigned long long>(); unsigned long long* late = c->chain_late.as<unsigned long long>();
-            unsigned long long* dep = c->chain_dep.as<unsigned long long>(); unsigned long long* xdep = c->chain_xdep.as<unsigned long long>();
-            size_t rows_tmp = 0;
-            HIPCHK(c, prim::ExclusiveSum(nullptr, rows_tmp, rows, rows, nG + 1, s));
-            if (rows_tmp > c->cub_tmp.cap) { HIPCHK(c, hipStreamSynchronize(s)); if (int rc = ensure_cub(c, std::max(rows_tmp, scan_tmp))) return rc; }
-            launch_chain_prep(s, false, R, c->D, V, first_read_index, w0, clist + c0, nc, c0, rank, c->chain_cnt.as<uint32_t>(), c->chain_own.as<uint32_t>(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-            launch_chain_tables(s, c->chain_cnt.as<uint32_t>(), c->chain_own.as<uint32_t>(), nc, rows, om, late);
-            HIPCHK(c, prim::ExclusiveSum(c->cub_tmp.p, rows_tmp, rows, rows, nG + 1, s));
-            HIPCHK(c, hipMemcpyAsync(c->h_rb + 0, rows + nG, 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, spin_sync(s));
-            const uint64_t total_rows = c->h_rb[0];
-            HIPCHK(c, c->chain_ent.ensure(std::max<uint64_t>(total_rows, 1) * 64 * 4));
-            launch_chain_prep(s, true, R, c->D, V, first_read_index, w0, clist + c0, nc, c0, rank, c->chain_cnt.as<uint32_t>(), c->chain_own.as<uint32_t>(), rows, c->chain_ent.as<uint32_t>(), om, late, dep, xdep);
-            if (launch_chain_seq(s, nc, c->chain_cnt.as<uint32_t>(), c->chain_own.as<uint32_t>(), dep, xdep, rows, c->chain_ent.as<uint32_t>(), c->chain_ins.as<unsigned long long>(), d_ctrace))
-                return fail(c, LEON_E_HIP, "the sequential resolution pass could not be launched (its LDS request was refused)");
-            launch_chain_apply(s, c->D, V, first_read_index, clist + c0, nc, c->chain_ins.as<unsigned long long>(), k);
-            HIPCHK(c, hipGetLastError());
-        }
-        // (the rounds end with every tent they touched cleared; so must this: a tent that still named a settled read would block whoever
-        // proposes the key in a later window)
-        { const uint32_t c_last = (left - 1) / CH * CH; launch_chain_repropose(s, c->D, V, first_read_index, clist + c_last, left - c_last, nullptr, 0); }
-        HIPCHK(c, hipEventRecord(c->chain_ev[2 * n_chain_ev + 1], s));
-        n_chain_ev++;
-        c->stats.resolve_chain_reads += left; c->stats.resolve_chain_windows++;
-        if (trace_chain) {
-            unsigned long long t[8];
-            HIPCHK(c, hipStreamSynchronize(s));
-            HIPCHK(c, hipMemcpy(t, d_ctrace, sizeof t, hipMemcpyDeviceToHost));
-            float cms = 0; (void)hipEventElapsedTime(&cms, c->chain_ev[2 * n_chain_ev - 2], c->chain_ev[2 * n_chain_ev - 1]);
-            fprintf(stderr, "[leon chain] window [%llu, %llu): %u reads left by the rounds; %llu steps of 64, %.2f ballot iterations and %.1f entry rows per step, %llu inserters; %.2f ms; per step the settler waited %.0f (tester: %.0f), settled + published %.0f ticks of s_memtime\n",
-                    (unsigned long long)w0, (unsigned long long)w1, left, t[0], t[0] ? (double)t[1] / t[0] : 0.0, t[0] ? (double)t[2] / t[0] : 0.0, t[3], cms,
-                    t[0] ? (double)t[4] / t[0] : 0.0, t[0] ? (double)t[5] / t[0] : 0.0, t[0] ? (double)t[6] / t[0] : 0.0);
-        }
-        return LEON_OK;
-    };
-    for (uint64_t w0 = 0, w1 = 0; w0 < n; w0 = w1) {
-        w1 = std::min(n, w0 + (w0 == 0 ? first_window(W) : W));
-        if (int rc = dict_reserve(c, c->n_keys + (w1 - w0))) return rc;
-        HIPCHK(c, hipMemsetAsync(counters, 0, 8, s));
-        HIPCHK(c, hipMemsetAsync(c->wbits.p, 0, (1ull << WBITS_LOG2) / 8, s));
-        HIPCHK(c, hipMemsetAsync(c->pbits.p, 0, (1ull << WBITS_LOG2) / 8, s));
-        if (!share_lookups) launch_lookup_cand(s, R, c->B, c->d_rv16, c->D, V, w0, w1, first_read_index, lists[0], counters, d_trace);
-        else {
-            // The window's look-ups divided among the ranks (leon_dna_set_gather): rank r takes the r-th run of P reads, everybody
-            // learns what everybody found from ONE all-gather of a word per read -- the caller's -- and makes the other runs' results
-            // its own (k_lookup_apply): every rank's dictionary goes on holding every proposal, as if it had looked everything up.
-            const uint64_t P = (w1 - w0 + Wn - 1) / Wn;
-            auto run_of = [&](uint32_t r, uint64_t& a, uint64_t& b) { a = std::min(w1, w0 + (uint64_t)r * P); b = std::min(w1, a + P); };
-            HIPCHK(c, c->xch_res.ensure((uint64_t)Wn * P * 8));
-            uint64_t* xres = c->xch_res.as<uint64_t>();
-            uint64_t s0 = 0, s1 = 0;
-            run_of(c->shard_rank, s0, s1);
-            launch_lookup_cand(s, R, c->B, c->d_rv16, c->D, V, s0, s1, first_read_index, lists[0], counters, d_trace, xres, w0, false);
-            HIPCHK(c, hipStreamSynchronize(s));
-            const auto t_l0 = std::chrono::steady_clock::now();
-            if (c->xch_mode == LEON_XCH_BY_ANCHOR) {
-                if (c->gather_fn(c->gather_user, xres, P * 8, Wn)) return fail(c, LEON_E_STATE, "the gather callback returned non-zero");
-                HIPCHK(c, hipSetDevice(c->device));               // (the callback may have changed the thread's device)
-                lk_call_ms += (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_l0).count();
-            } else {                                              // no other rank present: their runs computed here, leaving nothing but their words
-                for (uint32_t r = 0; r < Wn; r++) {
-                    if (r == c->shard_rank) continue;
-                    uint64_t a = 0, b = 0;
-                    run_of(r, a, b);
-                    launch_lookup_cand(s, R, c->B, c->d_rv16, c->D, V, a, b, first_read_index, lists[0], counters, nullptr, xres, w0, true);
-                }
-                HIPCHK(c, hipStreamSynchronize(s));
-                lk_emul_ms += (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_l0).count();
-            }
-            launch_lookup_apply(s, R, c->D, V, w0, w1, s0, s1, first_read_index, xres, lists[0], counters);
-        }
-        HIPCHK(c, hipMemcpyAsync(d_hist, counters, 4, hipMemcpyDeviceToDevice, s));         // hist[0]: the window's unresolved reads
-        int cur = 0;
-        uint32_t n_hist = 1, cnt = 0, cnt0 = 0;
-        bool first_wait = true;
-        // (Fewer rounds ahead for a file whose last window left the sequential pass most of its list -- position-sorted reads -- were
-        // measured and are slower: rounds 2 and 3 settle the reads that contain round 1's inserters, 15 M of a sorted 100 M-read
-        // file's, in 180 ms; the sequential pass takes 18 ns for each of them.  1 929 ms against 1 838 for the stage.)
-        for (uint32_t ahead = kRoundsAhead;; ahead = kRoundsMore) {
-            for (uint32_t r = 0; r < ahead && n_hist < kHist; r++) {
-                const int nxt = cur ^ 1;
-                const uint32_t h = std::max<uint32_t>(hint >> (2 * (n_hist - 1) < 31 ? 2 * (n_hist - 1) : 31), 4096);
-                HIPCHK(c, hipMemsetAsync(counters + nxt, 0, 4, s));
-                launch_check(s, R, c->D, V, first_read_index, lists[cur], counters + cur, h, lists[nxt], counters + nxt);
-                HIPCHK(c, hipMemcpyAsync(d_hist + n_hist, counters + nxt, 4, hipMemcpyDeviceToDevice, s));
-                launch_reset_tent(s, c->D, V, lists[cur], counters + cur, h);
-                launch_propose(s, c->D, V, first_read_index, lists[nxt], counters + nxt, h);
-                cur = nxt; n_hist++;
-            }
-            HIPCHK(c, hipMemcpyAsync(c->h_rb + 8, d_hist, n_hist * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipMemcpyAsync(c->h_rb + 1, c->D.err, 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, spin_sync(s));
-            if (first_wait) { hand_over(); first_wait = false; }
-            if ((int)(uint32_t)c->h_rb[1]) {
-                HIPCHK(c, hipMemsetAsync(c->D.err, 0, 4, s));
-                if ((int)(uint32_t)c->h_rb[1] == 2)
-                    return fail(c, LEON_E_STATE, "the look-ups gathered from the other ranks do not fit this rank's reads or dictionary (were all ranks fed the same batches?)");
-                return fail(c, LEON_E_STATE, "anchor dictionary: a two-word key stayed half-written (a stalled wave); batch abandoned");
-            }
-            const uint32_t* hist = reinterpret_cast<const uint32_t*>(c->h_rb + 8);
-            cnt0 = hist[0];
-            for (uint32_t r = 1; r < n_hist; r++)
-                if (hist[r - 1] > 0 && hist[r] >= hist[r - 1]) return fail(c, LEON_E_STATE, "anchor resolution made no progress (internal error)");
-            cnt = hist[n_hist - 1];
-            if (cnt == 0) {
-                for (uint32_t r = 1; r < n_hist; r++) if (hist[r - 1] > 0) c->stats.resolve_rounds++;
-                break;
-            }
-            // more rounds only while they pay: the list at least halved in the last round and the budget is not spent
-            const bool halving = n_hist >= 2 && 2ull * hist[n_hist - 1] <= hist[n_hist - 2];
-            if (!halving || n_hist - 1 >= kRoundsMax || n_hist + kRoundsMore > kHist) {
-                for (uint32_t r = 1; r < n_hist; r++) if (hist[r - 1] > 0) c->stats.resolve_rounds++;
-                if (int rc = chain_tail(cnt, w0, w1, lists[cur ^ 1])) return rc;
-                break;
-            }
-        }
-        hint = std::max<uint32_t>(2 * cnt0, 4096);
-        if (cnt0 > 0) {
-            launch_final_pos(s, R, c->D, V, w0, w1, first_read_index);
-            launch_ins_flags(s, V, w0, w1);
-            HIPCHK(c, prim::ExclusiveSum(c->cub_tmp.p, scan_tmp, V.ins_flag, c->rank.as<uint32_t>(), w1 - w0, s));
-            uint32_t last_rank = 0, last_flag = 0;
-            HIPCHK(c, hipMemcpyAsync(c->h_rb + 0, c->rank.as<uint32_t>() + (w1 - w0 - 1), 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipMemcpyAsync(c->h_rb + 1, V.ins_flag + (w1 - w0 - 1), 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipMemcpyAsync(c->h_rb + 2, c->d_nkeys, 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, spin_sync(s));
-            last_rank = (uint32_t)c->h_rb[0]; last_flag = (uint32_t)c->h_rb[1]; c->n_keys = c->h_rb[2];
-            uint64_t n_new = (uint64_t)last_rank + last_flag;
-            if (c->n_anchors + n_new > 0xFFFFFFFFull) return fail(c, LEON_E_OVERFLOW, "more than 2^32 anchors");
-            if ((c->n_anchors + n_new) * 8 * KW > c->anchor_kmers.cap) {      // grow, keeping what is there
-                TmpBuf nb;
-                HIPCHK(c, nb.ensure(std::max<uint64_t>((c->n_anchors + n_new) * 2, 1024) * 8 * KW));
-                if (c->n_anchors) HIPCHK(c, hipMemcpyAsync(nb.p, c->anchor_kmers.p, c->n_anchors * 8 * KW, hipMemcpyDeviceToDevice, s));
-                HIPCHK(c, hipStreamSynchronize(s));
-                std::swap(static_cast<DevBuf&>(nb).p, c->anchor_kmers.p);        // nb now holds the old buffer and releases it
-                std::swap(static_cast<DevBuf&>(nb).cap, c->anchor_kmers.cap);
-            }
-            launch_assign_addr(s, c->D, V, w0, w1, c->rank.as<uint32_t>(), c->n_anchors, c->anchor_kmers.as<uint64_t>(), k);
-            if (n_new && c->shard_rank == 0 && !(c->cfg.flags & LEON_F_DICT_ON_DEVICE)) {   // the window's new anchors, for the host thread coding the dictionary stream
-                HIPCHK(c, hipMemcpyAsync(c->h_anchor[anchor_buf], c->anchor_kmers.as<uint64_t>() + c->n_anchors * KW, n_new * 8 * KW, hipMemcpyDeviceToHost, s));
-                pending.buf = anchor_buf; pending.n = n_new;
-                anchor_buf ^= 1;
-                if (w0 == 0) {
-                    HIPCHK(c, spin_sync(s));
-                    hand_over();
-                    mark("first window's anchors to the chain");
-                }
-            }
-            c->n_anchors += n_new;
-        }
-        launch_finalize_reads(s, R, c->D, V, w0, w1);
-        while (w1 < n && packed_upto < std::min(n, w1 + W)) { if (int rc = pack_group()) return rc; }   // the next window's reads
-        c->stats.resolve_windows++;
-    }
-    if (pending.buf >= 0) { HIPCHK(c, spin_sync(s)); hand_over(); }
-    if (trace_resolve) {
-        unsigned long long t[12];
-        HIPCHK(c, hipMemcpy(t, d_trace, sizeof t, hipMemcpyDeviceToHost));
-        const char* cls[3] = {"found an anchor of the dictionary", "went on to propose its own", "no anchor at all"};
-        for (int j = 0; j < 3; j++)
-            if (t[4 * j]) fprintf(stderr, "[leon resolve] k_lookup_cand, reads that %-34s: %10llu reads, per read %.1f filter probes, %.1f dictionary probes behind a filter maybe, %.1f k-mers through the bloom\n",
-                                  cls[j], t[4 * j], (double)t[4 * j + 1] / t[4 * j], (double)t[4 * j + 2] / t[4 * j], (double)t[4 * j + 3] / t[4 * j]);
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev[2], s));
-    mark("resolution launched to its end");
-    // ---- this rank's share of the batch: a contiguous range of whole blocks (all of it when not sharded) ----
-    uint64_t lb0 = 0, lb1 = n_blocks;
-    if (c->shard_world > 1) {
-        const uint64_t q = n_blocks / c->shard_world, rm = n_blocks % c->shard_world, rk = c->shard_rank;
-        lb0 = rk * q + std::min<uint64_t>(rk, rm);
-        lb1 = lb0 + q + (rk < rm ? 1 : 0);
-    }
-    const uint64_t nbl = lb1 - lb0;
-    const uint64_t r0 = std::min<uint64_t>(n, lb0 * rpb), r1 = std::min<uint64_t>(n, lb1 * rpb), nl = r1 - r0;
-    uint64_t off_r0 = off_first, off_r1 = off_last;
-    if (c->shard_world > 1) {
-        HIPCHK(c, hipMemcpy(&off_r0, d_off + r0, 8, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(&off_r1, d_off + r1, 8, hipMemcpyDeviceToHost));
-    }
-    const uint64_t nl_bases = off_r1 - off_r0;
-    R.ev_origin = r0;
-    auto ms = [&](int a, int b) { float v = 0; (void)hipEventElapsedTime(&v, c->ev[a], c->ev[b]); return v; };
-    auto chain_ms = [&]() { float t = 0; for (uint32_t e = 0; e < n_chain_ev; e++) { float v = 0; (void)hipEventElapsedTime(&v, c->chain_ev[2 * e], c->chain_ev[2 * e + 1]); t += v; } return t; };
-    c->stats.n_reads = nl; c->stats.n_bases = nl_bases; c->stats.n_blocks = nbl; c->stats.n_anchors = c->n_anchors;
-    c->last_n = n; c->last_bases = nl_bases;
-    c->last_d_bases = d_bases; c->last_d_off = d_off;
-    const bool by_anchor = c->shard_world > 1 && c->xch_mode != LEON_XCH_OFF;
-    if (nl == 0 && !(by_anchor && c->xch_mode == LEON_XCH_BY_ANCHOR)) {   // nothing of this batch is ours to encode (and nobody waits for our slice)
-        HIPCHK(c, hipStreamSynchronize(s));
-        float pack2 = 0; for (uint32_t e = 1; e < n_pack_ev; e++) { float v = 0; (void)hipEventElapsedTime(&v, c->pack_ev[2 * e], c->pack_ev[2 * e + 1]); pack2 += v; }
-        c->stats.ms_pack = ms(0, 1) + pack2; c->stats.ms_resolve = ms(1, 2) - pack2; c->stats.ms_resolve_chain = chain_ms(); c->stats.ms_total = ms(0, 2);
-        c->next_read += n; c->next_block += n_blocks;
-        if (n % rpb) c->partial_seen = true;
-        c->poisoned = false;
-        return LEON_OK;
-    }
-    HIPCHK(c, c->events.ensure(nl_bases + 16));
-    HIPCHK(c, hipMemsetAsync(c->events.p, 0, nl_bases + 16, s));
-    // the walk's path cache: a 64-byte bucket per ~8 solid k-mers (the bloom's size says how many there are), at most an eighth of the
-    // free device memory; EMPTY again at every batch -- what a batch's walkers learn from the bloom is shared among THEM, a later
-    // batch (or a bench step) starts cold.  LEON_WALK_CACHE=0: off; LEON_WALK_CACHE_LOG2: log2 of the buckets (measurement)
-    WalkCache wc{nullptr, 0, 28, 0};
-    {
-        static const int wc_env = [] { const char* e = getenv("LEON_WALK_CACHE"); return e ? atoi(e) : 1; }();
-        static const int wc_log2 = [] { const char* e = getenv("LEON_WALK_CACHE_LOG2"); return e ? atoi(e) : 0; }();
-        // (not for a rank of four or more: the walkers that cover one genome region are spread over all ranks' slices, a rank's own cache
-        // would answer a fifth of its look-ups and cost as much as it saves)
-        if (wc_env && c->B.n_hash == 7 && c->shard_world <= 2) {
-            uint64_t want = c->cfg.bloom_tai / 12 / 8, buckets = 1024;
-            while (buckets < want && buckets < (1ull << 27)) buckets <<= 1;          // at most 2^27 buckets = 8 GiB
-            if (wc_log2 >= 10 && wc_log2 <= 31) buckets = 1ull << wc_log2;
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) while (buckets > 1024 && buckets * 64 > c->wcache.cap && buckets * 64 > free_b / 8) buckets >>= 1;
-            if (c->wcache.ensure(buckets * 64) == hipSuccess) {
-                wc.slots = c->wcache.as<uint64_t>(); wc.bucket_mask = buckets - 1;
-                static const int hop_log2 = [] { const char* e = getenv("LEON_WALK_HOP_LOG2"); const int v = e ? atoi(e) : 4; return v >= 1 && v <= 8 ? v : 4; }();
-                wc.hop_shift = 32 - hop_log2;
-
-                launch_walk_cache_init(s, wc, k);
-
-            } else (void)hipGetLastError();
-        }
-    }
-    HIPCHK(c, c->perm.ensure(n * 4));
-    hipLaunchKernelGGL(k_iota, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 8192)), dim3(256), 0, s, c->perm.as<uint32_t>(), n);
-    size_t sort_tmp = 0;
-    if (!by_anchor) {
-        // ---- sort the share's reads by (anchor address, strand) ----
-        HIPCHK(c, c->sort_key2.ensure(nl * 8)); HIPCHK(c, c->perm2.ensure(nl * 4));
-        // (measurement hook: another order of the reads in the walk changes which lanes share bloom sectors, never the bytes --
-        // events are indexed by read position)
-        const uint64_t* walk_key = walk_keys ? walk_keys + r0 : V.sort_key + r0;
-        const unsigned key_bits = walk_keys ? 48u : 33u;
-        HIPCHK(c, prim::SortPairs(nullptr, sort_tmp, walk_key, c->sort_key2.as<uint64_t>(), c->perm.as<uint32_t>() + r0,
-                                                     c->perm2.as<uint32_t>(), nl, 0, key_bits, s));
-        if (int rc = ensure_cub(c, sort_tmp)) return rc;
-        HIPCHK(c, prim::SortPairs(c->cub_tmp.p, sort_tmp, walk_key, c->sort_key2.as<uint64_t>(), c->perm.as<uint32_t>() + r0,
-                                                     c->perm2.as<uint32_t>(), nl, 0, key_bits, s));
-        HIPCHK(c, hipEventRecord(c->ev[3], s));
-        // ---- walk ----
-        HIPCHK(c, hipEventRecord(c->ev[4], s));
-        launch_walk(s, R, c->B, c->d_rv16, V.anchor_pos, V.flags, c->perm2.as<uint32_t>(), nl, c->events.as<uint8_t>(), nullptr, wc);
-        HIPCHK(c, hipEventRecord(c->ev[5], s));
-        c->stats.walk_launches = 1; c->stats.walk_reads = nl;
-    } else {
-        // ---- the walk divided by anchor (leon_dna_set_exchange): ALL of the batch's reads sorted by anchor address, cut into `world`
-        // slices of equal size; this rank walks its slice into a buffer of its own and what it found goes to the ranks that code
-        // the reads' blocks, as (place in that rank's event buffer, byte) words grouped by destination ----
-        const uint32_t Wd = c->shard_world, me = c->shard_rank;
-        if (Wd + 2 > 4096 / 8) return fail(c, LEON_E_INVALID, "set_exchange: world too large");
-        HIPCHK(c, c->sort_key2.ensure(n * 8)); HIPCHK(c, c->perm2.ensure(n * 4));
-        HIPCHK(c, prim::SortPairs(nullptr, sort_tmp, V.sort_key, c->sort_key2.as<uint64_t>(), c->perm.as<uint32_t>(), c->perm2.as<uint32_t>(), n, 0, 33, s));
-        if (int rc = ensure_cub(c, sort_tmp)) return rc;
-        HIPCHK(c, prim::SortPairs(c->cub_tmp.p, sort_tmp, V.sort_key, c->sort_key2.as<uint64_t>(), c->perm.as<uint32_t>(), c->perm2.as<uint32_t>(), n, 0, 33, s));
-        unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(c->counters.as<uint32_t>() + 10);
-        launch_lower_bound(s, c->sort_key2.as<uint64_t>(), n, 1ull << 32, d_cnt);            // reads without an anchor sort last: nothing to walk
-        HIPCHK(c, hipMemcpyAsync(c->h_rb + 0, d_cnt, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, spin_sync(s));
-        const uint64_t n_anch = c->h_rb[0];
-        // the slices: equal WEIGHT (a read 1, an anchor group's first read SLICE_GROUP_WEIGHT more), the same cuts on every rank
-        HIPCHK(c, c->xch_slot.ensure(n * 4)); HIPCHK(c, c->xch_off.ensure((n + 1) * 8));
-        size_t scan_n = 0;
-        HIPCHK(c, prim::ExclusiveSum(nullptr, scan_n, c->xch_off.as<uint64_t>(), c->xch_off.as<uint64_t>(), n + 1, s));
-        if (int rc = ensure_cub(c, scan_n)) return rc;
-        HIPCHK(c, c->xch_split.ensure((Wd + 1) * 8));
-        launch_slice_weights(s, c->sort_key2.as<uint64_t>(), n_anch, c->xch_off.as<uint64_t>());
-        HIPCHK(c, prim::ExclusiveSum(c->cub_tmp.p, scan_n, c->xch_off.as<uint64_t>(), c->xch_off.as<uint64_t>(), n_anch + 1, s));
-        launch_slice_splits(s, c->xch_off.as<uint64_t>(), n_anch, Wd, c->xch_split.as<unsigned long long>());
-        HIPCHK(c, hipMemcpyAsync(c->h_rb + 0, c->xch_split.p, (Wd + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipEventRecord(c->ev[3], s));
-        HIPCHK(c, spin_sync(s));
-        std::vector<uint64_t> slice_at(c->h_rb, c->h_rb + Wd + 1);
-        // where each rank's reads begin in file order (block_range of every rank), for the words' grouping
-        std::vector<uint64_t> rank_r0(Wd + 1);
-        for (uint32_t d = 0; d <= Wd; d++) {
-            const uint64_t q = n_blocks / Wd, rm = n_blocks % Wd;
-            rank_r0[d] = std::min<uint64_t>(n, (d * q + std::min<uint64_t>(d, rm)) * rpb);
-        }
-        std::vector<uint64_t> send_counts(Wd, 0), send_at(Wd + 1, 0);
-        // one slice: walked into xch_events, its words formed in xch_send (grouped by destination; send_at[d] = where rank d's begin)
-        auto do_slice = [&](uint32_t sl, bool timed) -> int {
-            const uint64_t s0 = slice_at[sl], s1 = slice_at[sl + 1], ns = s1 - s0;
-            const uint32_t* slice = c->perm2.as<uint32_t>() + s0;
-            HIPCHK(c, c->xch_evoff.ensure((ns + 1) * 8));
-            HIPCHK(c, hipMemsetAsync(c->xch_slot.p, 0xFF, n * 4, s));
-            launch_slice_reads(s, R, slice, ns, c->xch_evoff.as<uint64_t>(), c->xch_slot.as<uint32_t>());
-            size_t tb = 0;
-            HIPCHK(c, prim::ExclusiveSum(nullptr, tb, c->xch_evoff.as<uint64_t>(), c->xch_evoff.as<uint64_t>(), ns + 1, s));
-            if (int rc = ensure_cub(c, std::max(tb, scan_n))) return rc;
-            HIPCHK(c, prim::ExclusiveSum(c->cub_tmp.p, tb, c->xch_evoff.as<uint64_t>(), c->xch_evoff.as<uint64_t>(), ns + 1, s));
-            HIPCHK(c, hipMemcpyAsync(c->h_rb + 0, c->xch_evoff.as<uint64_t>() + ns, 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, spin_sync(s));
-            const uint64_t slice_bases = c->h_rb[0];
-            HIPCHK(c, c->xch_events.ensure(slice_bases + 16));
-            HIPCHK(c, hipMemsetAsync(c->xch_events.p, 0, slice_bases + 16, s));
-            if (timed) HIPCHK(c, hipEventRecord(c->ev[4], s));
-            launch_walk(s, R, c->B, c->d_rv16, V.anchor_pos, V.flags, slice, ns, c->xch_events.as<uint8_t>(), c->xch_evoff.as<uint64_t>(), wc);
-            if (timed) { HIPCHK(c, hipEventRecord(c->ev[5], s)); c->stats.walk_launches = 1; c->stats.walk_reads = ns; }
-            launch_ev_words(s, R, c->xch_slot.as<uint32_t>(), c->xch_evoff.as<uint64_t>(), c->xch_events.as<uint8_t>(), n, rpb, n_blocks, Wd,
-                            c->xch_off.as<uint64_t>(), nullptr);
-            HIPCHK(c, prim::ExclusiveSum(c->cub_tmp.p, scan_n, c->xch_off.as<uint64_t>(), c->xch_off.as<uint64_t>(), n + 1, s));
-            for (uint32_t d = 0; d <= Wd; d++) HIPCHK(c, hipMemcpyAsync(c->h_rb + 1 + d, c->xch_off.as<uint64_t>() + rank_r0[d], 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, spin_sync(s));
-            for (uint32_t d = 0; d <= Wd; d++) send_at[d] = c->h_rb[1 + d];
-            for (uint32_t d = 0; d < Wd; d++) send_counts[d] = send_at[d + 1] - send_at[d];
-            HIPCHK(c, c->xch_send.ensure(send_at[Wd] * 8 + 64));
-            launch_ev_words(s, R, c->xch_slot.as<uint32_t>(), c->xch_evoff.as<uint64_t>(), c->xch_events.as<uint8_t>(), n, rpb, n_blocks, Wd,
-                            c->xch_off.as<uint64_t>(), c->xch_send.as<uint64_t>());
-            HIPCHK(c, hipGetLastError());
-            return LEON_OK;
-        };
-        HIPCHK(c, hipMemsetAsync(c->errflag.as<int>() + 1, 0, 4, s));
-        const auto t_x0 = std::chrono::steady_clock::now();     // (ms_exchange: everything of the division that is not the slice's walk itself)
-        if (int rc = do_slice(me, true)) return rc;
-        HIPCHK(c, hipStreamSynchronize(s));
-        float walk_own = 0; (void)hipEventElapsedTime(&walk_own, c->ev[4], c->ev[5]);
-        auto since = [](std::chrono::steady_clock::time_point t) { return (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-        c->stats.xch_words_sent = send_at[Wd];
-        if (c->xch_mode == LEON_XCH_BY_ANCHOR) {
-            const uint64_t* d_recv = nullptr; uint64_t recv_total = 0;
-            const auto t_call = std::chrono::steady_clock::now();
-            if (c->xch_fn(c->xch_user, c->xch_send.as<uint64_t>(), send_counts.data(), Wd, &d_recv, &recv_total))
-                return fail(c, LEON_E_STATE, "the exchange callback returned non-zero");
-            c->stats.ms_exchange_call = since(t_call);
-            if (recv_total && !d_recv) return fail(c, LEON_E_STATE, "the exchange callback returned no buffer");
-            c->stats.xch_words_received = recv_total;
-            HIPCHK(c, hipSetDevice(c->device));                   // (the callback may have changed the thread's device)
-            launch_ev_scatter(s, d_recv, recv_total, c->events.as<uint8_t>(), nl_bases, c->errflag.as<int>() + 1);
-            HIPCHK(c, hipStreamSynchronize(s));                   // the caller's buffer is free again when this call returns
-            c->stats.ms_exchange = since(t_x0) - walk_own;
-        } else {
-            // no other rank present: this context plays them all, one slice after the other, and keeps what is meant for its own rank
-            launch_ev_scatter(s, c->xch_send.as<uint64_t>() + send_at[me], send_counts[me], c->events.as<uint8_t>(), nl_bases, c->errflag.as<int>() + 1);
-            c->stats.xch_words_received = send_counts[me];
-            HIPCHK(c, hipStreamSynchronize(s));
-            c->stats.ms_exchange = since(t_x0) - walk_own;
-            const auto t_e0 = std::chrono::steady_clock::now();
-            for (uint32_t sl = 0; sl < Wd; sl++) {
-                if (sl == me) continue;
-                if (int rc = do_slice(sl, false)) return rc;
-                launch_ev_scatter(s, c->xch_send.as<uint64_t>() + send_at[me], send_counts[me], c->events.as<uint8_t>(), nl_bases, c->errflag.as<int>() + 1);
-                c->stats.xch_words_received += send_counts[me];
-            }
-            HIPCHK(c, hipStreamSynchronize(s));
-            c->stats.ms_emulated = since(t_e0);
-        }
-        // (the window look-ups shared out among the ranks, earlier in this call: their gathers and, emulated, the other ranks' runs)
-        c->stats.ms_exchange_call += lk_call_ms; c->stats.ms_exchange += lk_call_ms; c->stats.ms_gather_call = lk_call_ms;
-        c->stats.ms_emulated += lk_emul_ms; c->stats.ms_emulated_lookups = lk_emul_ms;
-        HIPCHK(c, hipEventRecord(c->ev[9], s));                  // the symbols stage begins here
-        int xerr = 0;
-        HIPCHK(c, hipMemcpy(&xerr, c->errflag.as<int>() + 1, 4, hipMemcpyDeviceToHost));
-        if (xerr) return fail(c, LEON_E_STATE, "the exchange delivered a word that lies outside this rank's blocks");
-        if (nl == 0) {                                           // our slice is delivered; no block of the batch is ours to code
-            float pack2 = 0; for (uint32_t e = 1; e < n_pack_ev; e++) { float v = 0; (void)hipEventElapsedTime(&v, c->pack_ev[2 * e], c->pack_ev[2 * e + 1]); pack2 += v; }
-            c->stats.ms_pack = ms(0, 1) + pack2; c->stats.ms_resolve = ms(1, 2) - pack2; c->stats.ms_resolve_chain = chain_ms(); c->stats.ms_sort = ms(2, 3); c->stats.ms_walk = ms(4, 5); c->stats.ms_total = ms(0, 5);
-            c->next_read += n; c->next_block += n_blocks;
-            if (n % rpb) c->partial_seen = true;
-            c->poisoned = false;
-            return LEON_OK;
-        }
-    }
-
-    // ---- symbols ----
-    HIPCHK(c, c->prev.ensure(n * 8));
-    HIPCHK(c, c->sym_off.ensure((nl + 1) * 8));
-    HIPCHK(c, c->nerr.ensure(nl * 8));                         // (two words per read: error positions, chunks that hold events)
-    launch_prev_anchored(s, V.anchor_pos, n, rpb, lb0, nbl, c->prev.as<int64_t>());
-    HIPCHK(c, hipMemsetAsync(c->sym_off.as<uint64_t>() + nl, 0, 8, s));
-    launch_symbols(s, R, V.anchor_pos, V.anchor_addr, V.flags, c->prev.as<int64_t>(), c->events.as<uint8_t>(), r0, nl,
-                   c->sym_off.as<uint64_t>(), c->nerr.as<uint32_t>(), nullptr);
-    HIPCHK(c, prim::ExclusiveSum(nullptr, tmp_bytes, c->sym_off.as<uint64_t>(), c->sym_off.as<uint64_t>(), nl + 1, s));
-    if (int rc = ensure_cub(c, tmp_bytes)) return rc;
-    HIPCHK(c, prim::ExclusiveSum(c->cub_tmp.p, tmp_bytes, c->sym_off.as<uint64_t>(), c->sym_off.as<uint64_t>(), nl + 1, s));
-    uint64_t n_syms = 0, max_block_syms = 0;
-    unsigned long long* d_max = reinterpret_cast<unsigned long long*>(c->counters.as<uint32_t>() + 8);
-    HIPCHK(c, hipMemsetAsync(d_max, 0, 8, s));
-    launch_max_block_syms(s, c->sym_off.as<uint64_t>(), nl, rpb, nbl, d_max);
-    HIPCHK(c, hipMemcpyAsync(&n_syms, c->sym_off.as<uint64_t>() + nl, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(&max_block_syms, d_max, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    HIPCHK(c, c->syms.ensure(n_syms * 2 + 256));
-    launch_symbols(s, R, V.anchor_pos, V.anchor_addr, V.flags, c->prev.as<int64_t>(), c->events.as<uint8_t>(), r0, nl,
-                   c->sym_off.as<uint64_t>(), c->nerr.as<uint32_t>(), c->syms.as<uint8_t>());
-    HIPCHK(c, c->blk_begin.ensure((nbl + 1) * 8)); HIPCHK(c, c->out_off.ensure((nbl + 1) * 8));
-    HIPCHK(c, c->out_size.ensure(nbl * 8)); HIPCHK(c, c->dst_off.ensure((nbl + 1) * 8));
-    launch_block_ranges(s, c->sym_off.as<uint64_t>(), nl, rpb, nbl, c->blk_begin.as<uint64_t>(), c->out_off.as<uint64_t>());
-    HIPCHK(c, hipEventRecord(c->ev[6], s));
-
-    // ---- range coder ----
-    bool host_chains = rc_on_host(nbl, n_syms, max_block_syms, c->shard_world);
-    std::vector<uint64_t> sizes(nbl), dst(nbl + 1, 0);
-    uint64_t payload_bytes = 0;
-    if (host_chains) {
-        // a small launch: the chains run on host cores, from the modelers' records (host_blocks.h)
-        const int rc = rc_blocks_on_host(c, c->syms.as<uint8_t>(), c->blk_begin.as<uint64_t>(), nbl, n_syms, SMALL_SIZES_DNA, N_SMALL_MODELS);
-        if (rc == 1) host_chains = false;                        // (no room for the records: the device's coder)
-        else if (rc) return rc;
-    }
-    if (host_chains) {
-        HIPCHK(c, hipEventRecord(c->ev[7], s));
-        for (uint64_t b = 0; b < nbl; b++) { sizes[b] = c->hb_coders[b].size(); dst[b + 1] = dst[b] + sizes[b]; }
-        payload_bytes = dst[nbl];
-        HIPCHK(c, hipEventRecord(c->ev[8], s));
-        HIPCHK(c, hipStreamSynchronize(s));
-    } else {
-    const uint64_t rc_cap = 3 * n_syms + 72 * (nbl + 1);
-    HIPCHK(c, c->rc_out.ensure(rc_cap));
-    HIPCHK(c, c->rc_scratch.ensure(rc_model_scratch_bytes(nbl)));
-    HIPCHK(c, hipMemsetAsync(c->errflag.p, 0, 4, s));
-    launch_rc_encode(s, c->syms.as<uint8_t>(), c->blk_begin.as<uint64_t>(), nbl, c->rc_out.as<uint8_t>(),
-                     c->out_off.as<uint64_t>(), c->out_size.as<uint64_t>(), c->rc_scratch.as<uint32_t>(), c->errflag.as<int>(), max_block_syms,
-                     SMALL_SIZES_DNA, true);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev[7], s));
-
-    // ---- gather + D2H ----
-    int errflag = 0;
-    HIPCHK(c, hipMemcpyAsync(sizes.data(), c->out_size.p, nbl * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(&errflag, c->errflag.p, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (errflag == 3) return fail(c, LEON_E_STATE, "a numeric value's byte count above 8 in the symbol stream (internal error)");
-    if (errflag) return fail(c, LEON_E_OVERFLOW, errflag == 2 ? "a read block has 2^32 symbols or more"
-                                                              : "range coder output exceeded its 3 bytes/symbol bound");
-    for (uint64_t b = 0; b < nbl; b++) dst[b + 1] = dst[b] + sizes[b];
-    payload_bytes = dst[nbl];
-    HIPCHK(c, c->payload.ensure(payload_bytes + 16));
-    HIPCHK(c, hipMemcpyAsync(c->dst_off.p, dst.data(), (nbl + 1) * 8, hipMemcpyHostToDevice, s));
-    launch_gather_payload(s, c->rc_out.as<uint8_t>(), c->out_off.as<uint64_t>(), c->dst_off.as<uint64_t>(), c->out_size.as<uint64_t>(),
-                          nbl, c->payload.as<uint8_t>());
-    if (payload_bytes + 16 > c->h_payload_cap) {
-        if (c->h_payload) HIPCHK(c, hipHostFree(c->h_payload));
-        c->h_payload = nullptr; c->h_payload_cap = 0;
-        size_t want = payload_bytes + payload_bytes / 4 + 4096;
-        HIPCHK(c, hipHostMalloc(&c->h_payload, want, hipHostMallocDefault));
-        c->h_payload_cap = want;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->h_payload, c->payload.p, payload_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipEventRecord(c->ev[8], s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    }
-
-    // ---- stats ----
-    c->stats.n_symbols = n_syms; c->stats.payload_bytes = payload_bytes;
-    float pack2 = 0;                                                   // the part of the pack stage that ran inside the resolution loop
-    for (uint32_t e = 1; e < n_pack_ev; e++) { float v = 0; (void)hipEventElapsedTime(&v, c->pack_ev[2 * e], c->pack_ev[2 * e + 1]); pack2 += v; }
-    c->stats.ms_pack = ms(0, 1) + pack2; c->stats.ms_resolve = ms(1, 2) - pack2; c->stats.ms_resolve_chain = chain_ms(); c->stats.ms_sort = ms(2, 3); c->stats.ms_walk = ms(4, 5);
-    c->stats.ms_symbols = by_anchor ? ms(9, 6) : ms(5, 6); c->stats.ms_rangecoder = ms(6, 7); c->stats.ms_d2h = ms(7, 8); c->stats.ms_total = ms(0, 8);
-
-    // ---- Leon::writeBlock, in block order ----
-    const uint8_t* hp = (const uint8_t*)c->h_payload;
-    for (uint64_t b = 0; b < nbl; b++) {
-        uint32_t nr = (uint32_t)std::min<uint64_t>(rpb, n - (lb0 + b) * rpb);
-        const uint8_t* pay = host_chains ? c->hb_coders[b].data() : hp + dst[b];
-        if (sink(user, c->next_block + lb0 + b, pay, sizes[b], nr)) return fail(c, LEON_E_SINK, "block sink returned non-zero");
-    }
-    c->next_read += n;
-    c->next_block += n_blocks;
-    if (n % rpb) c->partial_seen = true;
-    c->poisoned = false;
-    (void)k;
-    return LEON_OK;
 }
 
 int leon_dna_encode_batch(leon_dna_ctx* c, const uint8_t* bases, const uint64_t* off, uint64_t n, uint64_t first_read_index,
@@ -1375,23 +1466,14 @@ int leon_dna_reserve(leon_dna_ctx* c, uint64_t max_reads, uint64_t max_bases) {
     const uint64_t n = max_reads, rpb = c->cfg.reads_per_block, nbl = (n + rpb - 1) / rpb;
     const uint64_t n_slots = max_bases / 32 + n, W = std::min<uint64_t>(c->cfg.resolve_window, n), est_syms = 40 * n;
     HIPCHK(c, c->slot_off.ensure((n + 1) * 8));
-    HIPCHK(c, c->packed.ensure((n_slots * 2 + 16) * 4)); HIPCHK(c, c->nmask.ensure((n_slots + 4) * 4));
-    HIPCHK(c, c->rlen.ensure(n * 4)); HIPCHK(c, c->ncount.ensure(n * 4));
-    HIPCHK(c, c->status.ensure(n));
-    HIPCHK(c, c->hit_pos.ensure(n * 4)); HIPCHK(c, c->hit_slot.ensure(n * 4));
-    HIPCHK(c, c->cand_pos.ensure(n * 4)); HIPCHK(c, c->cand_slot.ensure(n * 4));
-    HIPCHK(c, c->anchor_pos.ensure(n * 4)); HIPCHK(c, c->anchor_addr.ensure(n * 4));
-    HIPCHK(c, c->flags.ensure(n)); HIPCHK(c, c->sort_key.ensure(n * 8));
-    HIPCHK(c, c->ins_flag.ensure(W * 4)); HIPCHK(c, c->rank.ensure(W * 4));
-    HIPCHK(c, c->ulist0.ensure(W * 4)); HIPCHK(c, c->ulist1.ensure(W * 4));
+    if (int rc = ensure_pack_bufs(c, n, n_slots)) return rc;
+    if (int rc = ensure_resolve_bufs(c, n, W)) return rc;
     HIPCHK(c, c->sort_key2.ensure(n * 8)); HIPCHK(c, c->perm.ensure(n * 4)); HIPCHK(c, c->perm2.ensure(n * 4));
     HIPCHK(c, c->events.ensure(max_bases + 16));
     HIPCHK(c, c->prev.ensure(n * 8)); HIPCHK(c, c->sym_off.ensure((n + 1) * 8)); HIPCHK(c, c->nerr.ensure(n * 8));
     HIPCHK(c, c->syms.ensure(est_syms * 2 + 256));
-    HIPCHK(c, c->blk_begin.ensure((nbl + 1) * 8)); HIPCHK(c, c->out_off.ensure((nbl + 1) * 8));
-    HIPCHK(c, c->out_size.ensure(nbl * 8)); HIPCHK(c, c->dst_off.ensure((nbl + 1) * 8));
-    HIPCHK(c, c->rc_out.ensure(3 * est_syms + 72 * (nbl + 1)));
-    HIPCHK(c, c->rc_scratch.ensure(rc_model_scratch_bytes(nbl)));
+    if (int rc = ensure_block_bufs(c, nbl)) return rc;
+    if (int rc = ensure_rc_bufs(c, nbl, est_syms)) return rc;
     HIPCHK(c, c->payload.ensure(max_bases / 12 + 4096));
     size_t t1 = 0, t2 = 0, t3 = 0;                               // the scans' and the sort's work space
     HIPCHK(c, prim::ExclusiveSum(nullptr, t1, c->slot_off.as<uint64_t>(), c->slot_off.as<uint64_t>(), n + 1, c->stream));
@@ -1399,20 +1481,11 @@ int leon_dna_reserve(leon_dna_ctx* c, uint64_t max_reads, uint64_t max_bases) {
                                                  n, 0, 33, c->stream));
     HIPCHK(c, prim::ExclusiveSum(nullptr, t3, c->ins_flag.as<uint32_t>(), c->rank.as<uint32_t>(), W, c->stream));
     if (int rc = ensure_cub(c, std::max(t1, std::max(t2, t3)))) return rc;
-    if (max_bases / 12 + 4096 > c->h_payload_cap) {
-        if (c->h_payload) HIPCHK(c, hipHostFree(c->h_payload));
-        c->h_payload = nullptr; c->h_payload_cap = 0;
-        const size_t want = max_bases / 12 + 4096;
-        HIPCHK(c, hipHostMalloc(&c->h_payload, want, hipHostMallocDefault));
-        c->h_payload_cap = want;
-    }
-    // the walk's path cache (sized as encode_batch sizes it: a bucket per ~8 solid k-mers, at most 2^27; best effort)
-    if (c->B.n_hash == 7 && c->shard_world <= 2) {
-        uint64_t want = c->cfg.bloom_tai / 12 / 8, buckets = 1024;
-        while (buckets < want && buckets < (1ull << 27)) buckets <<= 1;
-        size_t free_b = 0, total_b = 0;
+    if (int rc = ensure_host_payload(c, max_bases / 12 + 4096, max_bases / 12 + 4096)) return rc;
+    // the walk's path cache (as a batch sizes it: walk_cache_buckets; best effort)
+    size_t free_b = 0, total_b = 0;
+    if (const uint64_t buckets = walk_cache_buckets(c))
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && buckets * 64 <= free_b / 8 && c->wcache.ensure(buckets * 64) != hipSuccess) (void)hipGetLastError();
-    }
     // the dictionary: one anchor per ~6 reads of a 30x read set; it grows (rehash) if the data want more
     if (int rc = dict_reserve(c, c->n_keys + n / 6 + 1024)) return rc;
     if ((n / 6) * 8 * kmer_words(c->cfg.kmer_size) > c->anchor_kmers.cap && c->n_anchors == 0) HIPCHK(c, c->anchor_kmers.ensure((n / 6) * 8 * kmer_words(c->cfg.kmer_size)));
@@ -1446,83 +1519,15 @@ static int header_batch_impl(leon_dna_ctx* c, const uint8_t* d_hdr, const uint64
     HIPCHK(c, hipMemcpyAsync(&bad_offsets, c->counters.as<uint32_t>() + 4, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if (bad_offsets) return fail(c, LEON_E_INVALID, "offsets are not monotonic (or a header is longer than 2^31 bytes)");
-    // this rank's share: the same contiguous block range as the DNA stream's
-    uint64_t lb0 = 0, lb1 = n_blocks;
-    if (c->shard_world > 1) {
-        const uint64_t q = n_blocks / c->shard_world, rm = n_blocks % c->shard_world, rk = c->shard_rank;
-        lb0 = rk * q + std::min<uint64_t>(rk, rm);
-        lb1 = lb0 + q + (rk < rm ? 1 : 0);
-    }
-    const uint64_t nbl = lb1 - lb0;
-    const uint64_t r0 = std::min<uint64_t>(n, lb0 * rpb), r1 = std::min<uint64_t>(n, lb1 * rpb), nl = r1 - r0;
-    if (nl) {
+    const Share sh = share_of(c, n);                            // this rank's share: the same contiguous block range as the DNA stream's
+    if (sh.nl) {
         HIPCHK(c, c->hdr_first.ensure(first_len + 16));
         if (first_len) HIPCHK(c, hipMemcpyAsync(c->hdr_first.p, first_header, first_len, hipMemcpyHostToDevice, s));
-        HIPCHK(c, c->sym_off.ensure((nl + 1) * 8));
-        HIPCHK(c, hipMemsetAsync(c->sym_off.as<uint64_t>() + nl, 0, 8, s));
-        launch_hdr_symbols(s, d_hdr, d_off + r0, nl, rpb, c->hdr_first.as<uint8_t>(), (uint32_t)first_len, c->sym_off.as<uint64_t>(), nullptr);
-        size_t tmp_bytes = 0;
-        HIPCHK(c, prim::ExclusiveSum(nullptr, tmp_bytes, c->sym_off.as<uint64_t>(), c->sym_off.as<uint64_t>(), nl + 1, s));
-        if (int rc = ensure_cub(c, tmp_bytes)) return rc;
-        HIPCHK(c, prim::ExclusiveSum(c->cub_tmp.p, tmp_bytes, c->sym_off.as<uint64_t>(), c->sym_off.as<uint64_t>(), nl + 1, s));
-        uint64_t n_syms = 0, max_block_syms = 0;
-        unsigned long long* d_max = reinterpret_cast<unsigned long long*>(c->counters.as<uint32_t>() + 8);
-        HIPCHK(c, hipMemsetAsync(d_max, 0, 8, s));
-        launch_max_block_syms(s, c->sym_off.as<uint64_t>(), nl, rpb, nbl, d_max);
-        HIPCHK(c, hipMemcpyAsync(&n_syms, c->sym_off.as<uint64_t>() + nl, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(&max_block_syms, d_max, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        HIPCHK(c, c->syms.ensure(n_syms * 2 + 256));
-        launch_hdr_symbols(s, d_hdr, d_off + r0, nl, rpb, c->hdr_first.as<uint8_t>(), (uint32_t)first_len, c->sym_off.as<uint64_t>(), c->syms.as<uint8_t>());
-        HIPCHK(c, c->blk_begin.ensure((nbl + 1) * 8)); HIPCHK(c, c->out_off.ensure((nbl + 1) * 8));
-        HIPCHK(c, c->out_size.ensure(nbl * 8)); HIPCHK(c, c->dst_off.ensure((nbl + 1) * 8));
-        launch_block_ranges(s, c->sym_off.as<uint64_t>(), nl, rpb, nbl, c->blk_begin.as<uint64_t>(), c->out_off.as<uint64_t>());
-        bool host_chains = rc_on_host(nbl, n_syms, max_block_syms, c->shard_world);
-        std::vector<uint64_t> sizes(nbl), dst(nbl + 1, 0);
-        if (host_chains) {                                       // a small launch: the blocks' chains on host cores (host_blocks.h)
-            const int rc = rc_blocks_on_host(c, c->syms.as<uint8_t>(), c->blk_begin.as<uint64_t>(), nbl, n_syms, SMALL_SIZES_HEADER, N_SMALL_MODELS);
-            if (rc == 1) host_chains = false;
-            else if (rc) return rc;
-        }
-        if (host_chains) {
-            for (uint64_t b = 0; b < nbl; b++) { sizes[b] = c->hb_coders[b].size(); dst[b + 1] = dst[b] + sizes[b]; }
-        } else {
-        HIPCHK(c, c->rc_out.ensure(3 * n_syms + 72 * (nbl + 1)));
-        HIPCHK(c, c->rc_scratch.ensure(rc_model_scratch_bytes(nbl)));
-        HIPCHK(c, hipMemsetAsync(c->errflag.p, 0, 4, s));
-        launch_rc_encode(s, c->syms.as<uint8_t>(), c->blk_begin.as<uint64_t>(), nbl, c->rc_out.as<uint8_t>(), c->out_off.as<uint64_t>(),
-                         c->out_size.as<uint64_t>(), c->rc_scratch.as<uint32_t>(), c->errflag.as<int>(), max_block_syms, SMALL_SIZES_HEADER);
-        HIPCHK(c, hipGetLastError());
-        int errflag = 0;
-        HIPCHK(c, hipMemcpyAsync(sizes.data(), c->out_size.p, nbl * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(&errflag, c->errflag.p, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        if (errflag) return fail(c, LEON_E_OVERFLOW, errflag == 2 ? "a header block has 2^32 symbols or more"
-                                                                  : "range coder output exceeded its 3 bytes/symbol bound");
-        for (uint64_t b = 0; b < nbl; b++) dst[b + 1] = dst[b] + sizes[b];
-        const uint64_t payload_bytes = dst[nbl];
-        HIPCHK(c, c->payload.ensure(payload_bytes + 16));
-        HIPCHK(c, hipMemcpyAsync(c->dst_off.p, dst.data(), (nbl + 1) * 8, hipMemcpyHostToDevice, s));
-        launch_gather_payload(s, c->rc_out.as<uint8_t>(), c->out_off.as<uint64_t>(), c->dst_off.as<uint64_t>(), c->out_size.as<uint64_t>(),
-                              nbl, c->payload.as<uint8_t>());
-        if (payload_bytes + 16 > c->h_payload_cap) {
-            if (c->h_payload) HIPCHK(c, hipHostFree(c->h_payload));
-            c->h_payload = nullptr; c->h_payload_cap = 0;
-            size_t want = payload_bytes + payload_bytes / 4 + 4096;
-            HIPCHK(c, hipHostMalloc(&c->h_payload, want, hipHostMallocDefault));
-            c->h_payload_cap = want;
-        }
-        HIPCHK(c, hipMemcpyAsync(c->h_payload, c->payload.p, payload_bytes, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        }
-        const uint8_t* hp = (const uint8_t*)c->h_payload;
-        for (uint64_t b = 0; b < nbl; b++) {
-            const uint32_t nr = (uint32_t)std::min<uint64_t>(rpb, n - (lb0 + b) * rpb);
-            if (sink(user, c->hdr_next_block + lb0 + b, host_chains ? c->hb_coders[b].data() : hp + dst[b], sizes[b], nr)) {
-                c->poisoned = true;                             // the caller holds part of the batch's blocks
-                return fail(c, LEON_E_SINK, "block sink returned non-zero (stream poisoned: leon_dna_reset_stream to go on)");
-            }
-        }
+        auto symbols = [&](uint8_t* syms) { launch_hdr_symbols(s, d_hdr, d_off + sh.r0, sh.nl, rpb, c->hdr_first.as<uint8_t>(), (uint32_t)first_len,
+                                                                c->sym_off.as<uint64_t>(), syms); };
+        CodedBlocks out;
+        if (int rc = code_blocks(c, sh, symbols, SMALL_SIZES_HEADER, false, "header", out)) return rc;
+        if (int rc = deliver_blocks(c, out, sh, n, c->hdr_next_block, sink, user)) return rc;
     }
     c->hdr_next_read += n;
     c->hdr_next_block += n_blocks;
@@ -1534,7 +1539,9 @@ int leon_header_encode_batch_device(leon_dna_ctx* c, const uint8_t* d_headers, c
                                     const uint8_t* first_header, uint64_t first_header_len, leon_block_sink sink, void* user) {
     if (!c) return LEON_E_INVALID;
     if (c->poisoned) return fail(c, LEON_E_STATE, "an earlier batch failed part-way: the stream is unusable until leon_dna_reset_stream");
-    return header_batch_impl(c, d_headers, d_off, n, first_read_index, first_header, first_header_len, sink, user);
+    const int rc = header_batch_impl(c, d_headers, d_off, n, first_read_index, first_header, first_header_len, sink, user);
+    if (rc != LEON_OK && c->poisoned) c->err += kPoisonedNote;   // (a sink that refused a block)
+    return rc;
 }
 
 int leon_header_encode_batch(leon_dna_ctx* c, const uint8_t* headers, const uint64_t* off, uint64_t n, uint64_t first_read_index,
@@ -1569,21 +1576,16 @@ int leon_qual_smooth_batch_device(leon_dna_ctx* c, const uint8_t* d_bases, const
     hipStream_t s = c->stream;
     HIPCHK(c, c->slot_off.ensure((n + 1) * 8));
     HIPCHK(c, hipMemsetAsync(c->counters.as<uint32_t>() + 4, 0, 4, s));
-    launch_read_slots(s, d_off, n, c->slot_off.as<uint64_t>(), c->counters.as<uint32_t>() + 4);
-    size_t tmp_bytes = 0;
-    HIPCHK(c, prim::ExclusiveSum(nullptr, tmp_bytes, c->slot_off.as<uint64_t>(), c->slot_off.as<uint64_t>(), n + 1, s));
-    if (int rc = ensure_cub(c, tmp_bytes)) return rc;
-    HIPCHK(c, prim::ExclusiveSum(c->cub_tmp.p, tmp_bytes, c->slot_off.as<uint64_t>(), c->slot_off.as<uint64_t>(), n + 1, s));
+    uint64_t* slot_off = c->slot_off.as<uint64_t>();
+    launch_read_slots(s, d_off, n, slot_off, c->counters.as<uint32_t>() + 4);
+    if (int rc = run_prim(c, [&](void* t, size_t& b) { return prim::ExclusiveSum(t, b, slot_off, slot_off, n + 1, s); })) return rc;
     uint64_t n_slots = 0;
     uint32_t bad_offsets = 0;
-    HIPCHK(c, hipMemcpyAsync(&n_slots, c->slot_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(&n_slots, slot_off + n, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(&bad_offsets, c->counters.as<uint32_t>() + 4, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if (bad_offsets) return fail(c, LEON_E_INVALID, "offsets are not monotonic (or a read is longer than 2^31 bases)");
-    HIPCHK(c, c->packed.ensure((n_slots * 2 + 16) * 4));
-    HIPCHK(c, c->nmask.ensure((n_slots + 4) * 4));
-    HIPCHK(c, c->rlen.ensure(n * 4));
-    HIPCHK(c, c->ncount.ensure(n * 4));
+    if (int rc = ensure_pack_bufs(c, n, n_slots)) return rc;
     HIPCHK(c, hipMemsetAsync(c->packed.as<uint32_t>() + n_slots * 2, 0, 64, s));
     launch_pack(s, d_bases, d_off, c->slot_off.as<uint64_t>(), n, c->packed.as<uint32_t>(), c->nmask.as<uint32_t>(), c->rlen.as<uint32_t>(),
                 c->ncount.as<uint32_t>());
@@ -1607,10 +1609,8 @@ int leon_qual_smooth_batch_device(leon_dna_ctx* c, const uint8_t* d_bases, const
                                               c->sort_key.as<uint32_t>(), c->hit_pos.as<uint32_t>());
         else launch_read_minimizer(s, R, c->sort_key.as<uint32_t>(), c->hit_pos.as<uint32_t>());
         hipLaunchKernelGGL(k_iota, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 8192)), dim3(256), 0, s, c->perm.as<uint32_t>(), n);
-        size_t sort_tmp = 0;
-        HIPCHK(c, prim::SortPairs(nullptr, sort_tmp, c->sort_key.as<uint32_t>(), c->sort_key2.as<uint32_t>(), c->perm.as<uint32_t>(), c->perm2.as<uint32_t>(), n, 0, 32, s));
-        if (int rc = ensure_cub(c, sort_tmp)) return rc;
-        HIPCHK(c, prim::SortPairs(c->cub_tmp.p, sort_tmp, c->sort_key.as<uint32_t>(), c->sort_key2.as<uint32_t>(), c->perm.as<uint32_t>(), c->perm2.as<uint32_t>(), n, 0, 32, s));
+        auto sort = [&](void* t, size_t& b) { return prim::SortPairs(t, b, c->sort_key.as<uint32_t>(), c->sort_key2.as<uint32_t>(), c->perm.as<uint32_t>(), c->perm2.as<uint32_t>(), n, 0, 32, s); };
+        if (int rc = run_prim(c, sort)) return rc;
         launch_solid_flags(s, R, c->B, c->d_rv16, c->perm2.as<uint32_t>(), c->hit_pos.as<uint32_t>(), c->events.as<uint32_t>());
         launch_qual_rewrite(s, R, c->events.as<uint32_t>(), d_quals);
     } else launch_qual_smooth(s, R, c->B, c->d_rv16, d_quals);

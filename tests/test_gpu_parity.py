@@ -209,8 +209,14 @@ def test_toy_fasta_default_block_size():
     _full_compare(bases, off, 31, 50000)
 
 
-@pytest.mark.parametrize("kw", [dict(), dict(n_rate=0.003), dict(ragged=True, n_rate=0.001), dict(err=0.05)])
-def test_synthetic_bit_exact(kw):
+_SYNTH_KW = [dict(), dict(n_rate=0.003), dict(ragged=True, n_rate=0.001), dict(err=0.05)]
+
+
+@pytest.mark.parametrize("kw,walk_cache", [(kw, "1") for kw in _SYNTH_KW] + [(kw, "0") for kw in _SYNTH_KW],
+                         ids=["kw%d" % i for i in range(len(_SYNTH_KW))] + ["kw%d-no_walk_cache" % i for i in range(len(_SYNTH_KW))])
+def test_synthetic_bit_exact(monkeypatch, kw, walk_cache):
+    # LEON_WALK_CACHE is read at every batch: the walk's path cache on and off, in one process
+    monkeypatch.setenv("LEON_WALK_CACHE", walk_cache)
     bases, off = common.synthetic(6000, 150, 20000, seed=11, **kw)
     _full_compare(bases, off, 31, 1000)
 
