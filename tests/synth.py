@@ -1,4 +1,9 @@
 """Seeded synthetic read sets modelled on data/toy.fasta's generator fields (er0.01, indel0, rev0/1)."""
+import functools
+import json
+import os
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 
 _ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
@@ -140,3 +145,126 @@ def make_structured_reads(genome, n_reads, read_len, seed=43, order="sorted", er
     if n_rate > 0:
         b = np.where(rng.random(total) < n_rate, np.uint8(ord("N")), b)
     return np.ascontiguousarray(b, dtype=np.uint8), off
+
+
+# ---- window-scale inputs: millions of reads, any read range regenerated on its own -------------------------------------------------
+# The generators above draw every base of the file from one stream: at 2.3 M x 150 bp they take half a minute and 15-20 GB.  window_reads
+# draws what places a read (start, strand, length, duplicates, order) from one stream for the whole file -- a few integers per read -- and
+# its bases' noise per chunk of WINDOW_CHUNK reads from a stream of that chunk's own, so that reads [r0, r1) come out without the rest and
+# equal the same slice of the whole file, whatever the thread count.
+
+WINDOW_CHUNK = 1 << 16
+_SUB = np.zeros((256, 3), dtype=np.uint8)            # _SUB[b, r]: the r-th of the three bases other than b
+for _b in b"ACGT":
+    _SUB[_b] = [x for x in b"ACGT" if x != _b]
+
+
+def window_genome(g):
+    """g: {"kind": "iid" | "structured", "length", "seed"[, "dispersed", "tandem"]}"""
+    if g["kind"] == "iid":
+        return make_genome(g["length"], seed=g["seed"])
+    assert g["kind"] == "structured", g
+    return make_structured_genome(g["length"], seed=g["seed"], dispersed=g.get("dispersed", 4), tandem=g.get("tandem", 4))
+
+
+def window_placement(spec, G):
+    """(lens, starts, strand) of every read of the file (int64, int64, bool)"""
+    n, L = spec["n_reads"], spec["read_len"]
+    rng = np.random.default_rng(spec["seed"])
+    lens = rng.integers(max(1, L // 4), L + 1, size=n) if spec.get("ragged") else np.full(n, L, dtype=np.int64)
+    lens = np.minimum(lens, G).astype(np.int64)
+    span = np.maximum(G - lens + 1, 1)
+    u = rng.random(n)
+    if spec.get("skew", 0) > 0:
+        hot = rng.random(n) < spec["skew"]
+        lo = rng.random() * 0.9
+        u = np.where(hot, lo + 0.1 * u, u)
+    starts = (u * span).astype(np.int64)
+    strand = rng.integers(0, 2, size=n).astype(bool)
+    order = spec.get("order", "random")
+    assert order in ("random", "sorted", "pairs"), order
+    if order == "pairs":
+        half = n // 2
+        gap = int(2.2 * L)
+        starts[1:2 * half:2] = np.minimum(starts[0:2 * half:2] + gap, span[1:2 * half:2] - 1)
+        strand[0:2 * half:2] = False
+        strand[1:2 * half:2] = True
+    if spec.get("dup_rate", 0) > 0:
+        dup = np.nonzero(rng.random(n) < spec["dup_rate"])[0]
+        src = rng.integers(0, n, size=len(dup))
+        starts[dup] = np.minimum(starts[src], span[dup] - 1)
+        strand[dup] = strand[src]
+    if order == "sorted":
+        o = np.argsort(starts, kind="stable")
+        starts, strand, lens = starts[o], strand[o], lens[o]
+    return lens, starts, strand
+
+
+@functools.lru_cache(maxsize=2)
+def _window_placed(spec_json):
+    """genome and placement of a spec (as JSON): the read ranges of one file, asked for one by one, share them"""
+    spec = json.loads(spec_json)
+    genome = window_genome(spec["genome"])
+    placed = (genome,) + window_placement(spec, len(genome))
+    for a in placed:
+        a.setflags(write=False)
+    return placed
+
+
+def _window_chunk(spec, genome, lens, starts, strand, c, out, at):
+    """the bases of chunk c (reads [c * WINDOW_CHUNK, ...)) into out[at:]"""
+    a, b = c * WINDOW_CHUNK, min(len(lens), (c + 1) * WINDOW_CHUNK)
+    G = len(genome)
+    w = at
+    for s in range(a, b, 8192):                                   # the 2-D gather in slices: a few MB of indices at a time
+        e = min(b, s + 8192)
+        ln, rv = lens[s:e, None], strand[s:e]
+        j = np.arange(int(ln.max()), dtype=np.int32)[None, :]
+        # a reverse read walks its span backwards from its last base
+        first = np.where(rv, starts[s:e] + lens[s:e] - 1, starts[s:e]).astype(np.int32)[:, None]
+        idx = first + np.where(rv, -1, 1).astype(np.int32)[:, None] * j
+        if spec.get("ragged"):
+            np.clip(idx, 0, G - 1, out=idx)                       # (past a short read's end: cut away below)
+        seg = genome[idx]
+        seg[rv] = _COMP[seg[rv]]
+        seg = seg[j < ln] if spec.get("ragged") else seg.reshape(-1)
+        out[w:w + len(seg)] = seg
+        w += len(seg)
+    err, n_rate = float(spec.get("err", 0)), float(spec.get("n_rate", 0))
+    if err > 0 or n_rate > 0:
+        # one float32 uniform per base: below err a substitution (which of the three other bases: where in [0, err) it lies), from err to
+        # err + n_rate an N
+        u = np.random.default_rng([spec["seed"], c]).random(w - at, dtype=np.float32)
+        seg = out[at:w]
+        if err > 0:
+            m = np.nonzero(u < err)[0]
+            seg[m] = _SUB[seg[m], np.minimum((u[m] * np.float32(3.0 / err)).astype(np.int64), 2)]
+        seg[(u >= err) & (u < err + n_rate)] = ord("N")
+
+
+def window_reads(spec, r0=0, r1=None, threads=None):
+    """reads [r0, r1) of the file `spec` describes: (bases uint8[total], offsets uint64[r1 - r0 + 1], offsets[0] = 0).
+    spec: {"genome": {...} (window_genome), "n_reads", "read_len", "seed", "ragged", "order": "random" | "sorted" | "pairs", "err",
+    "n_rate", "dup_rate", "skew"}; "pairs" interleaves mates (forward read at p, reverse read ~2.2 read lengths downstream)."""
+    n = spec["n_reads"]
+    r1 = n if r1 is None else r1
+    assert 0 <= r0 <= r1 <= n
+    genome, lens, starts, strand = _window_placed(json.dumps(spec, sort_keys=True))
+    assert len(genome) < 1 << 31                                    # (int32 indices)
+    c0, c1 = r0 // WINDOW_CHUNK, (r1 + WINDOW_CHUNK - 1) // WINDOW_CHUNK
+    a, b = c0 * WINDOW_CHUNK, min(n, c1 * WINDOW_CHUNK)             # whole chunks, cut to [r0, r1) at the end
+    off = np.zeros(b - a + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(lens[a:b])
+    out = np.empty(int(off[-1]), dtype=np.uint8)
+    if threads is None:
+        threads = min(16, int(os.environ.get("OMP_NUM_THREADS") or 16))
+    threads = max(1, min(threads, c1 - c0))
+    jobs = [(c, int(off[c * WINDOW_CHUNK - a])) for c in range(c0, c1)]
+    if threads == 1:
+        for c, at in jobs:
+            _window_chunk(spec, genome, lens, starts, strand, c, out, at)
+    else:
+        with ThreadPoolExecutor(threads) as ex:
+            list(ex.map(lambda j: _window_chunk(spec, genome, lens, starts, strand, j[0], out, j[1]), jobs))
+    o0, o1 = int(off[r0 - a]), int(off[r1 - a])
+    return out[o0:o1], (off[r0 - a:r1 - a + 1] - off[r0 - a]).astype(np.uint64)
