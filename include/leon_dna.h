@@ -262,6 +262,34 @@ int leon_header_text_from_symbols(const leon_header_symbols* set, uint64_t first
                                   const uint8_t* first_header, uint64_t first_header_len, uint8_t* out, uint64_t out_cap, uint64_t* out_off,
                                   uint64_t* out_size, uint32_t n_threads);
 void leon_header_symbols_free(leon_header_symbols* set);
+/* The header TEXT on the device as well (k_hdr_text, one wave per block: the device form of the host's text builder): same arguments,
+ * results and errors as leon_header_decode_blocks, but the text comes back from the device as it is.  A block the kernel declines
+ * -- a header longer than 4096 bytes, or more symbols than the block's share of the device buffer -- is decoded by the host
+ * decoder from its payload on n_threads threads; *n_blocks_on_host (may be NULL) counts those blocks. */
+int leon_header_decode_blocks_device(leon_dna_ctx* ctx, const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads,
+                                     uint64_t n_blocks, const uint8_t* first_header, uint64_t first_header_len, uint8_t* out,
+                                     uint64_t out_cap, uint64_t* out_off, uint64_t* out_size, uint32_t n_threads,
+                                     uint64_t* n_blocks_on_host);
+/* ... and its two halves, for callers that decode a file in rounds (as leon_header_decode_symbols / leon_header_text_from_symbols).
+ * leon_header_decode_text: the symbols and the text of ALL header blocks in one device call (both kernels on the context's stream); the
+ * text and one offset per header STAY IN DEVICE MEMORY until leon_header_text_free -- the text + 8 bytes per header, about 7 GB for
+ * 100 M SRA-style headers --, the symbol buffer is released before the call returns.  block_text_bytes: every block's text size where
+ * the caller knows it (the container's header table), or NULL: a sizing pass of the kernel counts them first.  A payload that does not
+ * decode gives LEON_E_INVALID.  The set belongs to the context's device; free it before the context is destroyed.
+ * leon_header_text_fetch: blocks [first_block, first_block + n_blocks) of the set to the host, outputs and LEON_E_OVERFLOW as
+ * leon_host_header_decode_blocks; LEON_E_STATE when the kernel declined a block of the run (see above, or a block_text_bytes entry
+ * that is not the block's size): the caller then decodes the run's payloads with leon_host_header_decode_blocks.
+ * leon_header_text_device_ptr: the same run where it lies: *d_text its first byte, d_off[0 .. reads of the run] the headers' bounds
+ * counted from the SET's first byte (d_off[i] - d_off[0] is header i's offset in the run), *size its bytes; same errors. */
+typedef struct leon_header_text leon_header_text;
+int leon_header_decode_text(leon_dna_ctx* ctx, const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads,
+                            const uint64_t* block_text_bytes, uint64_t n_blocks, const uint8_t* first_header, uint64_t first_header_len,
+                            leon_header_text** set);
+int leon_header_text_fetch(const leon_header_text* set, uint64_t first_block, uint64_t n_blocks, uint8_t* out, uint64_t out_cap,
+                           uint64_t* out_off, uint64_t* out_size);
+int leon_header_text_device_ptr(const leon_header_text* set, uint64_t first_block, uint64_t n_blocks, const uint8_t** d_text,
+                                const uint64_t** d_off, uint64_t* size);
+void leon_header_text_free(leon_header_text* set);
 /* Quality stream, lossy form (Leon's default, /root/reference/README.md:55): DnaEncoder::storeSolidCoverageInfo + smoothQuals
  * [RECALLED]: a quality becomes '@' where at least two of the read's solid k-mers (in the bloom of ctx) span the position, or
  * where it is above '@'; reads shorter than k are left alone.  quals: one byte per base, same offsets as the bases, rewritten

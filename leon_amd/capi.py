@@ -7,6 +7,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 ABI_VERSION = 5          # include/leon_dna.h LEON_DNA_ABI_VERSION this binding (Stats, _EXPORTS) was written for
+HEADER_TEXT_DEVICE_CAP = 4096   # the longest header k_hdr_text builds on the device (kernels.h LEON_HT_HEADER_CAP); longer ones go to the host decoder
 LEON_F_KEEP_TRACE = 1
 LEON_F_DICT_ON_DEVICE = 2
 
@@ -80,6 +81,12 @@ _EXPORTS = {
     "leon_header_decode_symbols": (C.c_int, [C.c_void_p, _u8p, _u64p, _u32p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "leon_header_text_from_symbols": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, _u32p, C.c_char_p, C.c_uint64, _u8p, C.c_uint64, _u64p, _u64p, C.c_uint32]),
     "leon_header_symbols_free": (None, [C.c_void_p]),
+    "leon_header_decode_blocks_device": (C.c_int, [C.c_void_p, _u8p, _u64p, _u32p, C.c_uint64, C.c_char_p, C.c_uint64, _u8p, C.c_uint64, _u64p, _u64p,
+                                                    C.c_uint32, _u64p]),
+    "leon_header_decode_text": (C.c_int, [C.c_void_p, _u8p, _u64p, _u32p, _u64p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "leon_header_text_fetch": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, _u8p, C.c_uint64, _u64p, _u64p]),
+    "leon_header_text_device_ptr": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _u64p]),
+    "leon_header_text_free": (None, [C.c_void_p]),
     "leon_dna_set_shard": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "leon_dna_set_exchange": (C.c_int, [C.c_void_p, C.c_uint32, EXCHANGE, C.c_void_p]),
     "leon_dna_set_gather": (C.c_int, [C.c_void_p, GATHER, C.c_void_p]),
@@ -525,6 +532,70 @@ class DnaEncodeContext:
 
             def close(self):
                 ctx.lib.leon_header_symbols_free(h)
+        return Set()
+
+    def header_decode_blocks_device(self, blocks, first_header, n_threads=0):
+        """HeaderDecoder with the symbols AND the text on the device (k_hdr_text): blocks = [(id, payload, n_reads)] ->
+        (list of header bytes, number of blocks the kernel declined and the host decoder took on n_threads threads)"""
+        if not blocks:
+            return [], 0
+        pay, off, nr = _join_blocks(blocks)
+        total = int(nr[:len(blocks)].sum())
+        out_off = np.zeros(total + 1, dtype=np.uint64)
+        need, on_host = C.c_uint64(), C.c_uint64()
+        cap = max(64, 64 * total)
+        for _ in range(2):
+            out = np.zeros(cap, dtype=np.uint8)
+            rc = self.lib.leon_header_decode_blocks_device(self.h, _ptr(pay, _u8p), _ptr(off, _u64p), _ptr(nr, _u32p), len(blocks), first_header,
+                                                           len(first_header), _ptr(out, _u8p), cap, _ptr(out_off, _u64p), C.byref(need), n_threads,
+                                                           C.byref(on_host))
+            if rc != -5:
+                break
+            cap = need.value
+        self._chk(rc)
+        raw = out.tobytes()
+        return [raw[int(out_off[i]):int(out_off[i + 1])] for i in range(total)], int(on_host.value)
+
+    def header_text_set(self, blocks, first_header, text_bytes=None):
+        """both device halves of header_decode_blocks_device over ALL of `blocks` in one call; the text stays in device memory.
+        text_bytes: every block's text size where known (a container's block table), else the kernel sizes them first.  Returns an object
+        whose .fetch(first_block, n_blocks) gives those blocks' headers, .device_ptr(first_block, n_blocks) -> (d_text, d_off, size), and
+        .close() frees the set (before the context is closed)"""
+        ctx = self
+        pay, off, nr = _join_blocks(blocks)
+        tb = None if text_bytes is None else np.ascontiguousarray(list(text_bytes) or [0], dtype=np.uint64)
+        if tb is not None and len(text_bytes) != len(blocks):
+            raise ValueError("text_bytes: one entry per block")
+        h = C.c_void_p()
+        self._chk(self.lib.leon_header_decode_text(self.h, _ptr(pay, _u8p), _ptr(off, _u64p), _ptr(nr, _u32p), None if tb is None else _ptr(tb, _u64p),
+                                                   len(blocks), first_header, len(first_header), C.byref(h)))
+
+        class Set:
+            def fetch(self, first_block, n_blocks):
+                total = int(nr[first_block:first_block + n_blocks].sum()) if first_block + n_blocks <= len(blocks) else 0
+                out_off = np.zeros(total + 1, dtype=np.uint64)
+                need = C.c_uint64()
+                cap = max(64, 64 * total)
+                for _ in range(2):
+                    out = np.zeros(cap, dtype=np.uint8)
+                    rc = ctx.lib.leon_header_text_fetch(h, first_block, n_blocks, _ptr(out, _u8p), cap, _ptr(out_off, _u64p), C.byref(need))
+                    if rc != -5:
+                        break
+                    cap = need.value
+                if rc:
+                    raise LeonDnaError(rc, (ctx.lib.leon_last_error(None) or b"").decode())
+                raw = out.tobytes()
+                return [raw[int(out_off[i]):int(out_off[i + 1])] for i in range(total)]
+
+            def device_ptr(self, first_block, n_blocks):
+                d_text, d_off, size = C.c_void_p(), C.c_void_p(), C.c_uint64()
+                rc = ctx.lib.leon_header_text_device_ptr(h, first_block, n_blocks, C.byref(d_text), C.byref(d_off), C.byref(size))
+                if rc:
+                    raise LeonDnaError(rc, (ctx.lib.leon_last_error(None) or b"").decode())
+                return d_text.value, d_off.value, int(size.value)
+
+            def close(self):
+                ctx.lib.leon_header_text_free(h)
         return Set()
 
     def qual_smooth_batch(self, bases, offsets, quals):

@@ -1915,6 +1915,49 @@ struct leon_header_symbols {
     bool overflowed = false;                                     // some block had more symbols than its share of the device buffer: decode the payloads on the host
 };
 
+// The front that the header decoders share: the payloads to the device, every block's share of the symbol buffer, the symbol
+// kernel on the context's stream (not waited for), and -- hdr_symbols_wait -- its verdict.
+struct HdrSymbolsDev {
+    TmpBuf pay, off, nreads, begin, count, syms, err;
+    std::vector<uint64_t> sym_begin, rel_off;                    // block b's share: syms[sym_begin[b] .. sym_begin[b + 1]); its payload's place
+};
+static int hdr_symbols_launch(leon_dna_ctx* c, const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads, uint64_t n_blocks, HdrSymbolsDev& D) {
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    // a block's share of the symbol buffer: enough for the headers sequencers write (a dozen symbols each); a block that
+    // needs more (free text in every header) is left to the host decoder -- same result, its speed
+    std::vector<uint64_t>& rel_off = D.rel_off;
+    rel_off.assign(n_blocks + 1, 0);
+    D.sym_begin.assign(n_blocks + 1, 0);
+    for (uint64_t b = 0; b < n_blocks; b++) {
+        if (payload_off[b + 1] < payload_off[b]) return fail(c, LEON_E_INVALID, "payload offsets are not monotonic");
+        D.sym_begin[b + 1] = D.sym_begin[b] + 24ull * block_n_reads[b] + 6 * (payload_off[b + 1] - payload_off[b]) + 256;   // (SRA-style headers: 12-17 symbols, ~6 bytes each)
+    }
+    for (uint64_t b = 0; b <= n_blocks; b++) rel_off[b] = payload_off[b] - payload_off[0];
+    const uint64_t pay_bytes = rel_off[n_blocks], sym_cap = D.sym_begin[n_blocks];
+    HIPCHK(c, D.pay.ensure(pay_bytes + 1024));                  // (the payload window reads up to 256 + 3 bytes past a block's end)
+    HIPCHK(c, D.off.ensure((n_blocks + 1) * 8)); HIPCHK(c, D.nreads.ensure(n_blocks * 4));
+    HIPCHK(c, D.begin.ensure((n_blocks + 1) * 8)); HIPCHK(c, D.count.ensure(n_blocks * 8));
+    HIPCHK(c, D.syms.ensure(sym_cap + 64)); HIPCHK(c, D.err.ensure(16));
+    HIPCHK(c, staged_h2d(c->device, D.pay.p, payloads + payload_off[0], pay_bytes));
+    HIPCHK(c, hipMemsetAsync((uint8_t*)D.pay.p + pay_bytes, 0, 1024, s));
+    HIPCHK(c, hipMemcpyAsync(D.off.p, rel_off.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(D.nreads.p, block_n_reads, n_blocks * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(D.begin.p, D.sym_begin.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(D.err.p, 0, 16, s));
+    launch_hdr_decode_symbols(s, D.pay.as<uint8_t>(), D.off.as<uint64_t>(), D.nreads.as<uint32_t>(), n_blocks, D.syms.as<uint8_t>(),
+                              D.begin.as<uint64_t>(), (unsigned long long*)D.count.p, D.err.as<int>());
+    HIPCHK(c, hipGetLastError());
+    return LEON_OK;
+}
+// err[0]: 0, 1 some block's symbols did not fit its share, 2 block err[1] is not a header stream
+static int hdr_symbols_wait(leon_dna_ctx* c, HdrSymbolsDev& D, int err[2]) {
+    err[0] = err[1] = 0;
+    HIPCHK(c, hipMemcpyAsync(err, D.err.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LEON_OK;
+}
+
 int leon_header_decode_symbols(leon_dna_ctx* c, const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads, uint64_t n_blocks,
                                leon_header_symbols** set) {
     if (!c) return LEON_E_INVALID;
@@ -1923,42 +1966,19 @@ int leon_header_decode_symbols(leon_dna_ctx* c, const uint8_t* payloads, const u
     std::unique_ptr<leon_header_symbols> H(new leon_header_symbols());
     H->begin.assign(n_blocks + 1, 0); H->count.assign(n_blocks, 0);
     if (!n_blocks) { *set = H.release(); return LEON_OK; }
-    HIPCHK(c, hipSetDevice(c->device));
+    HdrSymbolsDev D;
+    if (int rc = hdr_symbols_launch(c, payloads, payload_off, block_n_reads, n_blocks, D)) return rc;
     hipStream_t s = c->stream;
-    // a block's share of the symbol buffer: enough for the headers sequencers write (a dozen symbols each); a block that
-    // needs more (free text in every header) marks the whole set for the host decoder -- same result, its speed
-    std::vector<uint64_t> rel_off(n_blocks + 1), sym_begin(n_blocks + 1, 0);
-    for (uint64_t b = 0; b < n_blocks; b++) {
-        if (payload_off[b + 1] < payload_off[b]) return fail(c, LEON_E_INVALID, "payload offsets are not monotonic");
-        sym_begin[b + 1] = sym_begin[b] + 24ull * block_n_reads[b] + 6 * (payload_off[b + 1] - payload_off[b]) + 256;   // (SRA-style headers: 12-17 symbols, ~6 bytes each)
-    }
-    for (uint64_t b = 0; b <= n_blocks; b++) rel_off[b] = payload_off[b] - payload_off[0];
-    const uint64_t pay_bytes = rel_off[n_blocks], sym_cap = sym_begin[n_blocks];
-    TmpBuf d_pay, d_off, d_nreads, d_begin, d_count, d_syms, d_err;
-    HIPCHK(c, d_pay.ensure(pay_bytes + 1024));                  // (the payload window reads up to 256 + 3 bytes past a block's end)
-    HIPCHK(c, d_off.ensure((n_blocks + 1) * 8)); HIPCHK(c, d_nreads.ensure(n_blocks * 4));
-    HIPCHK(c, d_begin.ensure((n_blocks + 1) * 8)); HIPCHK(c, d_count.ensure(n_blocks * 8));
-    HIPCHK(c, d_syms.ensure(sym_cap + 64)); HIPCHK(c, d_err.ensure(16));
-    HIPCHK(c, staged_h2d(c->device, d_pay.p, payloads + payload_off[0], pay_bytes));
-    HIPCHK(c, hipMemsetAsync((uint8_t*)d_pay.p + pay_bytes, 0, 1024, s));
-    HIPCHK(c, hipMemcpyAsync(d_off.p, rel_off.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_nreads.p, block_n_reads, n_blocks * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_begin.p, sym_begin.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemsetAsync(d_err.p, 0, 16, s));
-    launch_hdr_decode_symbols(s, d_pay.as<uint8_t>(), d_off.as<uint64_t>(), d_nreads.as<uint32_t>(), n_blocks, d_syms.as<uint8_t>(),
-                              d_begin.as<uint64_t>(), (unsigned long long*)d_count.p, d_err.as<int>());
-    HIPCHK(c, hipGetLastError());
-    int err[2] = {0, 0};
-    HIPCHK(c, hipMemcpyAsync(err, d_err.p, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
+    int err[2];
+    if (int rc = hdr_symbols_wait(c, D, err)) return rc;
     if (err[0] == 2) return fail(c, LEON_E_INVALID, "header block " + std::to_string(err[1]) + " does not decode");
     if (err[0] == 1) { H->overflowed = true; *set = H.release(); return LEON_OK; }
-    HIPCHK(c, hipMemcpy(H->count.data(), d_count.p, n_blocks * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(H->count.data(), D.count.p, n_blocks * 8, hipMemcpyDeviceToHost));
     // only the symbols that were written come back (a block's share is mostly empty)
     for (uint64_t b = 0; b < n_blocks; b++) H->begin[b + 1] = H->begin[b] + H->count[b];
     H->syms.reset(new uint8_t[H->begin[n_blocks] + 1]);
     for (uint64_t b = 0; b < n_blocks; b++)
-        if (H->count[b]) HIPCHK(c, hipMemcpyAsync(H->syms.get() + H->begin[b], d_syms.as<uint8_t>() + sym_begin[b], H->count[b], hipMemcpyDeviceToHost, s));
+        if (H->count[b]) HIPCHK(c, hipMemcpyAsync(H->syms.get() + H->begin[b], D.syms.as<uint8_t>() + D.sym_begin[b], H->count[b], hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     *set = H.release();
     return LEON_OK;
@@ -1996,6 +2016,171 @@ int leon_header_decode_blocks(leon_dna_ctx* c, const uint8_t* payloads, const ui
         rc = leon_header_text_from_symbols(H, 0, n_blocks, block_n_reads, first_header, first_header_len, out, out_cap, out_off, out_size, n_threads);
     if (rc != LEON_OK) c->err = leon_last_error(nullptr);
     return rc;
+}
+
+// Header blocks, the text on the device too (k_hdr_text): what a set keeps, all of it in device memory
+struct leon_header_text {
+    int device = 0;
+    DevBuf text, off;                                            // every block's headers back to back; off[reads + 1], counted from text's first byte
+    std::vector<uint64_t> text_begin, read0;                     // block b: text[text_begin[b] .. text_begin[b + 1]), off[read0[b] .. read0[b + 1]]
+    std::vector<uint32_t> status;                                // HT_OK, or why the kernel declined the block (kernels.h)
+    ~leon_header_text() { if (text.p || off.p) { (void)hipSetDevice(device); text.release(); off.release(); } }
+};
+
+int leon_header_decode_text(leon_dna_ctx* c, const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads,
+                            const uint64_t* block_text_bytes, uint64_t n_blocks, const uint8_t* first_header, uint64_t first_header_len,
+                            leon_header_text** set) {
+    if (!c) return LEON_E_INVALID;
+    if (!set || (n_blocks && (!payloads || !payload_off || !block_n_reads)) || (!first_header && first_header_len)) return fail(c, LEON_E_INVALID, "null argument");
+    *set = nullptr;
+    std::unique_ptr<leon_header_text> T(new leon_header_text());
+    T->device = c->device;
+    T->text_begin.assign(n_blocks + 1, 0); T->read0.assign(n_blocks + 1, 0); T->status.assign(n_blocks, 0);
+    if (!n_blocks) { *set = T.release(); return LEON_OK; }
+    HdrSymbolsDev D;
+    if (int rc = hdr_symbols_launch(c, payloads, payload_off, block_n_reads, n_blocks, D)) return rc;
+    hipStream_t s = c->stream;
+    for (uint64_t b = 0; b < n_blocks; b++) T->read0[b + 1] = T->read0[b] + block_n_reads[b];
+    const uint64_t n_reads = T->read0[n_blocks];
+    // a first header beyond the kernel's cap is not uploaded: every block is declined by its length alone
+    const uint32_t first_len = (uint32_t)std::min<uint64_t>(first_header_len, (uint64_t)LEON_HT_HEADER_CAP + 1);
+    TmpBuf d_first, d_read0, d_tbegin, d_status, d_tsize;
+    HIPCHK(c, d_first.ensure(first_len + 64)); HIPCHK(c, d_read0.ensure((n_blocks + 1) * 8)); HIPCHK(c, d_tbegin.ensure((n_blocks + 1) * 8));
+    HIPCHK(c, d_status.ensure(n_blocks * 4)); HIPCHK(c, d_tsize.ensure(n_blocks * 8));
+    if (first_len) HIPCHK(c, hipMemcpyAsync(d_first.p, first_header, first_len, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_read0.p, T->read0.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, s));
+    auto text_kernel = [&](uint8_t* text, uint64_t* off) {
+        launch_hdr_text(s, D.syms.as<uint8_t>(), D.begin.as<uint64_t>(), (const unsigned long long*)D.count.p, D.nreads.as<uint32_t>(), d_read0.as<uint64_t>(),
+                        d_tbegin.as<uint64_t>(), n_blocks, d_first.as<uint8_t>(), first_len, text, off, d_status.as<uint32_t>(), d_tsize.as<uint64_t>());
+    };
+    std::vector<uint64_t> sizes;
+    if (!block_text_bytes) {                                     // the sizing pass: the same chains, nothing written but the counts
+        text_kernel(nullptr, nullptr);
+        HIPCHK(c, hipGetLastError());
+        sizes.resize(n_blocks);
+        HIPCHK(c, hipMemcpyAsync(sizes.data(), d_tsize.p, n_blocks * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        block_text_bytes = sizes.data();
+    }
+    for (uint64_t b = 0; b < n_blocks; b++) {
+        if (block_text_bytes[b] > (1ull << 48)) return fail(c, LEON_E_INVALID, "header block " + std::to_string(b) + ": text size out of range");
+        T->text_begin[b + 1] = T->text_begin[b] + block_text_bytes[b];
+    }
+    HIPCHK(c, T->text.ensure(T->text_begin[n_blocks] + 64)); HIPCHK(c, T->off.ensure((n_reads + 1) * 8));
+    HIPCHK(c, hipMemcpyAsync(d_tbegin.p, T->text_begin.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(T->off.p, 0, 8, s));
+    text_kernel(T->text.as<uint8_t>(), T->off.as<uint64_t>());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(T->status.data(), d_status.p, n_blocks * 4, hipMemcpyDeviceToHost, s));
+    int err[2];
+    if (int rc = hdr_symbols_wait(c, D, err)) return rc;
+    if (err[0] == 2) return fail(c, LEON_E_INVALID, "header block " + std::to_string(err[1]) + " does not decode");
+    for (uint64_t b = 0; b < n_blocks; b++)
+        if (T->status[b] >= HT_INVALID) return fail(c, LEON_E_INVALID, "header block " + std::to_string(b) + " does not decode");
+    *set = T.release();
+    return LEON_OK;
+}
+
+// blocks [b0, b0 + nb) of the set into out / out_off, the offsets counted from `at` (the run's first byte in the caller's text)
+static int header_text_copy(const leon_header_text* T, uint64_t b0, uint64_t nb, uint8_t* out, uint64_t* out_off, uint64_t at) {
+    const uint64_t t0 = T->text_begin[b0], size = T->text_begin[b0 + nb] - t0, r0 = T->read0[b0], nr = T->read0[b0 + nb] - r0;
+    if (hipSetDevice(T->device) != hipSuccess) return fail(nullptr, LEON_E_HIP, "hipSetDevice");
+    if (staged_d2h(T->device, out, T->text.as<uint8_t>() + t0, size) != hipSuccess) return fail(nullptr, LEON_E_HIP, "header text: copy to the host failed");
+    if (staged_d2h(T->device, out_off, T->off.as<uint64_t>() + r0, (nr + 1) * 8) != hipSuccess) return fail(nullptr, LEON_E_HIP, "header offsets: copy to the host failed");
+    if (at != t0) for (uint64_t i = 0; i <= nr; i++) out_off[i] = out_off[i] - t0 + at;
+    return LEON_OK;
+}
+static int header_text_run(const leon_header_text* T, uint64_t first_block, uint64_t n_blocks) {
+    if (first_block > T->status.size() || n_blocks > T->status.size() - first_block) return fail(nullptr, LEON_E_INVALID, "blocks beyond the text set");
+    for (uint64_t b = first_block; b < first_block + n_blocks; b++)
+        if (T->status[b]) return fail(nullptr, LEON_E_STATE, "header block " + std::to_string(b) + " was not built on the device (reason " + std::to_string(T->status[b]) +
+                                      "): decode the payloads with leon_host_header_decode_blocks");
+    return LEON_OK;
+}
+
+int leon_header_text_fetch(const leon_header_text* T, uint64_t first_block, uint64_t n_blocks, uint8_t* out, uint64_t out_cap, uint64_t* out_off, uint64_t* out_size) {
+    if (!T || !out_size || (n_blocks && !out_off)) return fail(nullptr, LEON_E_INVALID, "null argument");
+    *out_size = 0;
+    if (int rc = header_text_run(T, first_block, n_blocks)) return rc;
+    if (!n_blocks) return LEON_OK;
+    const uint64_t size = T->text_begin[first_block + n_blocks] - T->text_begin[first_block];
+    *out_size = size;
+    if (size > out_cap || !out) return fail(nullptr, LEON_E_OVERFLOW, "header output needs " + std::to_string(size) + " bytes");
+    return header_text_copy(T, first_block, n_blocks, out, out_off, 0);
+}
+
+int leon_header_text_device_ptr(const leon_header_text* T, uint64_t first_block, uint64_t n_blocks, const uint8_t** d_text, const uint64_t** d_off, uint64_t* size) {
+    if (!T || !d_text || !d_off || !size) return fail(nullptr, LEON_E_INVALID, "null argument");
+    *d_text = nullptr; *d_off = nullptr; *size = 0;
+    if (int rc = header_text_run(T, first_block, n_blocks)) return rc;
+    if (!T->text.p) return LEON_OK;                              // a set of no blocks
+    *d_text = T->text.as<uint8_t>() + T->text_begin[first_block];
+    *d_off = T->off.as<uint64_t>() + T->read0[first_block];
+    *size = T->text_begin[first_block + n_blocks] - T->text_begin[first_block];
+    return LEON_OK;
+}
+
+void leon_header_text_free(leon_header_text* T) { delete T; }
+
+int leon_header_decode_blocks_device(leon_dna_ctx* c, const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads, uint64_t n_blocks,
+                                     const uint8_t* first_header, uint64_t first_header_len, uint8_t* out, uint64_t out_cap, uint64_t* out_off,
+                                     uint64_t* out_size, uint32_t n_threads, uint64_t* n_blocks_on_host) {
+    if (!c) return LEON_E_INVALID;
+    if (!out_size || (n_blocks && (!payloads || !payload_off || !block_n_reads || !out_off)) || (!first_header && first_header_len))
+        return fail(c, LEON_E_INVALID, "null argument");
+    *out_size = 0;
+    if (n_blocks_on_host) *n_blocks_on_host = 0;
+    if (!n_blocks) return LEON_OK;
+    leon_header_text* Tp = nullptr;
+    if (int rc = leon_header_decode_text(c, payloads, payload_off, block_n_reads, nullptr, n_blocks, first_header, first_header_len, &Tp)) return rc;
+    std::unique_ptr<leon_header_text> T(Tp);
+    // the blocks the kernel declined, run by run, through the host decoder from their payloads
+    struct HostRun { uint64_t b0, nb; std::vector<uint8_t> text; std::vector<uint64_t> off; uint64_t size; };
+    std::vector<HostRun> runs;
+    uint64_t on_host = 0;
+    for (uint64_t b = 0; b < n_blocks;) {
+        if (!T->status[b]) { b++; continue; }
+        HostRun R; R.b0 = b;
+        while (b < n_blocks && T->status[b]) b++;
+        R.nb = b - R.b0; on_host += R.nb;
+        R.off.assign(T->read0[R.b0 + R.nb] - T->read0[R.b0] + 1, 0);
+        R.text.resize((payload_off[R.b0 + R.nb] - payload_off[R.b0]) * 8 + 4096);
+        auto decode = [&](uint64_t b0, uint64_t nb) {
+            return leon_host_header_decode_blocks(payloads, payload_off + b0, block_n_reads + b0, nb, first_header, first_header_len, R.text.data(), R.text.size(),
+                                                  R.off.data(), &R.size, n_threads);
+        };
+        int rc = decode(R.b0, R.nb);
+        if (rc == LEON_E_OVERFLOW) { R.text.resize(R.size + 1); rc = decode(R.b0, R.nb); }
+        if (rc == LEON_E_INVALID && R.nb > 1) {                  // (the host decoder counts from the run's first block: name the block by its place in the call)
+            for (uint64_t k = 0; k < R.nb; k++)
+                if (decode(R.b0 + k, 1) == LEON_E_INVALID) return fail(c, LEON_E_INVALID, "header block " + std::to_string(R.b0 + k) + " does not decode");
+        }
+        if (rc == LEON_E_INVALID) return fail(c, LEON_E_INVALID, "header block " + std::to_string(R.b0) + " does not decode");
+        if (rc != LEON_OK) { c->err = leon_last_error(nullptr); return rc; }
+        runs.push_back(std::move(R));
+    }
+    if (n_blocks_on_host) *n_blocks_on_host = on_host;
+    uint64_t total = T->text_begin[n_blocks];
+    for (const HostRun& R : runs) total += R.size;
+    *out_size = total;
+    if (total > out_cap || !out) return fail(c, LEON_E_OVERFLOW, "header output needs " + std::to_string(total) + " bytes");
+    uint64_t at = 0, b = 0;
+    size_t next_run = 0;
+    out_off[0] = 0;
+    while (b < n_blocks) {
+        uint64_t* o = out_off + T->read0[b];
+        if (next_run < runs.size() && runs[next_run].b0 == b) {
+            const HostRun& R = runs[next_run++];
+            if (R.size) memcpy(out + at, R.text.data(), R.size);
+            for (size_t i = 0; i < R.off.size(); i++) o[i] = at + R.off[i];
+            at += R.size; b += R.nb;
+        } else {
+            const uint64_t e = next_run < runs.size() ? runs[next_run].b0 : n_blocks;
+            if (int rc = header_text_copy(T.get(), b, e - b, out + at, o, at)) { c->err = leon_last_error(nullptr); return rc; }
+            at += T->text_begin[e] - T->text_begin[b]; b = e;
+        }
+    }
+    return LEON_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ traces

@@ -714,6 +714,286 @@ void launch_hdr_decode_symbols(hipStream_t s, const uint8_t* payloads, const uin
     hipLaunchKernelGGL(k_hdr_decode_symbols, dim3(g), dim3(64), 0, s, payloads, pay_off, blk_reads, n_blocks, syms, sym_begin, sym_count, err);
 }
 
+
+// ---- header blocks: the TEXT from the symbols, on the device too --------------------------------------------------------
+// The device form of host_streams.cpp's decode_header_block<SymbolSource>, record for record.  A block is a serial chain --
+// header r is built from header r - 1, every block starts from the file's first header -- so again one wave per block, all
+// blocks at once.  Everything that steers the wave (the symbols, positions, lengths) is the same in all its lanes; the lanes
+// share the BYTES: the previous and the current header live in LDS, a lane per byte.
+//   * Where the previous header's fields begin is one __ballot of "is not [0-9A-Za-z]" per 64 bytes (sepmask): field i starts
+//     after the i-th set bit, so "fields nf .. idx - 1 of the previous header" is one byte range, copied LDS to LDS.
+//   * A number is parsed and printed by its digits' lanes (digit x 10^place summed over the wave; v / 10^place % 10 per lane).
+//   * Text leaves LDS through a staging image whose index is congruent to the global offset mod 16: whole-wave dwordx4 stores
+//     of 1 KiB of consecutive bytes, byte stores only for a block's unaligned first and last bytes (they border other blocks'
+//     shares); the headers' end offsets leave 64 at a time.
+// Every LDS and global write is bounded by HT_CAP and the block's share of `text`; a block that does not fit is DECLINED
+// (status 1..4: the caller decodes it on the host from its payload), symbols that are not a record sequence give HT_INVALID.
+namespace {
+constexpr uint32_t HT_CAP = LEON_HT_HEADER_CAP;               // longest header built here (bytes)
+constexpr uint32_t HT_FLUSH = 1024;                           // staged bytes that leave in one wave-wide dwordx4 store
+constexpr uint32_t HT_STAGE = HT_FLUSH + 16 + HT_CAP;         // (a flush leaves < 16 bytes behind, one header is appended at a time)
+constexpr uint32_t HT_WIN = 256;                              // symbols in LDS at a time
+
+struct HText {
+    const uint8_t* syms; uint64_t n, i, wbase;                // the block's symbols, the next one, the window's first
+    uint8_t* win;
+    uint32_t lane;
+    bool over;                                                // asked for a symbol beyond the last
+};
+__device__ inline void ht_refill(HText& h) {
+    __syncthreads();
+    h.wbase = h.i;
+    for (uint32_t k = h.lane; k < HT_WIN; k += 64) h.win[k] = h.wbase + k < h.n ? h.syms[h.wbase + k] : (uint8_t)0;
+    __syncthreads();
+}
+__device__ inline uint32_t ht_sym(HText& h) {
+    if (h.i >= h.n) { h.over = true; return 0; }
+    if (h.i - h.wbase >= HT_WIN) ht_refill(h);
+    const uint32_t c = h.win[(uint32_t)(h.i - h.wbase)];
+    h.i++;
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
+}
+__device__ inline uint64_t ht_numeric(HText& h) {
+    uint32_t bc = ht_sym(h);
+    if (bc > 8) bc = 8;
+    uint64_t v = 0;
+#pragma unroll 1
+    for (uint32_t i = 0; i < bc; i++) v |= (uint64_t)ht_sym(h) << (8 * i);
+    return v;
+}
+__device__ inline uint64_t ht_count(HText& h) {
+    const uint64_t x = ht_sym(h);
+    return x < 255 ? x : 255 + ht_numeric(h);
+}
+__device__ inline uint64_t ht_uniform64(uint64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ inline bool ht_alnum(uint32_t c) { return (c - '0') < 10u || ((c | 32u) - 'a') < 26u; }
+// the position after the want-th separator at or after pp (found = true), or lp when the header has fewer (found = false,
+// n_seps = how many there were); pp < lp, want >= 1; mask bits at and beyond lp are 0
+__device__ inline uint32_t ht_after_seps(const uint64_t* mask, uint32_t lp, uint32_t pp, uint64_t want, uint32_t lane, bool& found, uint32_t& n_seps) {
+    const uint32_t nw = (lp + 63) >> 6;
+    uint32_t wi = pp >> 6, cnt = 0;
+    uint64_t word = mask[wi] & (~0ull << (pp & 63));
+    for (;;) {
+        const uint32_t c = (uint32_t)__popcll(word);
+        if ((uint64_t)cnt + c >= want) {
+            const uint32_t k = (uint32_t)(want - cnt);            // the k-th set bit of word, 1 <= k <= c: the lane whose bit it is says so
+            const bool mine = ((word >> lane) & 1ull) && (uint32_t)__popcll(word & ((1ull << lane) - 1)) == k - 1;
+            const uint32_t bit = (uint32_t)__builtin_ctzll(__ballot(mine));
+            found = true; n_seps = (uint32_t)want;
+            return wi * 64 + bit + 1;
+        }
+        cnt += c;
+        if (++wi >= nw) break;
+        word = mask[wi];
+    }
+    found = false; n_seps = cnt;
+    return lp;
+}
+__device__ inline void ht_copy(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t lane) {
+    for (uint32_t k = lane; k < n; k += 64) dst[k] = src[k];
+}
+// n bytes of the staging image, from index s0, to text + g0: s0 and g0 are congruent mod 16, the image is 16-byte aligned
+__device__ inline void ht_store(uint8_t* text, uint64_t g0, const uint8_t* stage, uint32_t s0, uint32_t n, uint32_t lane) {
+    uint32_t head = (16u - (s0 & 15u)) & 15u;
+    if (head > n) head = n;
+    if (lane < head) text[g0 + lane] = stage[s0 + lane];
+    const uint32_t body = (n - head) & ~15u;
+    for (uint32_t k = lane * 16; k < body; k += 64 * 16)
+        *reinterpret_cast<uint4*>(text + g0 + head + k) = *reinterpret_cast<const uint4*>(stage + s0 + head + k);
+    const uint32_t tail = n - head - body;                    // < 16
+    if (lane < tail) text[g0 + head + body + lane] = stage[s0 + head + body + lane];
+}
+}  // namespace
+
+// status[b]: 0 built; HT_LONG a header longer than HT_CAP; HT_SHARE the text is not exactly the block's share
+// text_begin[b] .. text_begin[b + 1]; HT_SYMS the symbols ran out; HT_NOSYMS the symbol kernel had declined the block;
+// HT_INVALID not a record sequence.  text_size[b]: the bytes of a block that was built (EMIT = false: only counted).
+// off[read0[b] + r + 1] = end of header r of block b, counted from text_begin[0] (off[0] is the caller's); a block's last
+// entry is text_begin[b + 1] whether it was built or not.
+template <bool EMIT>
+__global__ void __launch_bounds__(64) k_hdr_text(const uint8_t* syms, const uint64_t* sym_begin, const unsigned long long* sym_count, const uint32_t* blk_reads,
+                                                 const uint64_t* read0, const uint64_t* text_begin, uint64_t n_blocks, const uint8_t* first, uint32_t first_len,
+                                                 uint8_t* text, uint64_t* off, uint32_t* status, uint64_t* text_size) {
+    __shared__ __align__(16) uint8_t hbuf[2][HT_CAP];         // the previous and the current header, swapping
+    __shared__ __align__(16) uint8_t stage[EMIT ? HT_STAGE : 16];
+    __shared__ uint64_t sepmask[2][HT_CAP / 64];
+    __shared__ uint64_t offbuf[EMIT ? 64 : 1];
+    __shared__ uint64_t p10[20];
+    __shared__ uint8_t win[HT_WIN];
+    const uint32_t lane = lane_id();
+    if (lane < 20) { uint64_t p = 1; for (uint32_t i = 0; i < lane; i++) p *= 10; p10[lane] = p; }
+    for (uint64_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+        __syncthreads();
+        const uint32_t n_reads = blk_reads[b];
+        HText h;
+        h.syms = syms + sym_begin[b]; h.n = sym_count[b]; h.i = 0; h.wbase = 0; h.win = win; h.lane = lane; h.over = false;
+        uint32_t fail = 0;
+        if (first_len > HT_CAP) fail = HT_LONG;
+        else if (n_reads && !h.n) fail = HT_NOSYMS;
+        const uint64_t w0 = EMIT ? text_begin[b] : 0, w_end = EMIT ? text_begin[b + 1] : ~0ull;
+        uint64_t w = w0;                                      // where the next header goes (EMIT: counted from text_begin[0])
+        uint64_t gb = w0 & ~15ull;                            // stage[i] is byte gb + i of the text
+        uint32_t fill = (uint32_t)(w0 & 15u), start = fill, n_off = 0;
+        uint32_t pi = 0, lp = 0;                              // hbuf[pi][0 .. lp) is the previous header
+        if (!fail) {
+            lp = first_len;
+            for (uint32_t k0 = 0; k0 < lp; k0 += 64) {
+                const uint32_t k = k0 + lane;
+                const uint32_t c = k < lp ? first[k] : (uint32_t)'0';
+                if (k < lp) hbuf[0][k] = (uint8_t)c;
+                const uint64_t m = __ballot(k < lp && !ht_alnum(c));
+                if (lane == 0) sepmask[0][k0 >> 6] = m;
+            }
+            ht_refill(h);                                     // the first window of symbols
+        }
+        for (uint32_t r = 0; r < n_reads && !fail; r++) {
+            const uint8_t* prev = hbuf[pi];
+            uint8_t* cur = hbuf[pi ^ 1];
+            const uint64_t* pmask = sepmask[pi];
+            uint32_t pp = 0, cl = 0;
+            uint64_t nf = 0;
+            // fields nf .. limit - 1 are the previous header's
+            auto copy_prev_until = [&](uint64_t limit) {
+                if (nf >= limit || pp >= lp) return;
+                bool found; uint32_t n_seps;
+                const uint32_t e = ht_after_seps(pmask, lp, pp, limit - nf, lane, found, n_seps);
+                if (cl + (e - pp) > HT_CAP) { fail = HT_LONG; return; }
+                ht_copy(cur + cl, prev + pp, e - pp, lane);
+                nf += found ? (uint64_t)n_seps : (uint64_t)n_seps + (((pmask[(lp - 1) >> 6] >> ((lp - 1) & 63)) & 1ull) ? 0 : 1);   // (+ a last token without separator)
+                cl += e - pp; pp = e;
+            };
+            for (;;) {                                        // one record per turn
+                const uint32_t t = ht_sym(h);
+                if (h.over) { fail = HT_SYMS; break; }
+                if (t == H_END_MATCH) { copy_prev_until(~0ull); break; }
+                if (t == H_END) {
+                    const uint64_t f = ht_count(h);
+                    if (h.over) { fail = HT_SYMS; break; }
+                    if (f < nf) { fail = HT_INVALID; break; }
+                    copy_prev_until(f);
+                    if (!fail && nf != f) fail = HT_INVALID;
+                    break;
+                }
+                if (t < H_FIELD_ASCII || t >= H_TYPE_COUNT) { fail = HT_INVALID; break; }
+                const uint64_t idx = ht_count(h);
+                if (h.over) { fail = HT_SYMS; break; }
+                if (idx < nf) { fail = HT_INVALID; break; }
+                copy_prev_until(idx);
+                if (fail) break;
+                if (nf != idx) { fail = HT_INVALID; break; }
+                // the previous header's field here: token [p0, tok_end), then one separator if the header goes on
+                const bool have_p = pp < lp;
+                const uint32_t p0 = pp;
+                uint32_t tok_end = pp, p_len = 0;
+                bool p_sep = false;
+                if (have_p) {
+                    uint32_t n_seps;
+                    const uint32_t e = ht_after_seps(pmask, lp, pp, 1, lane, p_sep, n_seps);
+                    tok_end = p_sep ? e - 1 : lp;
+                    p_len = e - pp; pp = e;
+                }
+                if (t == H_FIELD_ASCII) {
+                    const uint64_t col = ht_count(h), sz = ht_count(h);
+                    if (h.over) { fail = HT_SYMS; break; }
+                    if (col > p_len) { fail = HT_INVALID; break; }
+                    if (sz > HT_CAP || cl + (uint32_t)col + (uint32_t)sz > HT_CAP) { fail = HT_LONG; break; }    // (the host decides what a header beyond the cap is)
+                    if (sz > h.n - h.i) { fail = HT_SYMS; break; }
+                    ht_copy(cur + cl, prev + p0, (uint32_t)col, lane);
+                    cl += (uint32_t)col;
+                    for (uint32_t k = lane; k < (uint32_t)sz; k += 64) cur[cl + k] = h.syms[h.i + k];   // the mismatching bytes are symbols themselves
+                    cl += (uint32_t)sz; h.i += sz;
+                } else {
+                    uint64_t v = 0, z = 0;
+                    uint32_t sep = 0; bool has_sep = false;
+                    if (t == H_FIELD_DELTA || t == H_FIELD_DELTA_2) {
+                        const uint64_t dv = ht_numeric(h);
+                        if (h.over) { fail = HT_SYMS; break; }
+                        // numeric as field_at says: digits only, 1..18 of them, no leading zero unless it is the only digit, separator not NUL
+                        const uint32_t tok = tok_end - p0;
+                        if (!have_p || tok < 1 || tok > 18) { fail = HT_INVALID; break; }
+                        const uint32_t c = lane < tok ? prev[p0 + lane] : (uint32_t)'0';
+                        const uint32_t sepc = p_sep ? prev[tok_end] : 1u;
+                        if (__ballot(lane < tok && (c - '0') >= 10u) || (tok > 1 && __ballot(lane == 0 && c == '0')) || (p_sep && sepc == 0)) { fail = HT_INVALID; break; }
+                        uint64_t pv = lane < tok ? (uint64_t)(c - '0') * p10[tok - 1 - lane] : 0;
+                        for (int o = 16; o; o >>= 1) pv += __shfl_xor(pv, o);          // (tok <= 18: the first 32 lanes hold it all)
+                        pv = ht_uniform64(pv);
+                        v = t == H_FIELD_DELTA ? pv + dv : pv - dv;                    // may wrap: the host prints the wrapped value, so does this
+                        sep = sepc; has_sep = p_sep;
+                    } else {
+                        if (t != H_FIELD_NUMERIC) z = ht_count(h);
+                        if (t != H_FIELD_ZERO_ONLY) v = ht_numeric(h);
+                        sep = ht_sym(h); has_sep = sep != 0;
+                        if (h.over) { fail = HT_SYMS; break; }
+                    }
+                    // std::to_string(uint64_t): its length first (the header's cap), then a lane per digit
+                    const uint32_t nd = t == H_FIELD_ZERO_ONLY ? 0 : 1 + (uint32_t)__popcll(__ballot(lane >= 1 && lane < 20 && v >= p10[lane < 20 ? lane : 0]));
+                    if (z > HT_CAP || cl + (uint32_t)z + nd + (has_sep ? 1u : 0u) > HT_CAP) { fail = HT_LONG; break; }
+                    for (uint32_t k = lane; k < (uint32_t)z; k += 64) cur[cl + k] = '0';
+                    cl += (uint32_t)z;
+                    if (lane < nd) {
+                        const uint32_t dgt = (v >> 32) ? (uint32_t)((v / p10[nd - 1 - lane]) % 10) : ((uint32_t)v / (uint32_t)p10[nd - 1 - lane]) % 10u;
+                        cur[cl + lane] = (uint8_t)('0' + dgt);
+                    }
+                    cl += nd;
+                    if (has_sep) { if (lane == 0) cur[cl] = (uint8_t)sep; cl++; }
+                }
+                nf++;
+            }
+            if (fail) break;
+            // the header is complete: its separators for the next one, its bytes to the staging image, its end to the offsets
+            if (w + cl > w_end) { fail = HT_SHARE; break; }
+            __syncthreads();
+            for (uint32_t k0 = 0; k0 < cl; k0 += 64) {
+                const uint32_t k = k0 + lane;
+                const uint32_t c = k < cl ? cur[k] : (uint32_t)'0';
+                const uint64_t m = __ballot(k < cl && !ht_alnum(c));
+                if (lane == 0) sepmask[pi ^ 1][k0 >> 6] = m;
+                if (EMIT && k < cl) stage[fill + k] = (uint8_t)c;
+            }
+            w += cl; pi ^= 1; lp = cl;
+            if (EMIT) {
+                fill += cl;
+                if (lane == 0) offbuf[n_off] = w;
+                n_off++;
+                __syncthreads();
+                if (n_off == 64) { off[read0[b] + r + 1 - 63 + lane] = offbuf[lane]; n_off = 0; }
+                if (fill - start >= HT_FLUSH) {               // whole 16-byte pieces go, what is left moves to the front
+                    const uint32_t upto = fill & ~15u;
+                    ht_store(text, gb + start, stage, start, upto - start, lane);
+                    const uint32_t left = fill - upto;
+                    uint8_t c = 0;
+                    if (lane < left) c = stage[upto + lane];
+                    __syncthreads();
+                    if (lane < left) stage[lane] = c;
+                    gb += upto; start = 0; fill = left;
+                }
+            }
+            __syncthreads();
+        }
+        if (!fail && h.i != h.n) fail = HT_INVALID;               // symbols left over
+        if (!fail && EMIT && w != w_end) fail = HT_SHARE;
+        if (EMIT && !fail) {
+            __syncthreads();
+            ht_store(text, gb + start, stage, start, fill - start, lane);
+            if (lane < n_off) off[read0[b] + n_reads - n_off + 1 + lane] = offbuf[lane];
+        }
+        // where the block ends is where the next one begins, built here or not (its neighbour's offsets count from there)
+        if (EMIT && n_reads && lane == 0) off[read0[b] + n_reads] = w_end;
+        if (lane == 0) { status[b] = fail; text_size[b] = fail ? 0 : w - w0; }
+    }
+}
+void launch_hdr_text(hipStream_t s, const uint8_t* syms, const uint64_t* sym_begin, const unsigned long long* sym_count, const uint32_t* blk_reads,
+                     const uint64_t* read0, const uint64_t* text_begin, uint64_t n_blocks, const uint8_t* first, uint32_t first_len,
+                     uint8_t* text, uint64_t* off, uint32_t* status, uint64_t* text_size) {
+    if (!n_blocks) return;
+    const uint32_t g = (uint32_t)(n_blocks > 256 * 8 ? 256 * 8 : n_blocks);
+    if (text) hipLaunchKernelGGL(k_hdr_text<true>, dim3(g), dim3(64), 0, s, syms, sym_begin, sym_count, blk_reads, read0, text_begin, n_blocks, first, first_len, text, off, status, text_size);
+    else hipLaunchKernelGGL(k_hdr_text<false>, dim3(g), dim3(64), 0, s, syms, sym_begin, sym_count, blk_reads, read0, text_begin, n_blocks, first, first_len, text, off, status, text_size);
+}
+
 size_t path_cache_slot_bytes(uint32_t k) { return k >= 32 ? 32 : 16; }
 // position-dependent 64-bit sum of the bloom's words (the array is padded past n_bytes, bytes beyond it are never set)
 __global__ void k_bloom_fingerprint(const uint8_t* bits, uint64_t n_words, uint64_t* sum) {

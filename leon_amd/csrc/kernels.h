@@ -182,6 +182,13 @@ size_t decode_scratch_bytes(uint64_t n_blocks);
 // header blocks: the stream's symbols as bytes, block b's in syms[sym_begin[b] .. sym_begin[b + 1]) (its share), sym_count[b] of them
 void launch_hdr_decode_symbols(hipStream_t s, const uint8_t* payloads, const uint64_t* pay_off, const uint32_t* blk_reads, uint64_t n_blocks,
                                uint8_t* syms, const uint64_t* sym_begin, unsigned long long* sym_count, int* err);
+// header blocks: the text from those symbols (k_hdr_text, one wave per block).  status[b]: HT_OK, a reason the block was not built
+// on the device (HT_LONG .. HT_NOSYMS: the caller decodes it on the host), or HT_INVALID; text == nullptr: only text_size[b] is counted
+constexpr uint32_t LEON_HT_HEADER_CAP = 4096;                 // the longest header the kernel builds (two of them live in LDS)
+enum : uint32_t { HT_OK = 0, HT_LONG = 1, HT_SHARE = 2, HT_SYMS = 3, HT_NOSYMS = 4, HT_INVALID = 16 };
+void launch_hdr_text(hipStream_t s, const uint8_t* syms, const uint64_t* sym_begin, const unsigned long long* sym_count, const uint32_t* blk_reads,
+                     const uint64_t* read0, const uint64_t* text_begin, uint64_t n_blocks, const uint8_t* first, uint32_t first_len,
+                     uint8_t* text /* 16-byte aligned */, uint64_t* off, uint32_t* status, uint64_t* text_size);
 void launch_decode_blocks(hipStream_t s, BloomDev B, PathCache C, const uint16_t* rv16, const uint64_t* anchors, uint64_t n_anchors,
                           const uint8_t* payloads, const uint64_t* pay_off, const uint32_t* blk_reads, const uint64_t* blk_read0,
                           const uint64_t* blk_out0, uint64_t n_blocks, uint8_t* out, uint32_t* out_len, uint32_t* scratch,

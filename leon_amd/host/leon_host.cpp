@@ -21,6 +21,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <deque>
 #include <cstdio>
@@ -166,6 +167,21 @@ QualEncoder qual_encoder_choice(const std::string& flag) {
     if (!strcmp(e, "device")) return QualEncoder::Device;
     throw Exception(std::string(what) + "'" + e + "': expected host, device or auto");
 }
+// Who rebuilds the header text of `-d`.  Not given, or `host`: the host threads (from the payloads, or from symbols the device decoded
+// where a round has LEON_HEADER_DEVICE_BLOCKS blocks).  `device`: symbols and text of every header block in one device call
+// (leon_header_decode_text), the rounds fetch their blocks' text; blocks the kernel declines go to the host decoder.  `auto`: the
+// device for files of at least kHeaderTextAutoBlocks blocks.  The restored file is the same bytes whichever way.
+enum class HeaderText { Host, Device, Auto };
+HeaderText header_text_choice(const std::string& flag) {
+    if (flag.empty() || flag == "host") return HeaderText::Host;
+    if (flag == "device") return HeaderText::Device;
+    if (flag == "auto") return HeaderText::Auto;
+    throw Exception("option -header-text: '" + flag + "': expected host, device or auto");
+}
+// Measured with `-d -test-file`, the ways alternating (profiles/README.md): 200 blocks, the host ahead (4.3-4.6 s against 4.6-4.7: one wave's
+// chain of 50 000 headers outlasts sixteen cores on 200 blocks); 1 000 blocks, the device ahead in every pair (12.6 / 13.5 / 14.3 s against
+// 12.6 / 15.1 / 15.9); 2 000 blocks, by 1.4-3.2 s of 24-27.  The smallest count at which the device won:
+constexpr uint64_t kHeaderTextAutoBlocks = 1000;
 size_t deflated_size(const std::string& text, int strategy) {
     z_stream z{};
     if (deflateInit2(&z, Z_DEFAULT_COMPRESSION, Z_DEFLATED, 15, 8, strategy) != Z_OK) return 0;
@@ -220,6 +236,7 @@ void Leon::run(int argc, char* argv[]) {
             else if (a == "-noqual") _noQual = true;
             else if (a == "-test-file") _testFile = true;
             else if (a == "-qual-deflate") { _qualDeflate = need("-qual-deflate"); (void)qual_encoder_choice(_qualDeflate); }
+            else if (a == "-header-text") { _headerText = need("-header-text"); (void)header_text_choice(_headerText); }
             else throw Exception("unknown option " + a);
         }
         if (_inputFilename.empty()) throw Exception("option -file is mandatory");
@@ -795,8 +812,12 @@ void Leon::executeDecompression() {
     if (const char* e = getenv("LEON_DECODE_DNA_ROUNDS")) { const long v = atol(e); if (v > 0) dna_rounds = (uint64_t)v; }   // (tests)
     // (what the header-symbol task and the rounds' tasks read: declared before `drain`, so destroyed after it has waited for them)
     RawBytes all_pay_h; std::vector<uint64_t> all_off_h; std::vector<uint32_t> all_reads_h;
+    std::vector<uint64_t> all_text_h;                            // every block's text size, from the block table (`-header-text device`)
+    std::atomic<uint64_t> hdr_blocks_fell_back{0};               // ... and the blocks whose rounds went to the host decoder all the same
     struct SymSet { leon_header_symbols* h = nullptr; ~SymSet() { leon_header_symbols_free(h); } };
     auto hdr_set = std::make_shared<SymSet>();
+    struct TextSet { leon_header_text* h = nullptr; ~TextSet() { leon_header_text_free(h); } };   // (`-header-text device`: the text, in device memory)
+    auto hdr_text_set = std::make_shared<TextSet>();
     std::shared_future<void> hdr_symbols;
     struct Drain {                                               // (no task outlives what it refers to, whatever way this function is left)
         std::vector<std::shared_future<void>> all;
@@ -809,7 +830,10 @@ void Leon::executeDecompression() {
     // A header block is one serial chain on one wave (~1.5 s for 50 000 headers) whether the call holds 200 blocks or 2 000, so a call
     // per round paid that chain every round (4 x 2.7 s of configuration #3's 20 s); the rounds now only rebuild their blocks' text
     // from the symbols, on the host threads.
-    const bool hdr_on_device = has_header && n_blocks > 0 && group >= header_blocks_on_device;
+    // `-header-text device`: the text as well, in the same call; it stays on the device and the rounds fetch their blocks' share
+    const HeaderText hdr_text_choice = header_text_choice(_headerText);
+    const bool hdr_text_device = has_header && n_blocks > 0 && (hdr_text_choice == HeaderText::Device || (hdr_text_choice == HeaderText::Auto && n_blocks >= kHeaderTextAutoBlocks));
+    const bool hdr_on_device = has_header && n_blocks > 0 && (hdr_text_device || group >= header_blocks_on_device);
     if (hdr_on_device) {
         all_off_h.assign(n_blocks + 1, 0); all_reads_h.resize(n_blocks);
         for (uint64_t b = 0; b < n_blocks; b++) { all_off_h[b + 1] = all_off_h[b] + thdr[3 * b]; all_reads_h[b] = (uint32_t)tdna[3 * b + 1]; }
@@ -821,8 +845,13 @@ void Leon::executeDecompression() {
         }
         leon_dna_ctx* hc = hdr_ctx.get();
         const uint8_t* pay = all_pay_h.data(); const uint64_t* off = all_off_h.data(); const uint32_t* nr = all_reads_h.data();
-        hdr_symbols = std::async(std::launch::async, [hc, pay, off, nr, n_blocks, hdr_set] {
-            if (leon_header_decode_symbols(hc, pay, off, nr, n_blocks, &hdr_set->h) != LEON_OK) throw Exception(std::string("header blocks: ") + leon_last_error(hc));
+        if (hdr_text_device) { all_text_h.resize(n_blocks); for (uint64_t b = 0; b < n_blocks; b++) all_text_h[b] = thdr[3 * b + 2]; }
+        const uint64_t* tb = all_text_h.data();
+        const uint8_t* fh = first_header.data(); const uint64_t fh_len = first_header.size();
+        hdr_symbols = std::async(std::launch::async, [hc, pay, off, nr, n_blocks, hdr_set, hdr_text_set, hdr_text_device, tb, fh, fh_len] {
+            const int rc = hdr_text_device ? leon_header_decode_text(hc, pay, off, nr, tb, n_blocks, fh, fh_len, &hdr_text_set->h)
+                                           : leon_header_decode_symbols(hc, pay, off, nr, n_blocks, &hdr_set->h);
+            if (rc != LEON_OK) throw Exception(std::string("header blocks: ") + leon_last_error(hc));
         }).share();
         drain.all.push_back(hdr_symbols);
     }
@@ -871,6 +900,7 @@ void Leon::executeDecompression() {
                 auto th = std::chrono::steady_clock::now();
                 const uint64_t nb = R->nb, g_bases = R->g_bases;
                 const bool on_device = hdr_on_device;
+                const bool text_device = hdr_text_device;
                 auto decode_quals = [&] {
                     R->qual.resize(g_bases + 1);
                     if (leon_host_qual_decode_blocks(R->pay_q.data(), R->off_q.data(), R->blk_reads.data(), R->blk_bases.data(), nb, R->qual.data(), g_bases, R->qual_off.data(), cores) != LEON_OK)
@@ -893,6 +923,12 @@ void Leon::executeDecompression() {
                         catch (...) { if (quals_beside.valid()) { try { quals_beside.get(); } catch (...) {} } throw; }
                     }
                     auto decode = [&]() -> int {
+                        if (text_device && !host_decoder) {
+                            const int rc = leon_header_text_fetch(hdr_text_set->h, R->block0, nb, R->hdr.data(), R->hdr.size(), R->hdr_off.data(), &need);
+                            if (rc != LEON_E_STATE) return rc;
+                            host_decoder = true;                 // the kernel declined a block of the round: the host decoder, from the payloads
+                            hdr_blocks_fell_back += nb;
+                        }
                         if (on_device && !host_decoder) {
                             const int rc = leon_header_text_from_symbols(hdr_set->h, R->block0, nb, R->blk_reads.data(), first_header.data(), first_header.size(),
                                                                          R->hdr.data(), R->hdr.size(), R->hdr_off.data(), &need, cores);
@@ -975,6 +1011,10 @@ void Leon::executeDecompression() {
         std::cout << "time: " << seconds_since(t_start) << " s (" << (n_blocks + group - 1) / group << " round(s); container reads " << t_read << ", dictionary + DNA blocks on the device " << t_dna
                   << "; beside them, a round behind: header blocks " << t_hdr << " + quality blocks " << t_qual << "; another round behind: formatting + writing "
                   << t_text << "; waited for them " << t_writer_wait + t_write << ")" << std::endl;
+    if (_verbose && has_header)
+        std::cout << "header text: " << (hdr_text_device ? "device (k_hdr_text), " + std::to_string(hdr_blocks_fell_back.load()) + " of " + std::to_string(n_blocks) + " blocks fell back to the host decoder"
+                                                         : hdr_on_device ? std::string("host threads, from symbols decoded on the device") : std::string("host threads"))
+                  << std::endl;
     if (_testFile) testDecompressedFile();
 }
 
