@@ -220,6 +220,13 @@ int leon_host_anchor_dict_encode(const uint64_t* kmers, uint64_t n_anchors, uint
 int leon_dna_decode_blocks(leon_dna_ctx* ctx, const uint64_t* anchors, uint64_t n_anchors, const uint8_t* payloads,
                            const uint64_t* payload_off, const uint32_t* block_n_reads, const uint64_t* block_n_bases,
                            uint64_t n_blocks, uint8_t* out_bases, uint64_t out_cap, uint32_t* out_len);
+/* The same with the bases and lengths left in CALLER-OWNED device buffers (leon_device_alloc): d_out_bases (out_cap >= the sum of
+ * block_n_bases) and d_out_len (one uint32 per read), complete on return and untouched when the call fails; out_len (may be NULL): a host
+ * copy of the lengths as well.  Caller-owned, because a caller that works on one call's reads on the device while the next call decodes
+ * cannot have them in the context's own buffers.  Same validation, errors and messages as leon_dna_decode_blocks. */
+int leon_dna_decode_blocks_device(leon_dna_ctx* ctx, const uint64_t* anchors, uint64_t n_anchors, const uint8_t* payloads,
+                                  const uint64_t* payload_off, const uint32_t* block_n_reads, const uint64_t* block_n_bases,
+                                  uint64_t n_blocks, uint8_t* d_out_bases, uint64_t out_cap, uint32_t* d_out_len, uint32_t* out_len);
 /* Host-only (no GPU, no ctx): Leon::decodeAnchorDict, the inverse of the stream leon_dna_finish returns.
  * out_kmers: n_anchors * W words. */
 int leon_host_anchor_dict_decode(const uint8_t* payload, uint64_t size, uint64_t n_anchors, uint32_t kmer_size,
@@ -290,6 +297,42 @@ int leon_header_text_fetch(const leon_header_text* set, uint64_t first_block, ui
 int leon_header_text_device_ptr(const leon_header_text* set, uint64_t first_block, uint64_t n_blocks, const uint8_t** d_text,
                                 const uint64_t** d_off, uint64_t* size);
 void leon_header_text_free(leon_header_text* set);
+/* -- the decoder's last step: the reads' FASTA / FASTQ text, formatted on the device (k_fmt_sizes, k_fmt_records: DESIGN.md 4.9) --
+ * Record r of a call, as the host mirror's -d writes it:
+ *     lead  header r | decimal(first_read_index + r)  '\n'
+ *     the sequence: its len bytes and '\n' when wrap == 0 or len <= wrap, else ceil(len / wrap) lines of at most wrap bytes, each + '\n'
+ *     fastq only:  '+'  [header r again when plus_kind == 1]  '\n'  len quality bytes  '\n'
+ * Everything lies in device memory: d_bases (n_bases bytes, the reads back to back) and d_len[n_reads] as leon_dna_decode_blocks_device
+ * leaves them; d_hdr_text / d_hdr_off[n_reads + 1] as leon_header_text_device_ptr hands them out (header r is d_hdr_text[d_hdr_off[r] -
+ * d_hdr_off[0] .. d_hdr_off[r + 1] - d_hdr_off[0]), hdr_bytes of the layout = d_hdr_off[n_reads] - d_hdr_off[0]); d_hdr_text == NULL: the
+ * read index stands in for the header; d_quals: one byte per base, indexed like d_bases (fastq only).  d_text needs no alignment.
+ * d_rec_off (may be NULL): every record's offset in the text, n_reads + 1 entries.  *text_size: the text's bytes.
+ * LEON_E_OVERFLOW when text_cap is smaller (or d_text NULL): *text_size = the bytes needed, nothing written.  LEON_E_INVALID, nothing
+ * written: lengths that do not add up to n_bases or header offsets that run backwards or do not end at hdr_bytes (checked on the device
+ * before anything is indexed with them), fastq without d_quals, plus_kind == 1 without headers, an unknown struct_size.
+ * The call works on a stream of its own and may run beside calls on any context.  Errors: leon_last_error(NULL). */
+typedef struct leon_record_layout {
+    uint32_t struct_size;        /* sizeof(leon_record_layout) */
+    uint8_t  lead;               /* '@' or '>' */
+    uint8_t  fastq;              /* 1: '+' line and qualities */
+    uint8_t  plus_kind;          /* 0: bare '+' lines, 1: every '+' line repeats its header */
+    uint8_t  reserved;
+    uint32_t wrap;               /* sequence line width, 0 = one line */
+    uint32_t reserved2;
+    uint64_t first_read_index;   /* the index of record 0 (what stands in for a header) */
+    uint64_t hdr_bytes;          /* bytes of d_hdr_text the offsets must end at (ignored without headers) */
+} leon_record_layout;
+int leon_records_format_device(int device_id, const leon_record_layout* lay, const uint8_t* d_bases, const uint32_t* d_len, uint64_t n_reads,
+                               uint64_t n_bases, const uint8_t* d_hdr_text, const uint64_t* d_hdr_off, const uint8_t* d_quals, uint8_t* d_text,
+                               uint64_t text_cap, uint64_t* d_rec_off, uint64_t* text_size);
+/* Device memory to a sink, in the pinned pieces the copy lands in (no second copy into pageable memory): the sink receives pieces of at
+ * most 16 MiB, every byte of [0, bytes) exactly once, disjoint, IN NO PARTICULAR ORDER AND FROM UP TO LEON_UPLOAD_THREADS (default 3)
+ * THREADS AT ONCE; a piece is valid until the sink returns.  Non-zero from the sink stops the call with LEON_E_SINK (pieces already
+ * under way on other threads may still arrive).  Copies below four pieces come one piece at a time on the calling thread, from a pinned
+ * buffer as well.  Errors: leon_last_error(NULL). */
+typedef int (*leon_piece_sink)(void* user, uint64_t offset, const void* bytes, uint64_t size);
+int leon_device_download_pieces(int device_id, const void* d_src, uint64_t bytes, leon_piece_sink sink, void* user);
+
 /* Quality stream, lossy form (Leon's default, /root/reference/README.md:55): DnaEncoder::storeSolidCoverageInfo + smoothQuals
  * [RECALLED]: a quality becomes '@' where at least two of the read's solid k-mers (in the bloom of ctx) span the position, or
  * where it is above '@'; reads shorter than k are left alone.  quals: one byte per base, same offsets as the bases, rewritten

@@ -51,6 +51,16 @@ XCH_OFF, XCH_BY_ANCHOR, XCH_EMULATE = 0, 1, 2
 # leon_gather_fn: (user, d_buf, part_bytes, world) -> 0 on success
 GATHER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32)
 
+# leon_piece_sink: (user, offset, bytes, size) -> 0 to go on
+PIECE_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64)
+
+
+class RecordLayout(C.Structure):
+    """leon_record_layout"""
+    _fields_ = [("struct_size", C.c_uint32), ("lead", C.c_uint8), ("fastq", C.c_uint8), ("plus_kind", C.c_uint8), ("reserved", C.c_uint8),
+                ("wrap", C.c_uint32), ("reserved2", C.c_uint32), ("first_read_index", C.c_uint64), ("hdr_bytes", C.c_uint64)]
+
+
 _u8p, _u32p, _i32p, _u64p = (C.POINTER(t) for t in (C.c_uint8, C.c_uint32, C.c_int32, C.c_uint64))
 
 _EXPORTS = {
@@ -74,6 +84,11 @@ _EXPORTS = {
                                                 C.c_void_p]),
     "leon_dna_decode_blocks": (C.c_int, [C.c_void_p, _u64p, C.c_uint64, _u8p, _u64p, _u32p, _u64p, C.c_uint64, _u8p, C.c_uint64,
                                           _u32p]),
+    "leon_dna_decode_blocks_device": (C.c_int, [C.c_void_p, _u64p, C.c_uint64, _u8p, _u64p, _u32p, _u64p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                 C.c_void_p, _u32p]),
+    "leon_records_format_device": (C.c_int, [C.c_int, C.POINTER(RecordLayout), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, _u64p]),
+    "leon_device_download_pieces": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, PIECE_SINK, C.c_void_p]),
     "leon_host_anchor_dict_decode": (C.c_int, [_u8p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p]),
     "leon_dna_finish": (C.c_int, [C.c_void_p, C.POINTER(_u8p), _u64p, _u64p]),
     "leon_dna_reset_stream": (C.c_int, [C.c_void_p]),
@@ -339,6 +354,66 @@ def device_upload_bytes(data, device_id=0):
     if rc:
         raise LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
     return p.value
+
+
+def device_alloc(n_bytes, device_id=0):
+    """plain device memory (leon_device_alloc); the caller frees it with device_free"""
+    lib = load_library()
+    p = C.c_void_p()
+    rc = lib.leon_device_alloc(device_id, int(n_bytes), C.byref(p))
+    if rc:
+        raise LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+    return p.value
+
+
+def device_download(d_ptr, n_bytes, device_id=0):
+    """n_bytes from a raw device pointer, as bytes"""
+    lib = load_library()
+    out = np.zeros(max(int(n_bytes), 1), dtype=np.uint8)
+    rc = lib.leon_device_download(device_id, C.c_void_p(out.ctypes.data), C.c_void_p(int(d_ptr)), int(n_bytes))
+    if rc:
+        raise LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+    return out[:int(n_bytes)].tobytes()
+
+
+def device_download_pieces(d_ptr, n_bytes, sink, device_id=0):
+    """leon_device_download_pieces: sink(offset, address, size) -> 0 to go on, called with every pinned piece where it landed -- in no
+    particular order and from several threads at once"""
+    lib = load_library()
+    raised = []
+
+    def thunk(user, offset, address, size):
+        try:
+            return int(sink(int(offset), int(address or 0), int(size)) or 0)
+        except Exception as e:                         # noqa: BLE001 -- nothing may cross the C boundary
+            raised.append(e)
+            return 1
+    rc = lib.leon_device_download_pieces(device_id, C.c_void_p(int(d_ptr)), int(n_bytes), PIECE_SINK(thunk), None)
+    if rc:
+        err = LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+        if raised:
+            raise err from raised[0]
+        raise err
+
+
+def records_format_device(d_bases, d_len, n_reads, n_bases, d_text, text_cap, lead=b"@", fastq=True, plus_kind=0, wrap=0, first_read_index=0,
+                          d_hdr_text=None, d_hdr_off=None, hdr_bytes=0, d_quals=None, d_rec_off=None, device_id=0, struct_size=None):
+    """leon_records_format_device over raw device pointers: the reads' FASTA / FASTQ text into d_text.  Returns the text's size;
+    a LeonDnaError carries .text_size (the bytes needed) when the capacity was too small"""
+    lib = load_library()
+    lay = RecordLayout()
+    lay.struct_size = C.sizeof(RecordLayout) if struct_size is None else struct_size
+    lay.lead, lay.fastq, lay.plus_kind, lay.wrap = lead[0], 1 if fastq else 0, plus_kind, wrap
+    lay.first_read_index, lay.hdr_bytes = int(first_read_index), int(hdr_bytes)
+    size = C.c_uint64()
+    vp = lambda p: C.c_void_p(int(p)) if p else None
+    rc = lib.leon_records_format_device(device_id, C.byref(lay), vp(d_bases), vp(d_len), int(n_reads), int(n_bases), vp(d_hdr_text), vp(d_hdr_off),
+                                        vp(d_quals), vp(d_text), int(text_cap), vp(d_rec_off), C.byref(size))
+    if rc:
+        err = LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+        err.text_size = int(size.value)
+        raise err
+    return int(size.value)
 
 
 class DnaEncodeContext:
@@ -639,6 +714,25 @@ class DnaEncodeContext:
                                                   _ptr(nreads, _u32p), _ptr(nbases, _u64p), nb, _ptr(out, _u8p), total,
                                                   _ptr(lens, _u32p)))
         return out[:total], lens[:n_total]
+
+    def decode_blocks_device(self, anchors, blocks, block_n_bases, d_bases, d_len, host_lens=True):
+        """decode_blocks_raw with the bases and lengths left in the caller's device buffers (raw pointers, device_alloc): returns the
+        host copy of the lengths (or None)"""
+        blocks = sorted(blocks)
+        nb = len(blocks)
+        anchors = np.ascontiguousarray(anchors, dtype=np.uint64)
+        W = kmer_words(self.kmer_size)
+        pay = np.frombuffer(b"".join(b[1] for b in blocks) + b"\0", dtype=np.uint8)
+        off = np.zeros(nb + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(b[1]) for b in blocks], dtype=np.uint64)
+        nreads = np.array([b[2] for b in blocks], dtype=np.uint32)
+        nbases = np.ascontiguousarray(block_n_bases, dtype=np.uint64)
+        total, n_total = int(nbases.sum()), int(nreads.sum())
+        lens = np.zeros(n_total + 1, dtype=np.uint32) if host_lens else None
+        self._chk(self.lib.leon_dna_decode_blocks_device(self.h, _ptr(anchors, _u64p), len(anchors) // W, _ptr(pay, _u8p), _ptr(off, _u64p),
+                                                         _ptr(nreads, _u32p), _ptr(nbases, _u64p), nb, C.c_void_p(int(d_bases)), total,
+                                                         C.c_void_p(int(d_len)), _ptr(lens, _u32p) if host_lens else None))
+        return lens[:n_total] if host_lens else None
 
     def reserve(self, max_reads, max_bases):
         self._chk(self.lib.leon_dna_reserve(self.h, int(max_reads), int(max_bases)))

@@ -1764,12 +1764,18 @@ int leon_host_anchor_dict_decode(const uint8_t* payload, uint64_t size, uint64_t
     return LEON_OK;
 }
 
-int leon_dna_decode_blocks(leon_dna_ctx* c, const uint64_t* anchors, uint64_t n_anchors, const uint8_t* payloads,
-                           const uint64_t* payload_off, const uint32_t* block_n_reads, const uint64_t* block_n_bases,
-                           uint64_t n_blocks, uint8_t* out_bases, uint64_t out_cap, uint32_t* out_len) {
+// leon_dna_decode_blocks and leon_dna_decode_blocks_device: the same call up to where the bases go once every block has decoded --
+// to the caller's host memory (out_bases, out_len), or to the caller's device buffers (d_user_bases, d_user_len; out_len then
+// optional, the host's copy of the lengths)
+static int decode_blocks_impl(leon_dna_ctx* c, const uint64_t* anchors, uint64_t n_anchors, const uint8_t* payloads,
+                              const uint64_t* payload_off, const uint32_t* block_n_reads, const uint64_t* block_n_bases,
+                              uint64_t n_blocks, uint8_t* out_bases, uint64_t out_cap, uint32_t* out_len, uint8_t* d_user_bases,
+                              uint32_t* d_user_len) {
     if (!c) return LEON_E_INVALID;
     if (n_blocks == 0) return LEON_OK;
-    if (!payloads || !payload_off || !block_n_reads || !block_n_bases || !out_bases || !out_len || (!anchors && n_anchors))
+    const bool to_device = d_user_bases != nullptr;
+    if (!payloads || !payload_off || !block_n_reads || !block_n_bases || (!to_device && (!out_bases || !out_len)) || (to_device && !d_user_len) ||
+        (!anchors && n_anchors))
         return fail(c, LEON_E_INVALID, "null argument");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
@@ -1869,7 +1875,7 @@ int leon_dna_decode_blocks(leon_dna_ctx* c, const uint64_t* anchors, uint64_t n_
     std::vector<std::thread> toucher;
     {
         const uint64_t nb_out = out0[n_blocks];
-        const uint32_t nt = nb_out >= (256ull << 20) ? 4u : 0u;
+        const uint32_t nt = !to_device && nb_out >= (256ull << 20) ? 4u : 0u;
         for (uint32_t w = 0; w < nt; w++)
             toucher.emplace_back([out_bases, nb_out, w, nt] {
                 volatile uint8_t* q = out_bases;
@@ -1897,9 +1903,95 @@ int leon_dna_decode_blocks(leon_dna_ctx* c, const uint64_t* anchors, uint64_t n_
                          : err[0] == 4 ? "the payload ends before its reads do" : "too many N / error positions in one read";
         return fail(c, LEON_E_INVALID, std::string("block ") + std::to_string(err[1]) + " does not decode: " + what);
     }
+    if (to_device) {                                          // the bases stay in HBM: into the caller's buffers, complete on return
+        if (out0[n_blocks]) HIPCHK(c, hipMemcpyAsync(d_user_bases, d_out.p, out0[n_blocks], hipMemcpyDeviceToDevice, s));
+        if (read0[n_blocks]) HIPCHK(c, hipMemcpyAsync(d_user_len, d_len.p, read0[n_blocks] * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        if (out_len && read0[n_blocks]) HIPCHK(c, staged_d2h(c->device, out_len, d_len.p, read0[n_blocks] * 4));
+        lap("bases to the caller's device buffers");
+        return LEON_OK;
+    }
     HIPCHK(c, staged_d2h(c->device, out_bases, d_out.p, out0[n_blocks]));     // gigabytes into the caller's pageable memory: at PCIe's rate (staging.h)
     if (read0[n_blocks]) HIPCHK(c, staged_d2h(c->device, out_len, d_len.p, read0[n_blocks] * 4));
     lap("bases to the host");
+    return LEON_OK;
+}
+
+int leon_dna_decode_blocks(leon_dna_ctx* c, const uint64_t* anchors, uint64_t n_anchors, const uint8_t* payloads,
+                           const uint64_t* payload_off, const uint32_t* block_n_reads, const uint64_t* block_n_bases,
+                           uint64_t n_blocks, uint8_t* out_bases, uint64_t out_cap, uint32_t* out_len) {
+    return decode_blocks_impl(c, anchors, n_anchors, payloads, payload_off, block_n_reads, block_n_bases, n_blocks, out_bases, out_cap, out_len, nullptr, nullptr);
+}
+
+int leon_dna_decode_blocks_device(leon_dna_ctx* c, const uint64_t* anchors, uint64_t n_anchors, const uint8_t* payloads,
+                                  const uint64_t* payload_off, const uint32_t* block_n_reads, const uint64_t* block_n_bases,
+                                  uint64_t n_blocks, uint8_t* d_out_bases, uint64_t out_cap, uint32_t* d_out_len, uint32_t* out_len) {
+    if (!c) return LEON_E_INVALID;
+    if (n_blocks && (!d_out_bases || !d_out_len)) return fail(c, LEON_E_INVALID, "null argument");
+    return decode_blocks_impl(c, anchors, n_anchors, payloads, payload_off, block_n_reads, block_n_bases, n_blocks, nullptr, out_cap, out_len, d_out_bases, d_out_len);
+}
+
+// ---- record text on the device (fmt_kernels.hip) ----
+int leon_records_format_device(int device_id, const leon_record_layout* lay, const uint8_t* d_bases, const uint32_t* d_len, uint64_t n_reads,
+                               uint64_t n_bases, const uint8_t* d_hdr_text, const uint64_t* d_hdr_off, const uint8_t* d_quals, uint8_t* d_text,
+                               uint64_t text_cap, uint64_t* d_rec_off, uint64_t* text_size) {
+    if (!lay || !text_size) return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: null argument");
+    *text_size = 0;
+    if (lay->struct_size != sizeof(leon_record_layout))
+        return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: unknown struct_size " + std::to_string(lay->struct_size) + " of leon_record_layout");
+    if (lay->plus_kind > 1) return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: plus_kind must be 0 (bare) or 1 (the header again)");
+    if (n_reads > (1ull << 40) || n_bases > (1ull << 46)) return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: implausible sizes");
+    if ((n_reads && !d_len) || (n_bases && !d_bases)) return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: null argument");
+    if (lay->fastq && !d_quals) return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: FASTQ records need the qualities (d_quals)");
+    if (lay->plus_kind == 1 && !d_hdr_text)
+        return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: '+' lines that repeat the header need the headers (d_hdr_text)");
+    if (d_hdr_text && !d_hdr_off) return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: headers without their offsets (d_hdr_off)");
+    if (!n_reads) return LEON_OK;
+    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_NO_DEVICE, "leon_records_format_device: no such HIP device"); }
+    // a stream of its own: the call runs beside decode calls on the contexts' streams
+    struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
+    HIPCHK(nullptr, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    hipStream_t s = st.s;
+    const uint64_t* hdr_off = d_hdr_text ? d_hdr_off : nullptr;
+    FmtLayout L{};
+    L.first_read_index = lay->first_read_index; L.hdr_bytes = lay->hdr_bytes; L.wrap = lay->wrap;
+    L.lead = lay->lead; L.fastq = lay->fastq ? 1 : 0; L.plus_kind = lay->fastq ? lay->plus_kind : 0;
+    TmpBuf d_in, d_off, d_flags, d_tmp;
+    HIPCHK(nullptr, d_in.ensure((n_reads + 1) * sizeof(FmtPair))); HIPCHK(nullptr, d_off.ensure((n_reads + 1) * sizeof(FmtPair)));
+    HIPCHK(nullptr, d_flags.ensure(64));
+    HIPCHK(nullptr, hipMemsetAsync(d_flags.p, 0, 64, s));
+    launch_fmt_sizes(s, L, d_len, hdr_off, n_reads, d_in.as<FmtPair>(), d_flags.as<uint32_t>());
+    HIPCHK(nullptr, hipGetLastError());
+    size_t tmp_bytes = 0;
+    HIPCHK(nullptr, fmt_scan(nullptr, tmp_bytes, d_in.as<FmtPair>(), d_off.as<FmtPair>(), n_reads, s));
+    HIPCHK(nullptr, d_tmp.ensure(std::max<size_t>(tmp_bytes, 16)));
+    HIPCHK(nullptr, fmt_scan(d_tmp.p, tmp_bytes, d_in.as<FmtPair>(), d_off.as<FmtPair>(), n_reads, s));
+    uint32_t flags[2] = {0, 0};
+    uint64_t totals[2] = {0, 0};
+    HIPCHK(nullptr, hipMemcpyAsync(flags, d_flags.p, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(nullptr, hipMemcpyAsync(totals, d_off.as<FmtPair>() + n_reads, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(nullptr, hipStreamSynchronize(s));
+    // what the arrays say against what the call was told, before anything is indexed with it
+    if (flags[0]) return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: the header offsets (d_hdr_off) run backwards");
+    if (flags[1]) return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: the header offsets (d_hdr_off) do not end at the " + std::to_string(lay->hdr_bytes) + " header bytes given");
+    if (totals[1] != n_bases)
+        return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: the lengths (d_len) add up to " + std::to_string(totals[1]) + " bases, not the " + std::to_string(n_bases) + " given");
+    *text_size = totals[0];
+    if (totals[0] > text_cap || !d_text) return fail(nullptr, LEON_E_OVERFLOW, "leon_records_format_device: the text needs " + std::to_string(totals[0]) + " bytes");
+    launch_fmt_records(s, L, d_off.as<FmtPair>(), hdr_off, n_reads, d_bases, d_hdr_text, d_quals, d_text, totals[0]);
+    HIPCHK(nullptr, hipGetLastError());
+    if (d_rec_off) { launch_fmt_rec_off(s, d_off.as<FmtPair>(), n_reads, d_rec_off); HIPCHK(nullptr, hipGetLastError()); }
+    HIPCHK(nullptr, hipStreamSynchronize(s));
+    return LEON_OK;
+}
+
+int leon_device_download_pieces(int device_id, const void* d_src, uint64_t bytes, leon_piece_sink sink, void* user) {
+    if (!sink || (bytes && !d_src)) return fail(nullptr, LEON_E_INVALID, "leon_device_download_pieces: null argument");
+    if (!bytes) return LEON_OK;
+    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_NO_DEVICE, "leon_device_download_pieces: no such HIP device"); }
+    const int rc = staged_d2h_pieces(device_id, d_src, bytes, [&](uint64_t offset, const void* p, uint64_t size) { return sink(user, offset, p, size); });
+    if (rc == 2) return fail(nullptr, LEON_E_SINK, "leon_device_download_pieces: the sink returned non-zero");
+    if (rc) return fail(nullptr, LEON_E_HIP, "leon_device_download_pieces: copy to the host failed");
     return LEON_OK;
 }
 

@@ -195,4 +195,22 @@ void launch_decode_blocks(hipStream_t s, BloomDev B, PathCache C, const uint16_t
                           uint32_t* pool, unsigned long long* pool_cursor, uint64_t pool_words, int* err,
                           unsigned long long* stats /* nullptr, or 16 counters: rounds by kind, time by part (LEON_TRACE_DECODE) */);
 
+// ---- record text (fmt_kernels.hip): FASTA / FASTQ records formatted on the device, DESIGN.md 4.9 ----
+struct FmtLayout { uint64_t first_read_index, hdr_bytes; uint32_t wrap; uint8_t lead, fastq, plus_kind; };
+struct FmtPair {                                               // what the scan carries: a record's text offset and its first base
+    uint64_t rec, base;
+    FmtPair() = default;
+    __host__ __device__ FmtPair(int v) : rec((uint64_t)v), base((uint64_t)v) {}
+    __host__ __device__ FmtPair(uint64_t r, uint64_t b) : rec(r), base(b) {}
+    __host__ __device__ FmtPair operator+(const FmtPair& o) const { return FmtPair(rec + o.rec, base + o.base); }
+};
+// in[n_reads + 1] = every record's (text bytes, bases) and a last (0, 0); flags[0]: the header offsets run backwards, flags[1]: they do
+// not end at L.hdr_bytes (both zeroed by the caller); hdr_off == nullptr: the read index stands in for the header
+void launch_fmt_sizes(hipStream_t s, const FmtLayout& L, const uint32_t* len, const uint64_t* hdr_off, uint64_t n_reads, FmtPair* in, uint32_t* flags);
+hipError_t fmt_scan(void* tmp, size_t& bytes, const FmtPair* in, FmtPair* out, uint64_t n_reads, hipStream_t s);   // exclusive, n_reads + 1 entries: out[n_reads] = the totals
+void launch_fmt_rec_off(hipStream_t s, const FmtPair* off, uint64_t n_reads, uint64_t* rec_off);
+// the text itself; the caller has verified off[n_reads] == (text_size, the bases given) and both flags of launch_fmt_sizes
+void launch_fmt_records(hipStream_t s, const FmtLayout& L, const FmtPair* off, const uint64_t* hdr_off, uint64_t n_reads, const uint8_t* bases,
+                        const uint8_t* hdr, const uint8_t* quals, uint8_t* text, uint64_t text_size);
+
 }  // namespace leon

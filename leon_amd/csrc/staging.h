@@ -99,6 +99,60 @@ inline hipError_t staged_d2h(int dev, void* dst, const void* d_src, uint64_t n) 
     return failed.load() ? hipErrorUnknown : hipSuccess;
 }
 
+// device -> the caller's sink, blocking: staged_d2h without its last memcpy.  Every pinned piece (at most kStagePiece bytes) is handed
+// to sink(offset, bytes, size) where it landed: every byte exactly once, in no particular order, from up to stage_threads() threads
+// at once.  Copies below four pieces go through one pinned buffer on the calling thread.  0 = done, 1 = a copy failed, 2 = the sink
+// returned non-zero (the other workers stop at their next piece).
+template <typename Sink>
+inline int staged_d2h_pieces(int dev, const void* d_src, uint64_t n, Sink&& sink) {
+    if (!n) return 0;
+    const uint64_t n_pieces = (n + kStagePiece - 1) / kStagePiece;
+    if (n_pieces < 4) {
+        void* buf = stage_pool().get();
+        if (!buf) return 1;
+        int rc = 0;
+        for (uint64_t a = 0; a < n && !rc; a += kStagePiece) {
+            const uint64_t m = std::min<uint64_t>(kStagePiece, n - a);
+            if (hipMemcpy(buf, (const uint8_t*)d_src + a, m, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); rc = 1; }
+            else if (sink(a, (const void*)buf, m)) rc = 2;
+        }
+        stage_pool().put(buf);
+        return rc;
+    }
+    std::atomic<uint64_t> next{0};
+    std::atomic<int> failed{0};
+    auto work = [&] {
+        StageLane L(dev);
+        if (!L.ok) { int z = 0; failed.compare_exchange_strong(z, 1); return; }
+        uint64_t held[2] = {~0ull, ~0ull};
+        auto finish = [&](int t) -> bool {               // buffer t's piece has arrived: to the sink, from where it is
+            if (held[t] == ~0ull) return true;
+            if (hipEventSynchronize(L.ev[t]) != hipSuccess) { int z = 0; failed.compare_exchange_strong(z, 1); return false; }
+            const uint64_t a = held[t] * kStagePiece;
+            held[t] = ~0ull;
+            if (sink(a, (const void*)L.buf[t], std::min<uint64_t>(kStagePiece, n - a))) { failed.store(2); return false; }
+            return true;
+        };
+        for (int turn = 0; !failed.load(); turn ^= 1) {
+            if (!finish(turn)) break;
+            const uint64_t piece = next.fetch_add(1);
+            if (piece >= n_pieces) break;
+            const uint64_t a = piece * kStagePiece, m = std::min<uint64_t>(kStagePiece, n - a);
+            if (hipMemcpyAsync(L.buf[turn], (const uint8_t*)d_src + a, m, hipMemcpyDeviceToHost, L.st) != hipSuccess ||
+                hipEventRecord(L.ev[turn], L.st) != hipSuccess) { int z = 0; failed.compare_exchange_strong(z, 1); break; }
+            held[turn] = piece;
+        }
+        for (int t = 0; t < 2; t++) if (!failed.load() && !finish(t)) break;
+    };
+    std::vector<std::thread> th;
+    const uint32_t nt = (uint32_t)std::min<uint64_t>(stage_threads(), n_pieces);
+    for (uint32_t i = 1; i < nt; i++) th.emplace_back(work);
+    work();
+    for (auto& t : th) t.join();
+    (void)hipSetDevice(dev);
+    return failed.load();
+}
+
 // pageable host -> device, blocking
 inline hipError_t staged_h2d(int dev, void* d_dst, const void* src, uint64_t n) {
     if (!n) return hipSuccess;

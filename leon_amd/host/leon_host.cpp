@@ -182,6 +182,23 @@ HeaderText header_text_choice(const std::string& flag) {
 // chain of 50 000 headers outlasts sixteen cores on 200 blocks); 1 000 blocks, the device ahead in every pair (12.6 / 13.5 / 14.3 s against
 // 12.6 / 15.1 / 15.9); 2 000 blocks, by 1.4-3.2 s of 24-27.  The smallest count at which the device won:
 constexpr uint64_t kHeaderTextAutoBlocks = 1000;
+// Who formats the records of `-d` (lead byte, header, sequence lines, '+' line, qualities).  Not given, or `host`: the host threads
+// (write_round below).  `device`: the bases never leave the device (leon_dna_decode_blocks_device), the header text stays there too under
+// `-header-text device`, the qualities go up, leon_records_format_device writes the text and it comes back in pinned pieces that are
+// pwritten as they are.  A file whose '+' lines are mixed is formatted on the host whatever the option says.  `auto`: the device for
+// files of at least kRecordTextAutoBlocks blocks (no file today: see the constant).  The restored file is the same bytes whichever way.
+enum class RecordText { Host, Device, Auto };
+RecordText record_text_choice(const std::string& flag) {
+    if (flag.empty() || flag == "host") return RecordText::Host;
+    if (flag == "device") return RecordText::Device;
+    if (flag == "auto") return RecordText::Auto;
+    throw Exception("option -record-text: '" + flag + "': expected host, device or auto");
+}
+// Measured with `-d` and `-d -test-file`, the ways alternating, three each (profiles/README.md): 200 blocks, the device ahead in every pair
+// (3.05-3.74 s against 4.03-4.41); 1 000 blocks, ahead in four pairs of six (9.7-12.1 s against 10.8-11.9); 2 000 blocks, in five of six
+// (18.1-20.8 s against 17.6-22.9).  Ahead on average everywhere, but there is no block count FROM which it was ahead in every pair, and
+// that is the rule `auto` follows (as kHeaderTextAutoBlocks does): `auto` = `host` until a measurement says otherwise.
+constexpr uint64_t kRecordTextAutoBlocks = ~0ull;
 size_t deflated_size(const std::string& text, int strategy) {
     z_stream z{};
     if (deflateInit2(&z, Z_DEFAULT_COMPRESSION, Z_DEFLATED, 15, 8, strategy) != Z_OK) return 0;
@@ -237,6 +254,7 @@ void Leon::run(int argc, char* argv[]) {
             else if (a == "-test-file") _testFile = true;
             else if (a == "-qual-deflate") { _qualDeflate = need("-qual-deflate"); (void)qual_encoder_choice(_qualDeflate); }
             else if (a == "-header-text") { _headerText = need("-header-text"); (void)header_text_choice(_headerText); }
+            else if (a == "-record-text") { _recordText = need("-record-text"); (void)record_text_choice(_recordText); }
             else throw Exception("unknown option " + a);
         }
         if (_inputFilename.empty()) throw Exception("option -file is mandatory");
@@ -692,6 +710,14 @@ void Leon::executeDecompression() {
     };
     const uint64_t wrap = fasta_in ? params[P_FASTA_LINE_WIDTH] : 0;      // sequences wrapped at this width in the original (0: one line)
     const char lead = fastq_out ? '@' : '>';
+    // `-record-text`: the records formatted on the device, where every '+' line is of one kind
+    const RecordText rt_choice = record_text_choice(_recordText);
+    const bool rt_asked = n_blocks > 0 && (rt_choice == RecordText::Device || (rt_choice == RecordText::Auto && n_blocks >= kRecordTextAutoBlocks));
+    std::string rt_reason;                                      // why the host formats although the device was asked for
+    if (rt_asked && (!plus.exc.empty() || plus.def > 1)) rt_reason = "the '+' lines are mixed: exception records in the pluslines table";
+    const bool rt_device = rt_asked && rt_reason.empty();
+    const int rt_dev = device_for(0);
+    std::atomic<uint64_t> rt_rounds_on_device{0}, rt_rounds_no_memory{0};
 
     // Blocks decoded per round.  A round costs the device ONE block's serial chain whatever the number of blocks in it (up to
     // a few thousand: one wave per block), so rounds should be large; up to five are alive at a time (see the stages below), each
@@ -717,11 +743,22 @@ void Leon::executeDecompression() {
         uint64_t size() const { return n; }
     };
     // what one round hands from the decoding stage to the writing stage
-    struct DnaGroup { RawBytes bases; std::unique_ptr<uint32_t[]> lens; };   // the DNA blocks of one device call: the bases and lengths of its rounds
+    struct DnaGroup {                                            // the DNA blocks of one device call: the bases and lengths of its rounds
+        RawBytes bases; std::unique_ptr<uint32_t[]> lens;
+        // `-record-text device`: the bases and lengths stay in device buffers of the call's own, until its last round is written
+        void* d_bases = nullptr; void* d_lens = nullptr;
+        std::atomic<uint32_t> rounds_left{0};
+        void release_device() { leon_device_free(d_bases); leon_device_free(d_lens); d_bases = d_lens = nullptr; }
+        ~DnaGroup() { release_device(); }
+    };
     struct Round {
         uint64_t read_index = 0, file_off = 0, g_reads = 0, g_bases = 0, n_text = 0, nb = 0, hdr_text_bytes = 0, block0 = 0;
         std::shared_ptr<DnaGroup> dna; uint64_t base0 = 0, read0 = 0;   // this round's share of them
-        const uint8_t* bases() const { return dna->bases.p.get() + base0; }
+        const uint8_t* bases() const { return own_bases.p ? own_bases.p.get() : dna->bases.p.get() + base0; }
+        bool on_device = false;                                  // `-record-text device`: the round's bases are in dna->d_bases
+        bool hdr_in_set = false;                                 // ... and its header text lies in the device's header-text set:
+        const uint8_t* d_hdr = nullptr; const uint64_t* d_hdr_off = nullptr; uint64_t d_hdr_size = 0;
+        RawBytes own_bases;                                      // (a round that had to come back to the host: no device memory for its text)
         const uint32_t* lens() const { return dna->lens.get() + read0; }
         RawBytes hdr, qual, pay_h, pay_q;                        // (gigabytes each: never zero-filled)
         std::vector<uint64_t> off_h, off_q, blk_bases;
@@ -819,6 +856,92 @@ void Leon::executeDecompression() {
     struct TextSet { leon_header_text* h = nullptr; ~TextSet() { leon_header_text_free(h); } };   // (`-header-text device`: the text, in device memory)
     auto hdr_text_set = std::make_shared<TextSet>();
     std::shared_future<void> hdr_symbols;
+    // The writing stage of `-record-text device`: the round's records formatted by the device from the bases (and, under `-header-text
+    // device`, the header text) that are there already; the finished text comes back in pinned pieces, each pwritten where it landed.
+    // false: no device memory for the round's buffers (nothing written): the caller formats it on the host.
+    auto write_round_device = [&](std::shared_ptr<Round> R) -> bool {
+        auto tl = std::chrono::steady_clock::now();
+        const uint64_t g_reads = R->g_reads, g_bases = R->g_bases, n_text = R->n_text;
+        if (fastq_out)
+            for (uint64_t r = 0; r < g_reads; r++)
+                if (R->qual_off[r + 1] - R->qual_off[r] != R->lens()[r]) throw Exception(_inputFilename + ": a read's quality and sequence lengths differ");
+        struct Dev { void* p = nullptr; ~Dev() { leon_device_free(p); } } d_text, d_qual, d_hdr, d_hoff;
+        auto upload = [&](void* d, const void* src, uint64_t n) {
+            if (leon_device_upload(rt_dev, d, src, n) != LEON_OK) throw Exception(std::string("leon_device_upload: ") + leon_last_error(nullptr));
+        };
+        if (leon_device_alloc(rt_dev, n_text + 64, &d_text.p) != LEON_OK) return false;
+        if (fastq_out) {
+            if (leon_device_alloc(rt_dev, g_bases + 64, &d_qual.p) != LEON_OK) return false;
+            upload(d_qual.p, R->qual.data(), g_bases);
+        }
+        const uint8_t* hp = nullptr; const uint64_t* ho = nullptr;
+        uint64_t hb = 0;
+        if (has_header && R->hdr_in_set) { hp = R->d_hdr; ho = R->d_hdr_off; hb = R->d_hdr_size; }
+        else if (has_header) {                                   // decoded on the host (`-header-text host`, or a block the kernel declined): up it goes
+            hb = R->hdr_off[g_reads] - R->hdr_off[0];
+            if (leon_device_alloc(rt_dev, hb + 64, &d_hdr.p) != LEON_OK || leon_device_alloc(rt_dev, (g_reads + 1) * 8, &d_hoff.p) != LEON_OK) return false;
+            upload(d_hdr.p, R->hdr.data() + R->hdr_off[0], hb);
+            upload(d_hoff.p, R->hdr_off.data(), (g_reads + 1) * 8);
+            hp = (const uint8_t*)d_hdr.p; ho = (const uint64_t*)d_hoff.p;
+        }
+        leon_record_layout lay{};
+        lay.struct_size = (uint32_t)sizeof(lay); lay.lead = (uint8_t)lead; lay.fastq = fastq_out ? 1 : 0; lay.plus_kind = fastq_out && plus.def == 1 ? 1 : 0;
+        lay.wrap = (uint32_t)std::min<uint64_t>(wrap, 0xFFFFFFFFull); lay.first_read_index = R->read_index; lay.hdr_bytes = hb;
+        uint64_t size = 0;
+        const int rc = leon_records_format_device(rt_dev, &lay, (const uint8_t*)R->dna->d_bases + R->base0, (const uint32_t*)R->dna->d_lens + R->read0, g_reads, g_bases,
+                                                  hp, ho, (const uint8_t*)d_qual.p, (uint8_t*)d_text.p, n_text, nullptr, &size);
+        if (rc == LEON_E_OVERFLOW || (rc == LEON_OK && size != n_text)) throw Exception(_inputFilename + ": the decoded reads do not add up to their blocks' sizes");
+        if (rc != LEON_OK) throw Exception(std::string("leon_records_format_device: ") + leon_last_error(nullptr));
+        // the text comes back in pinned pieces, each pwritten where it landed; a download keeps up to three copies in flight (PCIe's
+        // rate), the page cache takes more writers than that: four downloads side by side, each its own quarter of the text
+        struct Out { int fd; uint64_t at; };
+        auto piece_out = [](void* user, uint64_t offset, const void* bytes, uint64_t n) -> int {
+            const Out* o = static_cast<const Out*>(user);
+            for (uint64_t done = 0; done < n;) {
+                const ssize_t got = ::pwrite(o->fd, static_cast<const char*>(bytes) + done, (size_t)(n - done), (off_t)(o->at + offset + done));
+                if (got <= 0) return 1;
+                done += (uint64_t)got;
+            }
+            return 0;
+        };
+        const uint64_t piece = 16ull << 20, n_pieces = (n_text + piece - 1) / piece;
+        const uint32_t n_dl = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4, n_pieces / 4));
+        std::vector<int> dl_rc(n_dl, LEON_OK);
+        std::vector<std::string> dl_err(n_dl);
+        auto download = [&](uint32_t i) {
+            const uint64_t a = n_pieces * i / n_dl * piece, b = std::min(n_text, n_pieces * (i + 1) / n_dl * piece);
+            Out out{ofd.fd, R->file_off + a};
+            dl_rc[i] = leon_device_download_pieces(rt_dev, (const uint8_t*)d_text.p + a, b - a, piece_out, &out);
+            if (dl_rc[i] != LEON_OK) dl_err[i] = leon_last_error(nullptr);       // (the message is the calling thread's)
+        };
+        {
+            std::vector<std::thread> th;
+            for (uint32_t i = 1; i < n_dl; i++) th.emplace_back(download, i);
+            download(0);
+            for (auto& t : th) t.join();
+        }
+        for (uint32_t i = 0; i < n_dl; i++) {
+            if (dl_rc[i] == LEON_E_SINK) throw Exception("cannot write " + _outputFilename);
+            if (dl_rc[i] != LEON_OK) throw Exception("leon_device_download_pieces: " + dl_err[i]);
+        }
+        rt_rounds_on_device++;
+        lap(tl, t_text);
+        return true;
+    };
+    // ... and a round that found no device memory for its text: its bases (and header text) come to the host after all
+    auto round_to_host = [&](std::shared_ptr<Round> R) {
+        R->own_bases.resize(R->g_bases + 1);
+        if (leon_device_download(rt_dev, R->own_bases.data(), (const uint8_t*)R->dna->d_bases + R->base0, R->g_bases) != LEON_OK)
+            throw Exception(std::string("leon_device_download: ") + leon_last_error(nullptr));
+        if (R->hdr_in_set) {
+            uint64_t need = 0;
+            R->hdr.resize(R->d_hdr_size + 1);
+            if (leon_header_text_fetch(hdr_text_set->h, R->block0, R->nb, R->hdr.data(), R->hdr.size(), R->hdr_off.data(), &need) != LEON_OK)
+                throw Exception(std::string("header blocks: ") + leon_last_error(nullptr));
+            R->hdr_in_set = false;
+        }
+        rt_rounds_no_memory++;
+    };
     struct Drain {                                               // (no task outlives what it refers to, whatever way this function is left)
         std::vector<std::shared_future<void>> all;
         ~Drain() { for (auto& f : all) if (f.valid()) f.wait(); }
@@ -877,7 +1000,14 @@ void Leon::executeDecompression() {
         uint64_t ga_reads = 0, ga_bases = 0;
         for (uint64_t b = 0; b < na; b++) { a_reads[b] = (uint32_t)tdna[3 * (a0 + b) + 1]; a_bases[b] = tdna[3 * (a0 + b) + 2]; ga_reads += a_reads[b]; ga_bases += a_bases[b]; }
         gather(GROUP_DNA, tdna, 3, a0, na, pay, off);
-        G->bases.resize(ga_bases + 1); G->lens.reset(new uint32_t[ga_reads + 1]);
+        bool g_device = rt_device;
+        if (g_device && (leon_device_alloc(rt_dev, ga_bases + 64, &G->d_bases) != LEON_OK || leon_device_alloc(rt_dev, (ga_reads + 1) * 4, &G->d_lens) != LEON_OK)) {
+            G->release_device();                                 // no room: this call's rounds are formatted on the host
+            g_device = false;
+            rt_rounds_no_memory += (na + group - 1) / group;
+        }
+        if (!g_device) G->bases.resize(ga_bases + 1);
+        G->lens.reset(new uint32_t[ga_reads + 1]);
         std::vector<std::pair<std::shared_ptr<Round>, std::shared_future<void>>> rounds;
         uint64_t base0 = 0, read0 = 0;
         for (uint64_t g0 = a0; g0 < a1; g0 += group) {
@@ -888,6 +1018,8 @@ void Leon::executeDecompression() {
             for (uint64_t b = 0; b < nb; b++) { g_reads += R->blk_reads[b]; g_bases += R->blk_bases[b]; }
             R->read_index = read_index; R->g_reads = g_reads; R->g_bases = g_bases;
             R->dna = G; R->base0 = base0; R->read0 = read0;
+            R->on_device = g_device;
+            if (g_device) G->rounds_left++;
             if (has_header && !hdr_on_device) gather(GROUP_HEADER, thdr, 3, g0, nb, R->pay_h, R->off_h);
             R->block0 = g0;
             if (fastq_out) gather(GROUP_QUAL, tqual, 3, g0, nb, R->pay_q, R->off_q);
@@ -941,7 +1073,18 @@ void Leon::executeDecompression() {
                         return leon_host_header_decode_blocks(R->pay_h.data(), R->off_h.data(), R->blk_reads.data(), nb, first_header.data(), first_header.size(), R->hdr.data(),
                                                               R->hdr.size(), R->hdr_off.data(), &need, cores);
                     };
-                    int rc = decode();
+                    // `-record-text device` beside `-header-text device`: the round's text is used where it lies, nothing is fetched
+                    if (R->on_device && text_device) {
+                        const int rc0 = leon_header_text_device_ptr(hdr_text_set->h, R->block0, nb, &R->d_hdr, &R->d_hdr_off, &R->d_hdr_size);
+                        if (rc0 == LEON_OK) R->hdr_in_set = true;
+                        else if (rc0 == LEON_E_STATE) { host_decoder = true; hdr_blocks_fell_back += nb; }   // the kernel declined a block of the round
+                        else {
+                            const std::string msg = std::string("header blocks: ") + leon_last_error(nullptr);
+                            if (quals_beside.valid()) { try { quals_beside.get(); } catch (...) {} }
+                            throw Exception(msg);
+                        }
+                    }
+                    int rc = R->hdr_in_set ? LEON_OK : decode();
                     if (rc == LEON_E_OVERFLOW) { R->hdr.resize(need + 1); rc = decode(); }
                     if (rc != LEON_OK) {
                         const std::string msg = std::string("header blocks: ") + leon_last_error(nullptr);
@@ -963,6 +1106,10 @@ void Leon::executeDecompression() {
         lap(tl, t_read);
         // stage A, the device part
         if (dict_job.valid()) dict_job.get();
+        if (g_device)
+            check(ctx.get(), leon_dna_decode_blocks_device(ctx.get(), anchors.data(), n_anchors, pay.data(), off.data(), a_reads.data(), a_bases.data(), na,
+                                                           (uint8_t*)G->d_bases, ga_bases, (uint32_t*)G->d_lens, G->lens.get()), "leon_dna_decode_blocks_device");
+        else
         check(ctx.get(), leon_dna_decode_blocks(ctx.get(), anchors.data(), n_anchors, pay.data(), off.data(), a_reads.data(), a_bases.data(), na, G->bases.data(), ga_bases,
                                                 G->lens.get()), "leon_dna_decode_blocks");
         lap(tl, t_dna);
@@ -974,9 +1121,18 @@ void Leon::executeDecompression() {
                 host_job.get();                                  // (a failed stage B fails this round's stage C with its message)
                 if (writer_before.valid()) writer_before.get();  // file order; a failure before this round stops the rounds after it
                 const uint64_t g_reads = R->g_reads, g_bases = R->g_bases;
+                // (`-record-text device`: the call's device buffers go when its last round is written, or has failed)
+                struct Left { DnaGroup* g; ~Left() { if (g && --g->rounds_left == 0) g->release_device(); } } left{R->on_device ? R->dna.get() : nullptr};
                 // the size of this round's text: where the next round's begins
                 uint64_t n_text = 0;
-                if (has_header && !wrap && plus.exc.empty())     // (the decoder has checked that the lengths add up to the block table's bases)
+                if (R->on_device) {                              // ('+' lines of one kind; the header text may lie on the device: its size is known all the same)
+                    uint64_t hdr_total = 0, seq_total = wrap ? 0 : g_bases + g_reads;
+                    if (has_header) hdr_total = R->hdr_in_set ? R->d_hdr_size : R->hdr_off[g_reads] - R->hdr_off[0];
+                    else for (uint64_t r = 0; r < g_reads; r++) hdr_total += std::to_string(R->read_index + r).size();
+                    if (wrap) for (uint64_t r = 0; r < g_reads; r++) { const uint64_t len = R->lens()[r]; seq_total += len > wrap ? len + (len + wrap - 1) / wrap : len + 1; }
+                    n_text = 2 * g_reads + hdr_total + seq_total + (fastq_out ? 3 * g_reads + g_bases + (plus.def == 1 ? hdr_total : 0) : 0);
+                }
+                else if (has_header && !wrap && plus.exc.empty())     // (the decoder has checked that the lengths add up to the block table's bases)
                     n_text = 2 * g_reads + R->hdr_off[g_reads] + g_bases + g_reads + (fastq_out ? 3 * g_reads + g_bases : 0)
                              + (plus.def == 1 ? R->hdr_off[g_reads] : 0);      // every '+' line repeats its header
                 else {
@@ -990,6 +1146,8 @@ void Leon::executeDecompression() {
                 }
                 R->n_text = n_text; R->file_off = next_file_off;
                 next_file_off += n_text;
+                if (R->on_device && write_round_device(R)) return;
+                if (R->on_device) round_to_host(R);
                 write_round(R);
             }).share();
             drain.all.push_back(writer);
@@ -1014,6 +1172,11 @@ void Leon::executeDecompression() {
     if (_verbose && has_header)
         std::cout << "header text: " << (hdr_text_device ? "device (k_hdr_text), " + std::to_string(hdr_blocks_fell_back.load()) + " of " + std::to_string(n_blocks) + " blocks fell back to the host decoder"
                                                          : hdr_on_device ? std::string("host threads, from symbols decoded on the device") : std::string("host threads"))
+                  << std::endl;
+    if (_verbose)
+        std::cout << "record text: " << (rt_device ? "device (k_fmt_records), " + std::to_string(rt_rounds_on_device.load()) + " round(s)" +
+                                                         (rt_rounds_no_memory.load() ? ", " + std::to_string(rt_rounds_no_memory.load()) + " round(s) on the host threads for want of device memory" : std::string())
+                                                   : rt_asked ? "host threads (" + rt_reason + ")" : std::string("host threads"))
                   << std::endl;
     if (_testFile) testDecompressedFile();
 }

@@ -48,6 +48,7 @@ public:
     bool _lossless = false, _seqOnly = false, _noHeader = false, _noQual = false, _testFile = false, _verbose = false;
     std::string _qualDeflate;             // -qual-deflate host|device|auto; empty = not given: zlib on the host threads (the reference's bytes)
     std::string _headerText;              // -d: -header-text host|device|auto; empty = not given: the header text on the host threads
+    std::string _recordText;              // -d: -record-text host|device|auto; empty = not given: the records formatted on the host threads
 
 private:
     void executeCompression();
