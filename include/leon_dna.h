@@ -358,6 +358,22 @@ void leon_qual_deflate_release(void);
 int leon_host_qual_decode_blocks(const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads,
                                  const uint64_t* block_n_bytes, uint64_t n_blocks, uint8_t* out, uint64_t out_cap,
                                  uint64_t* out_off, uint32_t n_threads);
+/* The same inverse into DEVICE memory, the blocks inflated by the device (inflate_kernels.hip: k_qual_inflate, one wave per block, and
+ * a device-wide line pass).  payloads / payload_off[n_blocks + 1] / block_n_reads / block_n_bytes: HOST memory, as
+ * leon_host_qual_decode_blocks takes them.  d_quals (device, quals_cap bytes): the blocks' quality bytes back to back WITHOUT the
+ * newlines -- what leon_records_format_device takes as d_quals.  d_qual_off (device, may be NULL): total reads + 1 offsets into
+ * d_quals, [0] = 0.  d_len (device, may be NULL): when given, read r's line must have exactly d_len[r] bytes.  n_symbols (host, may
+ * be NULL): the literal/length symbols the call decoded (measurement).
+ * One decoder for every RFC 1950 / 1951 stream -- who wrote the blocks is not asked.  The verdict is the host function's on the
+ * same arguments: zlib's uncompress (header, code-length sets, codes, distances, stored lengths, a stream that ends early, the
+ * Adler-32; bytes behind the stream's end are ignored) and the line rules (exactly block_n_bytes[b] + block_n_reads[b] bytes of
+ * text, block_n_reads[b] newlines, the last byte one of them); LEON_E_INVALID "quality block N does not decode" names the smallest
+ * block that fails.  Arguments are refused before a device is touched, with the host function's words.  The call works on a stream of
+ * its own, beside a context's decode calls; its temporaries (the payloads, the text with its newlines) live for the call and are
+ * bounded by working through the blocks in launches of at most 1 024 blocks and 8 GiB of text.  Errors: leon_last_error(NULL). */
+int leon_qual_inflate_blocks_device(int device_id, const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads,
+                                    const uint64_t* block_n_bytes, uint64_t n_blocks, const uint32_t* d_len, uint8_t* d_quals,
+                                    uint64_t quals_cap, uint64_t* d_qual_off, uint64_t* n_symbols);
 
 /* Start a new output file on the same context: forgets the anchor dictionary, the dictionary stream and the
  * read/block counters (a fresh Leon object upstream); keeps the bloom and the device buffers. */

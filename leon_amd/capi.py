@@ -139,6 +139,8 @@ _EXPORTS = {
     "leon_qual_deflate_release": (None, []),
     "leon_device_trim": (None, []),
     "leon_host_qual_decode_blocks": (C.c_int, [_u8p, _u64p, _u32p, _u64p, C.c_uint64, _u8p, C.c_uint64, _u64p, C.c_uint32]),
+    "leon_qual_inflate_blocks_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                   C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
 }
 EXPORTED_SYMBOLS = tuple(_EXPORTS)
 _lib = None
@@ -281,6 +283,50 @@ def host_qual_decode_blocks(blocks, block_n_bytes, n_threads=0):
         raise LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
     raw = out.tobytes()
     return [raw[int(out_off[i]):int(out_off[i + 1])] for i in range(total)]
+
+
+def qual_inflate_blocks_device(payloads, payload_off, block_n_reads, block_n_bytes, d_quals, quals_cap, d_qual_off=0, d_len=0,
+                               device_id=0, n_blocks=None):
+    """leon_qual_inflate_blocks_device over raw pointers: payloads (bytes-like or a uint8 array, host), payload_off / block_n_reads /
+    block_n_bytes (host arrays), d_quals / d_qual_off / d_len (device pointers as integers, 0 = NULL).  Returns the literal/length
+    symbols the call decoded.  None for a host array passes NULL."""
+    lib = load_library()
+    keep = []
+
+    def host(a, dtype):
+        if a is None:
+            return C.c_void_p(0)
+        if isinstance(a, np.ndarray) and a.dtype == dtype:
+            keep.append(a)                       # as it lies (the tests pass odd addresses)
+        else:
+            keep.append(np.ascontiguousarray(np.frombuffer(bytes(a), dtype=np.uint8) if dtype == np.uint8 else a, dtype=dtype))
+        return C.c_void_p(keep[-1].ctypes.data)
+    if n_blocks is None:
+        n_blocks = len(block_n_reads)
+    n_syms = C.c_uint64()
+    rc = lib.leon_qual_inflate_blocks_device(device_id, host(payloads, np.uint8), host(payload_off, np.uint64), host(block_n_reads, np.uint32),
+                                             host(block_n_bytes, np.uint64), int(n_blocks), C.c_void_p(int(d_len)), C.c_void_p(int(d_quals)),
+                                             int(quals_cap), C.c_void_p(int(d_qual_off)), C.byref(n_syms))
+    if rc:
+        raise LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+    return n_syms.value
+
+
+def qual_inflate_blocks(blocks, block_n_bytes, device_id=0):
+    """the convenience form: blocks = [(id, zlib payload, n_reads)] -> (the quality bytes without newlines, offsets[total reads + 1]),
+    inflated on the device and brought back"""
+    pay, off, nr = _join_blocks(blocks)
+    nb = np.ascontiguousarray(block_n_bytes, dtype=np.uint64)
+    total, cap = int(nr[:len(blocks)].sum()), int(nb.sum())
+    d_q, d_o = device_alloc(cap + 64, device_id), device_alloc((total + 1) * 8, device_id)
+    try:
+        qual_inflate_blocks_device(pay, off, nr, nb, d_q, cap, d_o, 0, device_id, n_blocks=len(blocks))
+        quals = device_download(d_q, cap, device_id) if cap else b""
+        offsets = np.frombuffer(device_download(d_o, (total + 1) * 8, device_id), dtype=np.uint64) if blocks else np.zeros(1, np.uint64)
+        return quals, offsets
+    finally:
+        device_free(d_q)
+        device_free(d_o)
 
 
 def kmer_auto_cutoff(histogram):

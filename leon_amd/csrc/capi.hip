@@ -1985,6 +1985,109 @@ int leon_records_format_device(int device_id, const leon_record_layout* lay, con
     return LEON_OK;
 }
 
+// ---- quality blocks inflated on the device (inflate_kernels.hip) ----
+int leon_qual_inflate_blocks_device(int device_id, const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads,
+                                    const uint64_t* block_n_bytes, uint64_t n_blocks, const uint32_t* d_len, uint8_t* d_quals, uint64_t quals_cap,
+                                    uint64_t* d_qual_off, uint64_t* n_symbols) {
+    if (n_symbols) *n_symbols = 0;
+    if (n_blocks && (!payloads || !payload_off || !block_n_reads || !block_n_bytes || !d_quals)) return fail(nullptr, LEON_E_INVALID, "null argument");
+    if (!n_blocks) return LEON_OK;
+    if (n_blocks > (1ull << 31)) return fail(nullptr, LEON_E_INVALID, "implausible number of blocks");
+    std::vector<uint64_t> o0(n_blocks + 1, 0), r0(n_blocks + 1, 0);
+    for (uint64_t b = 0; b < n_blocks; b++) {
+        if (payload_off[b + 1] < payload_off[b]) return fail(nullptr, LEON_E_INVALID, "payload offsets are not monotonic");
+        o0[b + 1] = o0[b] + block_n_bytes[b];
+        r0[b + 1] = r0[b] + block_n_reads[b];
+        if (o0[b + 1] < o0[b] || o0[b + 1] > quals_cap) return fail(nullptr, LEON_E_INVALID, "output capacity below the sum of block_n_bytes");
+    }
+    const uint64_t total_reads = r0[n_blocks];
+    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_NO_DEVICE, "leon_qual_inflate_blocks_device: no such HIP device"); }
+    // a stream of its own: the call runs beside decode calls on the contexts' streams
+    struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
+    HIPCHK(nullptr, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    hipStream_t s = st.s;
+    // The blocks in launches of at most kMaxBlocks blocks and kMaxText bytes of temporary text (the lines WITH their newlines, every
+    // block's share 16-byte aligned): what bounds the temporaries; a launch holds at least one block.
+    constexpr uint64_t kMaxBlocks = 1024, kMaxText = 8ull << 30;
+    auto share = [&](uint64_t b) { return (block_n_bytes[b] + block_n_reads[b] + 15) & ~15ull; };
+    std::vector<uint64_t> cut{0};
+    uint64_t max_text = 0, max_pay = 0, max_tiles = 0, max_blocks = 0;
+    for (uint64_t b = 0; b < n_blocks;) {
+        uint64_t e = b, text = 0, tiles = 0;
+        while (e < n_blocks && (e == b || (e - b < kMaxBlocks && text + share(e) <= kMaxText))) {
+            text += share(e); tiles += (block_n_bytes[e] + block_n_reads[e] + 4095) / 4096; e++;
+        }
+        max_text = std::max(max_text, text); max_tiles = std::max(max_tiles, tiles); max_blocks = std::max(max_blocks, e - b);
+        max_pay = std::max(max_pay, payload_off[e] - payload_off[b]);
+        cut.push_back(e); b = e;
+    }
+    if (max_tiles >= (1ull << 31)) return fail(nullptr, LEON_E_INVALID, "implausible block sizes");
+    TmpBuf d_pay, d_text, d_blk, d_status, d_adler, d_tile_nl, d_nl_before, d_sums, d_last, d_tmp, d_cnt, d_off_own;
+    HIPCHK(nullptr, d_pay.ensure(max_pay + 64)); HIPCHK(nullptr, d_text.ensure(max_text + 64));
+    HIPCHK(nullptr, d_blk.ensure((max_blocks + 1) * sizeof(QiBlock)));
+    HIPCHK(nullptr, d_status.ensure(max_blocks * 4)); HIPCHK(nullptr, d_adler.ensure(max_blocks * 4)); HIPCHK(nullptr, d_last.ensure(max_blocks * 4));
+    HIPCHK(nullptr, d_sums.ensure(max_blocks * 16));
+    HIPCHK(nullptr, d_tile_nl.ensure((max_tiles + 1) * 4)); HIPCHK(nullptr, d_nl_before.ensure((max_tiles + 1) * 8));
+    HIPCHK(nullptr, d_cnt.ensure(16));
+    HIPCHK(nullptr, hipMemsetAsync(d_cnt.p, 0, 8, s));
+    HIPCHK(nullptr, hipMemsetAsync(d_cnt.as<uint8_t>() + 8, 0xFF, 8, s));
+    size_t tmp_bytes = 0;
+    HIPCHK(nullptr, qual_tiles_scan(nullptr, tmp_bytes, d_tile_nl.as<uint32_t>(), d_nl_before.as<uint64_t>(), max_tiles, s));
+    HIPCHK(nullptr, d_tmp.ensure(std::max<size_t>(tmp_bytes, 16)));
+    uint64_t* qual_off = d_qual_off;
+    if (!qual_off && d_len) { HIPCHK(nullptr, d_off_own.ensure((total_reads + 1) * 8)); qual_off = d_off_own.as<uint64_t>(); }   // the lengths are checked through the offsets
+    if (qual_off) HIPCHK(nullptr, hipMemsetAsync(qual_off, 0, 8, s));
+    std::vector<QiBlock> blk;
+    std::vector<uint32_t> status;
+    for (size_t g = 0; g + 1 < cut.size(); g++) {
+        const uint64_t b0 = cut[g], b1 = cut[g + 1], nb = b1 - b0, pay_bytes = payload_off[b1] - payload_off[b0];
+        blk.assign(nb + 1, QiBlock{});
+        uint64_t text = 0, tiles = 0;
+        for (uint64_t b = b0; b <= b1; b++) {
+            QiBlock& K = blk[b - b0];
+            K.text0 = text; K.tile0 = tiles;
+            if (b == b1) break;
+            K.pay0 = payload_off[b] - payload_off[b0]; K.pay_size = payload_off[b + 1] - payload_off[b];
+            K.text_size = block_n_bytes[b] + block_n_reads[b];
+            K.q0 = o0[b]; K.read0 = r0[b]; K.n_reads = block_n_reads[b];
+            text += share(b); tiles += (K.text_size + 4095) / 4096;
+        }
+        if (staged_h2d(device_id, d_pay.p, payloads + payload_off[b0], pay_bytes) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_HIP, "leon_qual_inflate_blocks_device: the payloads' copy to the device failed"); }
+        HIPCHK(nullptr, hipMemcpyAsync(d_blk.p, blk.data(), (nb + 1) * sizeof(QiBlock), hipMemcpyHostToDevice, s));
+        HIPCHK(nullptr, hipMemsetAsync(d_sums.p, 0, nb * 16, s));
+        HIPCHK(nullptr, hipMemsetAsync(d_last.p, 0, nb * 4, s));
+        HIPCHK(nullptr, hipMemsetAsync(d_tile_nl.as<uint32_t>() + tiles, 0, 4, s));
+        launch_qual_inflate(s, d_pay.as<uint32_t>(), (pay_bytes + 3) / 4, d_blk.as<QiBlock>(), (uint32_t)nb, d_text.as<uint8_t>(), d_status.as<uint32_t>(),
+                            d_adler.as<uint32_t>(), n_symbols ? d_cnt.as<unsigned long long>() : nullptr);
+        HIPCHK(nullptr, hipGetLastError());
+        launch_qual_tiles(s, d_blk.as<QiBlock>(), (uint32_t)nb, tiles, d_text.as<uint8_t>(), d_tile_nl.as<uint32_t>(), d_sums.as<unsigned long long>(), d_last.as<uint32_t>());
+        HIPCHK(nullptr, hipGetLastError());
+        HIPCHK(nullptr, qual_tiles_scan(d_tmp.p, tmp_bytes, d_tile_nl.as<uint32_t>(), d_nl_before.as<uint64_t>(), tiles, s));
+        launch_qual_check(s, d_blk.as<QiBlock>(), (uint32_t)nb, d_nl_before.as<uint64_t>(), d_sums.as<unsigned long long>(), d_last.as<uint32_t>(),
+                          d_adler.as<uint32_t>(), d_status.as<uint32_t>());
+        HIPCHK(nullptr, hipGetLastError());
+        // the blocks' status words in one small copy; the smallest failing block is the one the host way names
+        status.assign(nb, 0);
+        HIPCHK(nullptr, hipMemcpyAsync(status.data(), d_status.p, nb * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(nullptr, hipStreamSynchronize(s));
+        for (uint64_t b = 0; b < nb; b++)
+            if (status[b] != QI_OK) return fail(nullptr, LEON_E_INVALID, "quality block " + std::to_string(b0 + b) + " does not decode");
+        launch_qual_lines(s, d_blk.as<QiBlock>(), (uint32_t)nb, tiles, d_text.as<uint8_t>(), d_nl_before.as<uint64_t>(), d_quals, o0[n_blocks], qual_off, total_reads);
+        HIPCHK(nullptr, hipGetLastError());
+        HIPCHK(nullptr, hipStreamSynchronize(s));                 // the next launch reuses the temporaries (and the host's blk)
+    }
+    uint64_t words[2] = {0, ~0ull};
+    if (d_len) { launch_qual_lens(s, qual_off, d_len, 0, total_reads, d_cnt.as<unsigned long long>() + 1); HIPCHK(nullptr, hipGetLastError()); }
+    HIPCHK(nullptr, hipMemcpyAsync(words, d_cnt.p, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(nullptr, hipStreamSynchronize(s));
+    if (n_symbols) *n_symbols = words[0];
+    if (words[1] != ~0ull) {
+        const uint64_t b = (uint64_t)(std::upper_bound(r0.begin(), r0.end(), words[1]) - r0.begin()) - 1;
+        return fail(nullptr, LEON_E_INVALID, "read " + std::to_string(words[1]) + " (quality block " + std::to_string(b) + "): the quality line's length is not the one given (d_len)");
+    }
+    return LEON_OK;
+}
+
 int leon_device_download_pieces(int device_id, const void* d_src, uint64_t bytes, leon_piece_sink sink, void* user) {
     if (!sink || (bytes && !d_src)) return fail(nullptr, LEON_E_INVALID, "leon_device_download_pieces: null argument");
     if (!bytes) return LEON_OK;

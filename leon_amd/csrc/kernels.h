@@ -213,4 +213,25 @@ void launch_fmt_rec_off(hipStream_t s, const FmtPair* off, uint64_t n_reads, uin
 void launch_fmt_records(hipStream_t s, const FmtLayout& L, const FmtPair* off, const uint64_t* hdr_off, uint64_t n_reads, const uint8_t* bases,
                         const uint8_t* hdr, const uint8_t* quals, uint8_t* text, uint64_t text_size);
 
+// ---- quality blocks inflated on the device (inflate_kernels.hip), DESIGN.md 4.10 ----
+// a block of one launch: its payload in the launch's payload buffer, its share of the temporary text (16-byte aligned, text_size =
+// its quality bytes + its reads: the lines with their newlines), its first 4 KiB tile of the text, its place in d_quals and d_qual_off
+struct QiBlock { uint64_t pay0, pay_size, text0, text_size, tile0, q0, read0, n_reads; };
+enum : uint32_t { QI_OK = 0, QI_HEADER = 1, QI_TYPE = 2, QI_STORED = 3, QI_TABLE = 4, QI_CODE = 5, QI_DIST = 6, QI_LONG = 7, QI_EARLY = 8,
+                  QI_SHORT = 9, QI_LINES = 10, QI_ADLER = 11 };
+// one wave per block; status[b] = QI_OK or why the stream was refused, adler_expect[b] = the stream's own checksum; n_syms: nullptr,
+// or a counter of the literal/length symbols decoded (measurement)
+void launch_qual_inflate(hipStream_t s, const uint32_t* pay, uint64_t pay_words, const QiBlock* blk /* n_blocks + 1 */, uint32_t n_blocks, uint8_t* text,
+                         uint32_t* status, uint32_t* adler_expect, unsigned long long* n_syms);
+// per 4 KiB tile of the text: its newlines; per block (zeroed by the caller): the two Adler-32 sums, whether the last byte is a newline
+void launch_qual_tiles(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, uint64_t n_tiles, const uint8_t* text, uint32_t* tile_nl /* n_tiles + 1, the last 0 */,
+                       unsigned long long* sums, uint32_t* last_nl);
+hipError_t qual_tiles_scan(void* tmp, size_t& bytes, const uint32_t* tile_nl, uint64_t* nl_before, uint64_t n_tiles, hipStream_t s);   // exclusive, n_tiles + 1 entries
+void launch_qual_check(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, const uint64_t* nl_before, const unsigned long long* sums,
+                       const uint32_t* last_nl, const uint32_t* adler_expect, uint32_t* status);
+// the text without its newlines and the reads' offsets; only after every status of the launch is QI_OK
+void launch_qual_lines(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, uint64_t n_tiles, const uint8_t* text, const uint64_t* nl_before,
+                       uint8_t* quals, uint64_t quals_end, uint64_t* qual_off, uint64_t total_reads);
+void launch_qual_lens(hipStream_t s, const uint64_t* qual_off, const uint32_t* len, uint64_t read0, uint64_t n, unsigned long long* bad_read /* ~0 before */);
+
 }  // namespace leon

@@ -199,6 +199,22 @@ RecordText record_text_choice(const std::string& flag) {
 // (18.1-20.8 s against 17.6-22.9).  Ahead on average everywhere, but there is no block count FROM which it was ahead in every pair, and
 // that is the rule `auto` follows (as kHeaderTextAutoBlocks does): `auto` = `host` until a measurement says otherwise.
 constexpr uint64_t kRecordTextAutoBlocks = ~0ull;
+// Who inflates the quality blocks of `-d`.  Not given, or `host`: zlib on the host threads (leon_host_qual_decode_blocks).  `device`:
+// leon_qual_inflate_blocks_device, per round, beside the DNA decode -- under `-record-text device` straight into the device buffer the
+// formatter reads (the round's upload of the inflated qualities disappears; the reads' offsets, 8 bytes each, come to the host for the
+// check that a read's quality and sequence lengths agree), otherwise into a buffer that is downloaded into the round's host arrays.
+// A round for which the device has no memory is inflated on the host.  The restored file is the same bytes whichever way.
+enum class QualInflate { Host, Device, Auto };
+QualInflate qual_inflate_choice(const std::string& flag) {
+    if (flag.empty() || flag == "host") return QualInflate::Host;
+    if (flag == "device") return QualInflate::Device;
+    if (flag == "auto") return QualInflate::Auto;
+    throw Exception("option -qual-inflate: '" + flag + "': expected host, device or auto");
+}
+// The rule of kHeaderTextAutoBlocks: the smallest measured block count FROM which `device` was ahead of `host` in every alternating
+// pair.  No such count has been measured (profiles/README.md, "qual_inflate": the command's runs at the three sizes are still to be
+// made), so `auto` = `host` until a measurement says otherwise.
+constexpr uint64_t kQualInflateAutoBlocks = ~0ull;
 size_t deflated_size(const std::string& text, int strategy) {
     z_stream z{};
     if (deflateInit2(&z, Z_DEFAULT_COMPRESSION, Z_DEFLATED, 15, 8, strategy) != Z_OK) return 0;
@@ -255,6 +271,7 @@ void Leon::run(int argc, char* argv[]) {
             else if (a == "-qual-deflate") { _qualDeflate = need("-qual-deflate"); (void)qual_encoder_choice(_qualDeflate); }
             else if (a == "-header-text") { _headerText = need("-header-text"); (void)header_text_choice(_headerText); }
             else if (a == "-record-text") { _recordText = need("-record-text"); (void)record_text_choice(_recordText); }
+            else if (a == "-qual-inflate") { _qualInflate = need("-qual-inflate"); (void)qual_inflate_choice(_qualInflate); }
             else throw Exception("unknown option " + a);
         }
         if (_inputFilename.empty()) throw Exception("option -file is mandatory");
@@ -718,6 +735,10 @@ void Leon::executeDecompression() {
     const bool rt_device = rt_asked && rt_reason.empty();
     const int rt_dev = device_for(0);
     std::atomic<uint64_t> rt_rounds_on_device{0}, rt_rounds_no_memory{0};
+    // `-qual-inflate`: the quality blocks inflated on the device
+    const QualInflate qi_choice = qual_inflate_choice(_qualInflate);
+    const bool qi_device = fastq_out && n_blocks > 0 && (qi_choice == QualInflate::Device || (qi_choice == QualInflate::Auto && n_blocks >= kQualInflateAutoBlocks));
+    std::atomic<uint64_t> qi_rounds_on_device{0}, qi_rounds_no_memory{0};
 
     // Blocks decoded per round.  A round costs the device ONE block's serial chain whatever the number of blocks in it (up to
     // a few thousand: one wave per block), so rounds should be large; up to five are alive at a time (see the stages below), each
@@ -764,6 +785,9 @@ void Leon::executeDecompression() {
         std::vector<uint64_t> off_h, off_q, blk_bases;
         std::vector<uint32_t> blk_reads;
         std::vector<uint64_t> hdr_off, qual_off;
+        void* d_qual = nullptr;                                  // `-qual-inflate device` under `-record-text device`: the qualities, inflated where the formatter reads them
+        void release_quals() { leon_device_free(d_qual); d_qual = nullptr; }
+        ~Round() { release_quals(); }
     };
     std::unique_ptr<char[]> text;                                // the writing stage's records (never zero-filled)
     uint64_t text_cap = 0;
@@ -870,10 +894,11 @@ void Leon::executeDecompression() {
             if (leon_device_upload(rt_dev, d, src, n) != LEON_OK) throw Exception(std::string("leon_device_upload: ") + leon_last_error(nullptr));
         };
         if (leon_device_alloc(rt_dev, n_text + 64, &d_text.p) != LEON_OK) return false;
-        if (fastq_out) {
+        if (fastq_out && !R->d_qual) {
             if (leon_device_alloc(rt_dev, g_bases + 64, &d_qual.p) != LEON_OK) return false;
             upload(d_qual.p, R->qual.data(), g_bases);
         }
+        const uint8_t* const quals = (const uint8_t*)(R->d_qual ? R->d_qual : d_qual.p);
         const uint8_t* hp = nullptr; const uint64_t* ho = nullptr;
         uint64_t hb = 0;
         if (has_header && R->hdr_in_set) { hp = R->d_hdr; ho = R->d_hdr_off; hb = R->d_hdr_size; }
@@ -889,9 +914,10 @@ void Leon::executeDecompression() {
         lay.wrap = (uint32_t)std::min<uint64_t>(wrap, 0xFFFFFFFFull); lay.first_read_index = R->read_index; lay.hdr_bytes = hb;
         uint64_t size = 0;
         const int rc = leon_records_format_device(rt_dev, &lay, (const uint8_t*)R->dna->d_bases + R->base0, (const uint32_t*)R->dna->d_lens + R->read0, g_reads, g_bases,
-                                                  hp, ho, (const uint8_t*)d_qual.p, (uint8_t*)d_text.p, n_text, nullptr, &size);
+                                                  hp, ho, quals, (uint8_t*)d_text.p, n_text, nullptr, &size);
         if (rc == LEON_E_OVERFLOW || (rc == LEON_OK && size != n_text)) throw Exception(_inputFilename + ": the decoded reads do not add up to their blocks' sizes");
         if (rc != LEON_OK) throw Exception(std::string("leon_records_format_device: ") + leon_last_error(nullptr));
+        R->release_quals();
         // the text comes back in pinned pieces, each pwritten where it landed; a download keeps up to three copies in flight (PCIe's
         // rate), the page cache takes more writers than that: four downloads side by side, each its own quarter of the text
         struct Out { int fd; uint64_t at; };
@@ -939,6 +965,11 @@ void Leon::executeDecompression() {
             if (leon_header_text_fetch(hdr_text_set->h, R->block0, R->nb, R->hdr.data(), R->hdr.size(), R->hdr_off.data(), &need) != LEON_OK)
                 throw Exception(std::string("header blocks: ") + leon_last_error(nullptr));
             R->hdr_in_set = false;
+        }
+        if (R->d_qual) {                                         // (`-qual-inflate device`: so do its qualities)
+            R->qual.resize(R->g_bases + 1);
+            if (leon_device_download(rt_dev, R->qual.data(), R->d_qual, R->g_bases) != LEON_OK) throw Exception(std::string("leon_device_download: ") + leon_last_error(nullptr));
+            R->release_quals();
         }
         rt_rounds_no_memory++;
     };
@@ -1033,7 +1064,29 @@ void Leon::executeDecompression() {
                 const uint64_t nb = R->nb, g_bases = R->g_bases;
                 const bool on_device = hdr_on_device;
                 const bool text_device = hdr_text_device;
+                // `-qual-inflate device`: false when the device has no memory for the round (nothing done: the host threads inflate it)
+                auto inflate_on_device = [&]() -> bool {
+                    struct Dev { void* p = nullptr; ~Dev() { leon_device_free(p); } } d_q, d_off;
+                    if (leon_device_alloc(rt_dev, g_bases + 64, &d_q.p) != LEON_OK || leon_device_alloc(rt_dev, (R->g_reads + 1) * 8, &d_off.p) != LEON_OK) return false;
+                    const int rc = leon_qual_inflate_blocks_device(rt_dev, R->pay_q.data(), R->off_q.data(), R->blk_reads.data(), R->blk_bases.data(), nb, nullptr,
+                                                                   (uint8_t*)d_q.p, g_bases, (uint64_t*)d_off.p, nullptr);
+                    if (rc == LEON_E_HIP && std::string(leon_last_error(nullptr)).find("out of memory") != std::string::npos) return false;   // (its temporaries)
+                    if (rc != LEON_OK) throw Exception(std::string("leon_qual_inflate_blocks_device: ") + leon_last_error(nullptr));
+                    // the reads' offsets come to the host: the check that a read's quality and sequence lengths agree is the writing stage's
+                    if (leon_device_download(rt_dev, R->qual_off.data(), d_off.p, (R->g_reads + 1) * 8) != LEON_OK) throw Exception(std::string("leon_device_download: ") + leon_last_error(nullptr));
+                    if (R->on_device) { R->d_qual = d_q.p; d_q.p = nullptr; }
+                    else {
+                        R->qual.resize(g_bases + 1);
+                        if (leon_device_download(rt_dev, R->qual.data(), d_q.p, g_bases) != LEON_OK) throw Exception(std::string("leon_device_download: ") + leon_last_error(nullptr));
+                    }
+                    qi_rounds_on_device++;
+                    return true;
+                };
                 auto decode_quals = [&] {
+                    if (qi_device) {
+                        if (inflate_on_device()) return;
+                        qi_rounds_no_memory++;
+                    }
                     R->qual.resize(g_bases + 1);
                     if (leon_host_qual_decode_blocks(R->pay_q.data(), R->off_q.data(), R->blk_reads.data(), R->blk_bases.data(), nb, R->qual.data(), g_bases, R->qual_off.data(), cores) != LEON_OK)
                         throw Exception(std::string("leon_host_qual_decode_blocks: ") + leon_last_error(nullptr));
@@ -1177,6 +1230,11 @@ void Leon::executeDecompression() {
         std::cout << "record text: " << (rt_device ? "device (k_fmt_records), " + std::to_string(rt_rounds_on_device.load()) + " round(s)" +
                                                          (rt_rounds_no_memory.load() ? ", " + std::to_string(rt_rounds_no_memory.load()) + " round(s) on the host threads for want of device memory" : std::string())
                                                    : rt_asked ? "host threads (" + rt_reason + ")" : std::string("host threads"))
+                  << std::endl;
+    if (_verbose && fastq_out)
+        std::cout << "quality blocks: " << (qi_device ? "device (k_qual_inflate), " + std::to_string(qi_rounds_on_device.load()) + " round(s)" +
+                                                            (qi_rounds_no_memory.load() ? ", " + std::to_string(qi_rounds_no_memory.load()) + " round(s) on the host threads for want of device memory" : std::string())
+                                                      : std::string("host threads"))
                   << std::endl;
     if (_testFile) testDecompressedFile();
 }

@@ -49,6 +49,7 @@ public:
     std::string _qualDeflate;             // -qual-deflate host|device|auto; empty = not given: zlib on the host threads (the reference's bytes)
     std::string _headerText;              // -d: -header-text host|device|auto; empty = not given: the header text on the host threads
     std::string _recordText;              // -d: -record-text host|device|auto; empty = not given: the records formatted on the host threads
+    std::string _qualInflate;             // -d: -qual-inflate host|device|auto; empty = not given: the quality blocks inflated by zlib on the host threads
 
 private:
     void executeCompression();
