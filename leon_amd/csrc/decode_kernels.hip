@@ -710,6 +710,7 @@ __global__ void __launch_bounds__(64) k_hdr_decode_symbols(const uint8_t* payloa
 void launch_hdr_decode_symbols(hipStream_t s, const uint8_t* payloads, const uint64_t* pay_off, const uint32_t* blk_reads, uint64_t n_blocks,
                                uint8_t* syms, const uint64_t* sym_begin, unsigned long long* sym_count, int* err) {
     if (!n_blocks) return;
+    // (grid cap 256 * 8 blocks: tests/many_blocks.py's N_BLOCKS must stay above twice that, so that a wave takes a second trip)
     const uint32_t g = (uint32_t)(n_blocks > 256 * 8 ? 256 * 8 : n_blocks);
     hipLaunchKernelGGL(k_hdr_decode_symbols, dim3(g), dim3(64), 0, s, payloads, pay_off, blk_reads, n_blocks, syms, sym_begin, sym_count, err);
 }
@@ -989,6 +990,7 @@ void launch_hdr_text(hipStream_t s, const uint8_t* syms, const uint64_t* sym_beg
                      const uint64_t* read0, const uint64_t* text_begin, uint64_t n_blocks, const uint8_t* first, uint32_t first_len,
                      uint8_t* text, uint64_t* off, uint32_t* status, uint64_t* text_size) {
     if (!n_blocks) return;
+    // (grid cap 256 * 8 blocks: tests/many_blocks.py's N_BLOCKS must stay above twice that, so that a wave takes a second trip)
     const uint32_t g = (uint32_t)(n_blocks > 256 * 8 ? 256 * 8 : n_blocks);
     if (text) hipLaunchKernelGGL(k_hdr_text<true>, dim3(g), dim3(64), 0, s, syms, sym_begin, sym_count, blk_reads, read0, text_begin, n_blocks, first, first_len, text, off, status, text_size);
     else hipLaunchKernelGGL(k_hdr_text<false>, dim3(g), dim3(64), 0, s, syms, sym_begin, sym_count, blk_reads, read0, text_begin, n_blocks, first, first_len, text, off, status, text_size);
@@ -1020,6 +1022,7 @@ void launch_decode_blocks(hipStream_t s, BloomDev B, PathCache C, const uint16_t
                           const uint64_t* blk_out0, uint64_t n_blocks, uint8_t* out, uint32_t* out_len, uint32_t* scratch,
                           uint32_t* pool, unsigned long long* pool_cursor, uint64_t pool_words, int* err, unsigned long long* stats) {
     if (!n_blocks) return;
+    // (grid cap 256 * 8 blocks: tests/many_blocks.py's N_BLOCKS must stay above twice that, so that a wave takes a second trip)
     const uint32_t g = (uint32_t)(n_blocks > 256 * 8 ? 256 * 8 : n_blocks);   // 8 waves per CU: the kernel's registers allow two per SIMD
     static const char* force = getenv("LEON_DC_DEEP");       // measurement override
     const bool deep = force ? force[0] == '1' : true;        // 21 probe sets per round and wave: measured better at 200 and at 2 000 blocks

@@ -559,6 +559,7 @@ __global__ void __launch_bounds__(256) k_rc_records4(const uint8_t* syms, const 
 void launch_rc_records(hipStream_t s, const uint8_t* syms, const uint64_t* blk_begin, uint64_t n_blocks, uint32_t tile0, uint32_t tile1, uint64_t* recs,
                        const uint64_t* rec_off, uint32_t* state, uint32_t* model_scratch, int* err, uint32_t small_sizes) {
     if (!n_blocks || tile0 >= tile1) return;
+    // (grid cap 256 * 4 blocks: tests/many_blocks.py's N_BLOCKS must stay above twice that, so that a workgroup takes a second trip)
     static const bool one_wave = [] { const char* e = getenv("LEON_RC_RECORDS_WAVES"); return e && atoi(e) == 1; }();     // (measurement: the round-4 kernel)
     if (one_wave) hipLaunchKernelGGL(k_rc_records, dim3((uint32_t)std::min<uint64_t>(n_blocks, 256 * 4)), dim3(64), 0, s, syms, blk_begin, n_blocks, tile0, tile1, recs, rec_off,
                                      state, model_scratch, err, small_sizes);
@@ -575,6 +576,7 @@ void launch_rc_encode(hipStream_t s, const uint8_t* syms, const uint64_t* blk_be
     uint32_t G = per_cu <= 1 ? 1u : per_cu <= 2 ? 2u : per_cu <= 4 ? 4u : 8u;
     if (force) { int v = atoi(force); if (v == 1 || v == 2 || v == 4 || v == 8) G = (uint32_t)v; }
     const uint64_t n_groups = (n_blocks + G - 1) / G;
+    // (grid cap 256 * (8 / G) groups = 2048 blocks for every G: tests/many_blocks.py's N_BLOCKS must stay above twice that)
     const uint32_t g = (uint32_t)std::min<uint64_t>(n_groups, 256ull * (8 / G));
     // totals at which the coder switches to the exact division (test hook: a low value sends ordinary data down that path)
     uint32_t fast_total = RC_MAX_TOTAL;
