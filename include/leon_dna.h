@@ -375,6 +375,18 @@ int leon_qual_inflate_blocks_device(int device_id, const uint8_t* payloads, cons
                                     const uint64_t* block_n_bytes, uint64_t n_blocks, const uint32_t* d_len, uint8_t* d_quals,
                                     uint64_t quals_cap, uint64_t* d_qual_off, uint64_t* n_symbols);
 
+/* -- block checksums: zlib's CRC-32 of segments of one buffer --
+ * Segment s is bytes[seg_off[s] .. seg_off[s + 1]); crc[s] = what zlib's crc32() gives for it (reflected polynomial 0xEDB88320,
+ * initial value and final XOR 0xFFFFFFFF; an empty segment gives 0).  seg_off (n_seg + 1 entries) and crc (n_seg) are HOST memory in
+ * both forms.  Bytes outside [seg_off[0], seg_off[n_seg]) are never read.  Both forms refuse, before anything is touched, with
+ * LEON_E_INVALID and the same words: null pointers with non-zero counts, offsets that run backwards, seg_off[n_seg] > n_bytes.
+ * n_seg == 0 and segments that are all empty are LEON_OK.  Errors: leon_last_error(NULL).
+ * The device form takes d_bytes in DEVICE memory (no alignment asked), works on a stream of its own beside calls on any context and
+ * is complete on return; its temporaries (the offsets, 4 bytes per segment) live for the call (crc_kernels.hip: k_crc32_tiles). */
+int leon_crc32_segments_device(int device_id, const uint8_t* d_bytes, uint64_t n_bytes, const uint64_t* seg_off, uint64_t n_seg, uint32_t* crc);
+/* zlib's crc32 on n_threads host threads (0 = all this process may use); needs no GPU */
+int leon_host_crc32_segments(const uint8_t* bytes, uint64_t n_bytes, const uint64_t* seg_off, uint64_t n_seg, uint32_t n_threads, uint32_t* crc);
+
 /* Start a new output file on the same context: forgets the anchor dictionary, the dictionary stream and the
  * read/block counters (a fresh Leon object upstream); keeps the bloom and the device buffers. */
 int leon_dna_reset_stream(leon_dna_ctx* ctx);

@@ -141,6 +141,8 @@ _EXPORTS = {
     "leon_host_qual_decode_blocks": (C.c_int, [_u8p, _u64p, _u32p, _u64p, C.c_uint64, _u8p, C.c_uint64, _u64p, C.c_uint32]),
     "leon_qual_inflate_blocks_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                    C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "leon_crc32_segments_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "leon_host_crc32_segments": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_EXPORTS)
 _lib = None
@@ -327,6 +329,40 @@ def qual_inflate_blocks(blocks, block_n_bytes, device_id=0):
     finally:
         device_free(d_q)
         device_free(d_o)
+
+
+def _crc32_args(seg_off, n_seg):
+    """seg_off (None = NULL) as a uint64 array, the count of segments and the host words the call fills"""
+    off = None if seg_off is None else np.ascontiguousarray(seg_off, dtype=np.uint64)
+    if n_seg is None:
+        n_seg = 0 if off is None else max(len(off) - 1, 0)
+    return off, int(n_seg), np.zeros(max(int(n_seg), 1), dtype=np.uint32)
+
+
+def crc32_segments_device(d_bytes, n_bytes, seg_off, device_id=0, n_seg=None, null_crc=False):
+    """leon_crc32_segments_device: zlib's CRC-32 of every segment [seg_off[s], seg_off[s + 1]) of the n_bytes at the device pointer
+    d_bytes (an integer, 0 = NULL), as a uint32 array.  seg_off is a host array (None passes NULL, as null_crc does for the result)."""
+    lib = load_library()
+    off, n_seg, crc = _crc32_args(seg_off, n_seg)
+    rc = lib.leon_crc32_segments_device(device_id, C.c_void_p(int(d_bytes)), int(n_bytes), C.c_void_p(0 if off is None else off.ctypes.data), n_seg,
+                                        C.c_void_p(0 if null_crc else crc.ctypes.data))
+    if rc:
+        raise LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+    return crc[:n_seg]
+
+
+def host_crc32_segments(data, seg_off, n_threads=0, n_bytes=None, n_seg=None, null_crc=False):
+    """leon_host_crc32_segments (no GPU): data is bytes-like or a uint8 array (None passes NULL), the rest as crc32_segments_device"""
+    lib = load_library()
+    buf = None if data is None else (data if isinstance(data, np.ndarray) and data.dtype == np.uint8 else np.frombuffer(bytes(data) + b"\0", dtype=np.uint8))
+    if n_bytes is None:
+        n_bytes = 0 if data is None else len(data)
+    off, n_seg, crc = _crc32_args(seg_off, n_seg)
+    rc = lib.leon_host_crc32_segments(C.c_void_p(0 if buf is None else buf.ctypes.data), int(n_bytes), C.c_void_p(0 if off is None else off.ctypes.data),
+                                      n_seg, n_threads, C.c_void_p(0 if null_crc else crc.ctypes.data))
+    if rc:
+        raise LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+    return crc[:n_seg]
 
 
 def kmer_auto_cutoff(histogram):

@@ -2088,6 +2088,31 @@ int leon_qual_inflate_blocks_device(int device_id, const uint8_t* payloads, cons
     return LEON_OK;
 }
 
+// ---- zlib's CRC-32 of segments of a device buffer (crc_kernels.hip) ----
+extern "C++" { namespace leon {                                // (host_streams.cpp)
+const char* crc32_segments_refusal(const uint8_t* bytes, uint64_t n_bytes, const uint64_t* seg_off, uint64_t n_seg, const uint32_t* crc);
+} }
+int leon_crc32_segments_device(int device_id, const uint8_t* d_bytes, uint64_t n_bytes, const uint64_t* seg_off, uint64_t n_seg, uint32_t* crc) {
+    if (const char* why = crc32_segments_refusal(d_bytes, n_bytes, seg_off, n_seg, crc)) return fail(nullptr, LEON_E_INVALID, why);
+    if (!n_seg) return LEON_OK;
+    const uint64_t n_tiles = crc32_tile_count(d_bytes, seg_off[0], seg_off[n_seg]);
+    if (!n_tiles) { memset(crc, 0, n_seg * sizeof(uint32_t)); return LEON_OK; }      // nothing but empty segments: no device is asked
+    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_NO_DEVICE, "leon_crc32_segments_device: no such HIP device"); }
+    // a stream of its own: the call runs beside calls on the contexts' streams
+    struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
+    HIPCHK(nullptr, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    hipStream_t s = st.s;
+    TmpBuf d_off, d_acc;
+    HIPCHK(nullptr, d_off.ensure((n_seg + 1) * sizeof(uint64_t))); HIPCHK(nullptr, d_acc.ensure(n_seg * sizeof(uint32_t)));
+    HIPCHK(nullptr, hipMemcpyAsync(d_off.p, seg_off, (n_seg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    HIPCHK(nullptr, hipMemsetAsync(d_acc.p, 0, n_seg * sizeof(uint32_t), s));
+    launch_crc32_segments(s, d_bytes, d_off.as<uint64_t>(), n_seg, n_tiles, d_acc.as<uint32_t>());
+    HIPCHK(nullptr, hipGetLastError());
+    HIPCHK(nullptr, hipMemcpyAsync(crc, d_acc.p, n_seg * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(nullptr, hipStreamSynchronize(s));
+    return LEON_OK;
+}
+
 int leon_device_download_pieces(int device_id, const void* d_src, uint64_t bytes, leon_piece_sink sink, void* user) {
     if (!sink || (bytes && !d_src)) return fail(nullptr, LEON_E_INVALID, "leon_device_download_pieces: null argument");
     if (!bytes) return LEON_OK;

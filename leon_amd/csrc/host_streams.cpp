@@ -356,3 +356,40 @@ int leon_host_qual_decode_blocks(const uint8_t* payloads, const uint64_t* payloa
 }
 
 }  // extern "C"
+
+// ---- zlib's CRC-32 of segments of a buffer: the host form of leon_crc32_segments_device ----
+namespace leon {
+// what both forms refuse, in the same words; nullptr: the arguments are in order.  Reads seg_off only.
+const char* crc32_segments_refusal(const uint8_t* bytes, uint64_t n_bytes, const uint64_t* seg_off, uint64_t n_seg, const uint32_t* crc) {
+    if (!n_seg) return nullptr;
+    if (!seg_off || !crc) return "crc32 segments: null argument";
+    for (uint64_t s = 0; s < n_seg; s++)
+        if (seg_off[s + 1] < seg_off[s]) return "crc32 segments: segment offsets are not monotonic";
+    if (seg_off[n_seg] > n_bytes) return "crc32 segments: the segments end behind the bytes given";
+    if (n_bytes >> 62) return "crc32 segments: implausible sizes";
+    if (seg_off[n_seg] > seg_off[0] && !bytes) return "crc32 segments: null argument";
+    return nullptr;
+}
+}  // namespace leon
+
+int leon_host_crc32_segments(const uint8_t* bytes, uint64_t n_bytes, const uint64_t* seg_off, uint64_t n_seg, uint32_t n_threads, uint32_t* crc) {
+    if (const char* why = leon::crc32_segments_refusal(bytes, n_bytes, seg_off, n_seg, crc)) return fail(LEON_E_INVALID, why);
+    // pieces of at most 4 MiB, so that one long segment is shared among the threads too; zlib's crc32_combine joins them
+    constexpr uint64_t kPiece = 4ull << 20;
+    struct Piece { uint64_t at, size; uint32_t crc; };
+    std::vector<Piece> pieces;
+    std::vector<uint64_t> first(n_seg + 1, 0);
+    for (uint64_t s = 0; s < n_seg; s++) {
+        for (uint64_t at = seg_off[s]; at < seg_off[s + 1]; at += kPiece) pieces.push_back(Piece{at, std::min(kPiece, seg_off[s + 1] - at), 0});
+        first[s + 1] = pieces.size();
+    }
+    parallel_blocks(pieces.size(), n_threads, [&](uint64_t i) {
+        pieces[i].crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), bytes + pieces[i].at, (uInt)pieces[i].size);
+    });
+    for (uint64_t s = 0; s < n_seg; s++) {
+        uLong c = crc32(0L, Z_NULL, 0);
+        for (uint64_t i = first[s]; i < first[s + 1]; i++) c = i == first[s] ? pieces[i].crc : crc32_combine(c, pieces[i].crc, (z_off_t)pieces[i].size);
+        crc[s] = (uint32_t)c;
+    }
+    return LEON_OK;
+}

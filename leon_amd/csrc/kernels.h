@@ -234,4 +234,11 @@ void launch_qual_lines(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, uin
                        uint8_t* quals, uint64_t quals_end, uint64_t* qual_off, uint64_t total_reads);
 void launch_qual_lens(hipStream_t s, const uint64_t* qual_off, const uint32_t* len, uint64_t read0, uint64_t n, unsigned long long* bad_read /* ~0 before */);
 
+// ---- zlib's CRC-32 of segments of a device buffer (crc_kernels.hip), DESIGN.md 4.11 ----
+constexpr uint64_t CRC32_MAX_GROUPS = 4096;                    // the grid's cap: a workgroup walks ceil(tiles / cap) consecutive tiles
+// the 4 KiB tiles (cut at 16-byte aligned addresses) that hold bytes[first .. last)
+uint64_t crc32_tile_count(const uint8_t* bytes, uint64_t first, uint64_t last);
+// off[n_seg + 1] (device); acc[n_seg] zeroed by the caller, holds every segment's CRC-32 afterwards
+void launch_crc32_segments(hipStream_t s, const uint8_t* bytes, const uint64_t* off, uint64_t n_seg, uint64_t n_tiles, uint32_t* acc);
+
 }  // namespace leon

@@ -215,6 +215,22 @@ QualInflate qual_inflate_choice(const std::string& flag) {
 // pair.  No such count has been measured (profiles/README.md, "qual_inflate": the command's runs at the three sizes are still to be
 // made), so `auto` = `host` until a measurement says otherwise.
 constexpr uint64_t kQualInflateAutoBlocks = ~0ull;
+// Block checksums (`-c -checksum`, verified by `-d`: DESIGN.md 4.11): zlib's CRC-32 per read block and stream, taken where the bytes lie
+// -- leon_crc32_segments_device for bytes in device memory, leon_host_crc32_segments on the host threads for the rest.
+// block_off: nb + 1 offsets into the bytes, one segment per block; sums: nb words.
+void sums_on_device(int device, const void* d_bytes, uint64_t n_bytes, const uint64_t* block_off, uint64_t nb, uint32_t* sums) {
+    check(nullptr, leon_crc32_segments_device(device, static_cast<const uint8_t*>(d_bytes), n_bytes, block_off, nb, sums), "leon_crc32_segments_device");
+}
+void sums_on_host(const void* bytes, uint64_t n_bytes, const uint64_t* block_off, uint64_t nb, uint32_t cores, uint32_t* sums) {
+    check(nullptr, leon_host_crc32_segments(static_cast<const uint8_t*>(bytes), n_bytes, block_off, nb, cores, sums), "leon_host_crc32_segments");
+}
+// every rpb-th of a batch's per-read offsets (and the last): the batch's blocks
+std::vector<uint64_t> block_offsets(const uint64_t* off, uint64_t n_reads, uint64_t rpb) {
+    std::vector<uint64_t> b;
+    for (uint64_t r = 0; r < n_reads; r += rpb) b.push_back(off[r]);
+    b.push_back(off[n_reads]);
+    return b;
+}
 size_t deflated_size(const std::string& text, int strategy) {
     z_stream z{};
     if (deflateInit2(&z, Z_DEFAULT_COMPRESSION, Z_DEFLATED, 15, 8, strategy) != Z_OK) return 0;
@@ -268,6 +284,8 @@ void Leon::run(int argc, char* argv[]) {
             else if (a == "-noheader") _noHeader = true;
             else if (a == "-noqual") _noQual = true;
             else if (a == "-test-file") _testFile = true;
+            else if (a == "-checksum") _checksum = true;
+            else if (a == "-ignore-checksum") _ignoreChecksum = true;
             else if (a == "-qual-deflate") { _qualDeflate = need("-qual-deflate"); (void)qual_encoder_choice(_qualDeflate); }
             else if (a == "-header-text") { _headerText = need("-header-text"); (void)header_text_choice(_headerText); }
             else if (a == "-record-text") { _recordText = need("-record-text"); (void)record_text_choice(_recordText); }
@@ -276,6 +294,8 @@ void Leon::run(int argc, char* argv[]) {
         }
         if (_inputFilename.empty()) throw Exception("option -file is mandatory");
         if (_compress == _decompress) throw Exception("choose one of -c (compress) or -d (decompress)");
+        if (_checksum && _decompress) throw Exception("option -checksum belongs to -c: -d verifies whenever the container holds checksums (-ignore-checksum to go on past a mismatch)");
+        if (_ignoreChecksum && _compress) throw Exception("option -ignore-checksum belongs to -d");
         if (_seqOnly) _noHeader = _noQual = true;             // "same as -noheader -noqual", /root/reference/README.md:56
         execute();
     } catch (const Exception&) {
@@ -341,6 +361,11 @@ void Leon::executeCompression() {
     std::future<uint64_t> parsing = std::async(std::launch::async, parse_next, &buffers[0]);
     struct ParseJoin { std::future<uint64_t>& f; ~ParseJoin() { if (f.valid()) { try { f.get(); } catch (...) {} } } } parse_join{parsing};   // (never left running over dead buffers)
     double w_reader = 0, w_headers = 0, w_quals = 0, w_uploads = 0;   // where the pass's own thread spent its time (-verbose)
+    // `-checksum`: a CRC-32 per read block and stream (leon/metadata/checksums), each taken where the bytes lie.  The headers' are taken
+    // on the host threads by a job of their own, beside the next batch's parsing: this thread is the pass's bottleneck.
+    const bool checksum = _checksum;
+    std::vector<uint32_t> sum_dna, sum_hdr, sum_qual;            // per block; the jobs of a batch fill their blocks' words
+    std::future<void> hdr_sum_job;                               // (reads the batch's buffer in place, like qual_job: joined before the reader gets it back)
     for (uint32_t cur = 0;; cur ^= 1) {
         auto t_w = std::chrono::steady_clock::now();
         const uint64_t got = parsing.get();                      // (the reader's exceptions surface here)
@@ -351,10 +376,23 @@ void Leon::executeCompression() {
         // before the reader is allowed to fill it again
         t_w = std::chrono::steady_clock::now();
         if (qual_job.valid()) qual_job.get();
+        if (hdr_sum_job.valid()) hdr_sum_job.get();
         w_quals += seconds_since(t_w);
         if (got == batch_reads) parsing = std::async(std::launch::async, parse_next, &buffers[cur ^ 1]);
         if (n_reads == 0) first_header.assign(batch.headers, 0, batch.header_off[1]);
+        const uint64_t batch_blocks_n = (got + rpb - 1) / rpb, batch_block0 = n_reads / rpb;
+        if (checksum) { sum_hdr.resize(batch_block0 + batch_blocks_n, 0); sum_qual.resize(batch_block0 + batch_blocks_n, 0); }   // (no job is running: both were joined above)
         t_w = std::chrono::steady_clock::now();
+        if (keep_header && checksum) {
+            const std::string* headers = &batch.headers;
+            const std::vector<uint64_t>* hoff = &batch.header_off;
+            uint32_t* sums = sum_hdr.data() + batch_block0;
+            const uint32_t cores = (uint32_t)_nbCores;
+            hdr_sum_job = std::async(std::launch::async, [headers, hoff, got, cores, sums] {
+                const std::vector<uint64_t> boff = block_offsets(hoff->data(), got, READ_PER_BLOCK);
+                sums_on_host(headers->data(), headers->size(), boff.data(), boff.size() - 1, cores, sums);
+            });
+        }
         if (keep_header) {
             check_sink(hdr_ctx.get(), leon_header_encode_batch(hdr_ctx.get(), reinterpret_cast<const uint8_t*>(batch.headers.data()), batch.header_off.data(), got, n_reads,
                                                                reinterpret_cast<const uint8_t*>(first_header.data()), first_header.size(), StreamWriter::sink, &wh),
@@ -375,7 +413,10 @@ void Leon::executeCompression() {
             const uint32_t cores = (uint32_t)_nbCores;
             const int qdev = store[0]->device;
             const bool on_device = qual_on_device;
-            qual_job = std::async(std::launch::async, [quals, qoff, got, first_block, cores, qdev, on_device, &wq, &d_qbuf, &d_qbuf_cap] {
+            uint32_t* sums = checksum ? sum_qual.data() + batch_block0 : nullptr;
+            qual_job = std::async(std::launch::async, [quals, qoff, got, first_block, cores, qdev, on_device, sums, &wq, &d_qbuf, &d_qbuf_cap] {
+                // (`-checksum`: the file's own quality bytes -- on the device where the deflate has uploaded them, else beside compress2)
+                const std::vector<uint64_t> boff = sums ? block_offsets(qoff->data(), got, READ_PER_BLOCK) : std::vector<uint64_t>();
                 if (on_device) {
                     if (quals->size() > d_qbuf_cap) {
                         leon_device_free(d_qbuf); d_qbuf = nullptr; d_qbuf_cap = 0;
@@ -384,10 +425,12 @@ void Leon::executeCompression() {
                         d_qbuf_cap = want;
                     }
                     if (!quals->empty()) check(nullptr, leon_device_upload(qdev, d_qbuf, quals->data(), quals->size()), "leon_device_upload");
+                    if (sums) sums_on_device(qdev, d_qbuf, quals->size(), boff.data(), boff.size() - 1, sums);
                     int rc = leon_qual_deflate_blocks_device(qdev, static_cast<const uint8_t*>(d_qbuf), qoff->data(), got, READ_PER_BLOCK, StreamWriter::sink, &wq, first_block);
                     check_sink(nullptr, rc, wq, "leon_qual_deflate_blocks_device");
                     return;
                 }
+                if (sums) sums_on_host(quals->data(), quals->size(), boff.data(), boff.size() - 1, cores, sums);
                 int rc = leon_host_qual_encode_blocks(reinterpret_cast<const uint8_t*>(quals->data()), qoff->data(), got, READ_PER_BLOCK, -1, cores, StreamWriter::sink, &wq,
                                                       first_block);
                 check_sink(nullptr, rc, wq, "leon_host_qual_encode_blocks");
@@ -407,8 +450,15 @@ void Leon::executeCompression() {
         if (got < batch_reads) break;                            // the partial batch is the last one
     }
     if (qual_job.valid()) qual_job.get();
+    if (hdr_sum_job.valid()) hdr_sum_job.get();
     const uint64_t n_blocks = (n_reads + rpb - 1) / rpb, n_bases = offsets.back();
     for (auto& st : store) st->set_offsets(offsets);
+    // `-checksum`: the bases' words from device 0's resident copy; the lossy qualities' below, once they are smoothed
+    const std::vector<uint64_t> file_block_off = checksum ? block_offsets(offsets.data(), n_reads, rpb) : std::vector<uint64_t>();
+    if (checksum) {
+        sum_dna.assign(n_blocks, 0); sum_hdr.resize(n_blocks, 0); sum_qual.resize(n_blocks, 0);
+        sums_on_device(store[0]->device, store[0]->d_bases, n_bases, file_block_off.data(), n_blocks, sum_dna.data());
+    }
     hdr_ctx.reset();
     const double t_parse = seconds_since(t_start);
 
@@ -491,6 +541,7 @@ void Leon::executeCompression() {
             check(ctx[0].get(), rc, "leon_qual_smooth_batch_device");
             r += got;
         }
+        if (checksum) sums_on_device(store[0]->device, qstore->d_bases, n_bases, file_block_off.data(), n_blocks, sum_qual.data());    // what is stored: the smoothed bytes
         {   // the sample that picks the encoder: the first reads' smoothed lines
             const uint64_t ns = std::min<uint64_t>(n_reads, 4000);
             std::string sample(offsets[ns] - offsets[0], '\0');
@@ -541,6 +592,10 @@ void Leon::executeCompression() {
             check(nullptr, leon_device_upload(store[0]->device, d_q, batch.quals.data(), batch.quals.size()), "leon_device_upload");
             check(ctx[0].get(), leon_qual_smooth_batch_device(ctx[0].get(), store[0]->d_bases, store[0]->d_off + r, got, static_cast<uint8_t*>(d_q)),
                   "leon_qual_smooth_batch_device");
+            if (checksum) {
+                const std::vector<uint64_t> boff = block_offsets(batch.qual_off.data(), got, rpb);
+                sums_on_device(store[0]->device, d_q, batch.quals.size(), boff.data(), boff.size() - 1, sum_qual.data() + r / rpb);
+            }
             if (r == 0) {                                        // the sample that picks the encoder: the first reads' smoothed lines
                 const uint64_t ns = std::min<uint64_t>(got, 4000);
                 std::string sample(batch.qual_off[ns] - batch.qual_off[0], '\0');
@@ -590,6 +645,11 @@ void Leon::executeCompression() {
         const std::string plus = bank.plusLines();
         if (!plus.empty()) out.putBytes(DS_PLUS_LINES, plus.data(), plus.size());
     }
+    if (checksum) {                                              // kind, then per block: dna, header, quality (0 for a stream the file does not have)
+        table.assign(1, CHECKSUM_CRC32);
+        for (uint64_t b = 0; b < n_blocks; b++) { table.push_back(sum_dna[b]); table.push_back(keep_header ? sum_hdr[b] : 0); table.push_back(keep_qual ? sum_qual[b] : 0); }
+        out.putU64(DS_CHECKSUMS, table.data(), table.size());
+    }
     out.putBytes(DS_ANCHOR_DICT, dict, dict_size);
     out.putBytes(DS_BLOOM_BITS, bloom.data(), bloom.size());
     const uint8_t info = (uint8_t)((fastq ? 0 : INFO_FASTA) | (keep_header ? 0 : INFO_NO_HEADER) | (keep_qual ? 0 : INFO_NO_QUAL) | (_lossless ? INFO_LOSSLESS : 0));
@@ -612,6 +672,7 @@ void Leon::executeCompression() {
     if (keep_header) std::cout << "header stream: " << header_bytes << " bytes -> " << wh.bytes << " bytes\n";
     if (keep_qual) std::cout << "quality stream (" << (_lossless ? "lossless" : "lossy") << "): " << qual_bytes << " bytes -> " << wq.bytes << " bytes"
                              << (qual_on_device ? " (deflated on the device: runs + dynamic Huffman codes)" : " (zlib on the host threads)") << "\n";
+    if (checksum) std::cout << "checksums: CRC-32 of " << n_blocks << " blocks (dna" << (keep_header ? ", header" : "") << (keep_qual ? ", quality" : "") << ")\n";
     std::cout << "written to " << _outputFilename << std::endl;
     if (_verbose)
         std::cout << "time: parse + headers" << (keep_qual && _lossless ? " + qualities " : " ") << t_parse << " s, k-mer counting " << t_kmers << " s, contexts + bloom "
@@ -676,6 +737,18 @@ void Leon::executeDecompression() {
             if (tqual[3 * b + 1] != tdna[3 * b + 1] || tqual[3 * b + 2] != tdna[3 * b + 2]) throw Exception(_inputFilename + ": quality and DNA blocks disagree");
     }
 
+    // block checksums (`-c -checksum`): verified whenever the table is there, round by round, before the round is written
+    std::vector<uint64_t> tsum;
+    const bool has_sums = in.exists(DS_CHECKSUMS);
+    if (has_sums) {
+        tsum = in.getU64(DS_CHECKSUMS);
+        if (tsum.empty()) throw Exception(_inputFilename + ": the checksum table does not match the read count");
+        if (tsum[0] != CHECKSUM_CRC32) throw Exception(_inputFilename + ": unknown checksum kind " + std::to_string(tsum[0]) + " in " + DS_CHECKSUMS + " (this build knows 1 = CRC-32)");
+        if (tsum.size() != 1 + 3 * n_blocks) throw Exception(_inputFilename + ": the checksum table does not match the read count");
+    }
+    enum : uint32_t { SUM_ON_DEVICE = 1, SUM_ON_HOST = 2 };
+    std::atomic<uint32_t> sum_ways[3] = {{0}, {0}, {0}};         // dna, header, quality: where the rounds' digests were taken
+    std::atomic<uint64_t> sum_mismatches{0};
     CtxPtr ctx = make_ctx((uint32_t)k, tai, device_for(0), (uint32_t)n_hash, (uint32_t)nbits, (uint32_t)rpb);
     CtxPtr hdr_ctx;                                              // header blocks decode on the device too, on a stream of their own
     if (has_header) hdr_ctx = make_ctx((uint32_t)k, 1000, device_for(0));
@@ -786,6 +859,7 @@ void Leon::executeDecompression() {
         std::vector<uint32_t> blk_reads;
         std::vector<uint64_t> hdr_off, qual_off;
         void* d_qual = nullptr;                                  // `-qual-inflate device` under `-record-text device`: the qualities, inflated where the formatter reads them
+        std::vector<uint32_t> sum_hdr, sum_qual;                 // the restored blocks' digests, taken by stage B where the bytes lay (empty: not taken)
         void release_quals() { leon_device_free(d_qual); d_qual = nullptr; }
         ~Round() { release_quals(); }
     };
@@ -1064,6 +1138,7 @@ void Leon::executeDecompression() {
                 const uint64_t nb = R->nb, g_bases = R->g_bases;
                 const bool on_device = hdr_on_device;
                 const bool text_device = hdr_text_device;
+                auto blk_off = [](const std::vector<uint64_t>& sizes) { std::vector<uint64_t> o(sizes.size() + 1, 0); for (size_t b = 0; b < sizes.size(); b++) o[b + 1] = o[b] + sizes[b]; return o; };
                 // `-qual-inflate device`: false when the device has no memory for the round (nothing done: the host threads inflate it)
                 auto inflate_on_device = [&]() -> bool {
                     struct Dev { void* p = nullptr; ~Dev() { leon_device_free(p); } } d_q, d_off;
@@ -1074,6 +1149,11 @@ void Leon::executeDecompression() {
                     if (rc != LEON_OK) throw Exception(std::string("leon_qual_inflate_blocks_device: ") + leon_last_error(nullptr));
                     // the reads' offsets come to the host: the check that a read's quality and sequence lengths agree is the writing stage's
                     if (leon_device_download(rt_dev, R->qual_off.data(), d_off.p, (R->g_reads + 1) * 8) != LEON_OK) throw Exception(std::string("leon_device_download: ") + leon_last_error(nullptr));
+                    if (has_sums) {                              // digested where they were inflated
+                        R->sum_qual.assign(nb, 0);
+                        sums_on_device(rt_dev, d_q.p, g_bases, blk_off(R->blk_bases).data(), nb, R->sum_qual.data());
+                        sum_ways[2] |= SUM_ON_DEVICE;
+                    }
                     if (R->on_device) { R->d_qual = d_q.p; d_q.p = nullptr; }
                     else {
                         R->qual.resize(g_bases + 1);
@@ -1090,6 +1170,11 @@ void Leon::executeDecompression() {
                     R->qual.resize(g_bases + 1);
                     if (leon_host_qual_decode_blocks(R->pay_q.data(), R->off_q.data(), R->blk_reads.data(), R->blk_bases.data(), nb, R->qual.data(), g_bases, R->qual_off.data(), cores) != LEON_OK)
                         throw Exception(std::string("leon_host_qual_decode_blocks: ") + leon_last_error(nullptr));
+                    if (has_sums) {
+                        R->sum_qual.assign(nb, 0);
+                        sums_on_host(R->qual.data(), g_bases, blk_off(R->blk_bases).data(), nb, cores, R->sum_qual.data());
+                        sum_ways[2] |= SUM_ON_HOST;
+                    }
                 };
                 // while the first round waits for the device's header symbols the host threads have nothing to do: the quality blocks go then
                 std::future<void> quals_beside;
@@ -1144,6 +1229,30 @@ void Leon::executeDecompression() {
                         if (quals_beside.valid()) { try { quals_beside.get(); } catch (...) {} }
                         throw Exception(msg);
                     }
+                    if (has_sums) {
+                        // the header text where it lies: in the device's set under `-header-text device` (its blocks' shares follow one another,
+                        // sized by the block table), else the round's host buffer, its blocks cut at the reads' offsets
+                        R->sum_hdr.assign(nb, 0);
+                        const uint8_t* dh = R->d_hdr; const uint64_t* dho = nullptr; uint64_t dsz = R->d_hdr_size;
+                        bool in_set = R->hdr_in_set;
+                        if (!in_set && text_device && !host_decoder) in_set = leon_header_text_device_ptr(hdr_text_set->h, R->block0, nb, &dh, &dho, &dsz) == LEON_OK;
+                        std::vector<uint64_t> boff(nb + 1, 0);
+                        if (in_set) {
+                            for (uint64_t b = 0; b < nb; b++) boff[b + 1] = boff[b] + thdr[3 * (R->block0 + b) + 2];
+                            if (boff[nb] != dsz) in_set = false;
+                        }
+                        try {
+                            if (in_set) { sums_on_device(rt_dev, dh, dsz, boff.data(), nb, R->sum_hdr.data()); sum_ways[1] |= SUM_ON_DEVICE; }
+                            else {
+                                if (R->hdr_in_set) throw Exception(_inputFilename + ": the header block table does not add up");
+                                uint64_t r = 0;
+                                for (uint64_t b = 0; b < nb; b++) { boff[b] = R->hdr_off[r]; r += R->blk_reads[b]; }
+                                boff[nb] = R->hdr_off[r];
+                                sums_on_host(R->hdr.data(), boff[nb], boff.data(), nb, cores, R->sum_hdr.data());
+                                sum_ways[1] |= SUM_ON_HOST;
+                            }
+                        } catch (...) { if (quals_beside.valid()) { try { quals_beside.get(); } catch (...) {} } throw; }
+                    }
                 }
                 lap(th, t_hdr);
                 if (quals_beside.valid()) quals_beside.get();
@@ -1176,6 +1285,31 @@ void Leon::executeDecompression() {
                 const uint64_t g_reads = R->g_reads, g_bases = R->g_bases;
                 // (`-record-text device`: the call's device buffers go when its last round is written, or has failed)
                 struct Left { DnaGroup* g; ~Left() { if (g && --g->rounds_left == 0) g->release_device(); } } left{R->on_device ? R->dna.get() : nullptr};
+                if (has_sums) {
+                    // the restored bases where the decoder left them; the headers' and qualities' digests are stage B's
+                    const uint64_t nb = R->nb;
+                    std::vector<uint64_t> boff(nb + 1, 0);
+                    for (uint64_t b = 0; b < nb; b++) boff[b + 1] = boff[b] + R->blk_bases[b];
+                    std::vector<uint32_t> sum_dna(nb, 0);
+                    if (R->on_device) { sums_on_device(rt_dev, (const uint8_t*)R->dna->d_bases + R->base0, g_bases, boff.data(), nb, sum_dna.data()); sum_ways[0] |= SUM_ON_DEVICE; }
+                    else { sums_on_host(R->bases(), g_bases, boff.data(), nb, cores, sum_dna.data()); sum_ways[0] |= SUM_ON_HOST; }
+                    // the smallest failing block first (the rounds come in file order), its streams in the order dna, header, quality
+                    const char* const names[3] = {"dna", "header", "quality"};
+                    const std::vector<uint32_t>* got[3] = {&sum_dna, has_header ? &R->sum_hdr : nullptr, has_qual && fastq_out ? &R->sum_qual : nullptr};
+                    for (uint64_t b = 0; b < nb; b++)
+                        for (int st = 0; st < 3; st++) {
+                            if (!got[st]) continue;
+                            if (got[st]->size() != nb) throw Exception(std::string("checksum: the ") + names[st] + " digests of block " + std::to_string(R->block0 + b) + " were not taken");
+                            const uint64_t stored = tsum[1 + 3 * (R->block0 + b) + st];
+                            if (stored == (*got[st])[b]) continue;
+                            char hex[64];
+                            snprintf(hex, sizeof hex, "(stored 0x%08llx, restored 0x%08x)", (unsigned long long)stored, (unsigned)(*got[st])[b]);
+                            const std::string msg = std::string("checksum: ") + names[st] + " block " + std::to_string(R->block0 + b) + " does not match what was compressed " + hex;
+                            if (!_ignoreChecksum) throw Exception(msg);
+                            std::cerr << "WARNING: " << msg << std::endl;
+                            sum_mismatches++;
+                        }
+                }
                 // the size of this round's text: where the next round's begins
                 uint64_t n_text = 0;
                 if (R->on_device) {                              // ('+' lines of one kind; the header text may lie on the device: its size is known all the same)
@@ -1222,6 +1356,14 @@ void Leon::executeDecompression() {
         std::cout << "time: " << seconds_since(t_start) << " s (" << (n_blocks + group - 1) / group << " round(s); container reads " << t_read << ", dictionary + DNA blocks on the device " << t_dna
                   << "; beside them, a round behind: header blocks " << t_hdr << " + quality blocks " << t_qual << "; another round behind: formatting + writing "
                   << t_text << "; waited for them " << t_writer_wait + t_write << ")" << std::endl;
+    if (_verbose && has_sums) {
+        auto way = [&](int st, bool present) -> std::string {
+            const uint32_t w = sum_ways[st].load();
+            return !present ? "not stored" : w == SUM_ON_DEVICE ? "device" : w == SUM_ON_HOST ? "host threads" : w ? "device and host threads" : "nothing to verify";
+        };
+        std::cout << "checksums: " << n_blocks << " blocks verified (dna: " << way(0, true) << ", header: " << way(1, has_header) << ", quality: " << way(2, has_qual && fastq_out) << ")"
+                  << (sum_mismatches.load() ? ", " + std::to_string(sum_mismatches.load()) + " mismatch(es) ignored (-ignore-checksum)" : std::string()) << std::endl;
+    }
     if (_verbose && has_header)
         std::cout << "header text: " << (hdr_text_device ? "device (k_hdr_text), " + std::to_string(hdr_blocks_fell_back.load()) + " of " + std::to_string(n_blocks) + " blocks fell back to the host decoder"
                                                          : hdr_on_device ? std::string("host threads, from symbols decoded on the device") : std::string("host threads"))

@@ -46,6 +46,8 @@ public:
     int _nbCores = 0;                     // 0 = all
     int _gpus = 1;
     bool _lossless = false, _seqOnly = false, _noHeader = false, _noQual = false, _testFile = false, _verbose = false;
+    bool _checksum = false;               // -c: -checksum: a CRC-32 per read block and stream in leon/metadata/checksums; -d verifies it whenever it is there
+    bool _ignoreChecksum = false;         // -d: -ignore-checksum: a mismatch is a WARNING on stderr, the file is kept
     std::string _qualDeflate;             // -qual-deflate host|device|auto; empty = not given: zlib on the host threads (the reference's bytes)
     std::string _headerText;              // -d: -header-text host|device|auto; empty = not given: the header text on the host threads
     std::string _recordText;              // -d: -record-text host|device|auto; empty = not given: the records formatted on the host threads
