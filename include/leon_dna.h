@@ -387,6 +387,29 @@ int leon_crc32_segments_device(int device_id, const uint8_t* d_bytes, uint64_t n
 /* zlib's crc32 on n_threads host threads (0 = all this process may use); needs no GPU */
 int leon_host_crc32_segments(const uint8_t* bytes, uint64_t n_bytes, const uint64_t* seg_off, uint64_t n_seg, uint32_t n_threads, uint32_t* crc);
 
+/* -- every sequence letter kept: lower-case runs and bytes outside ACGTN --
+ * For the n_bytes bases at d_bases (the reads' bases one after another): a RUN is a maximal interval [begin, end) of bytes in
+ * 'a'..'z'; an ODD byte is one that, folded to upper case when it is lower-case, is none of A C G T N; the FOLDED buffer holds the
+ * upper-case form where that is one of A C G T N and 'N' elsewhere -- what the DNA coder can carry.  Positions are relative to
+ * d_bases, which may have any alignment; the tables are HOST memory; nothing outside [d_bases, d_bases + n_bytes) is read or written.
+ * The three device calls take no context, work on a stream of their own and are complete on return (letters_kernels.hip).
+ * count: the runs and odd bytes of the buffer; writes nothing to it.
+ * take:  runs (2 * n_runs words: begin, end), odd_pos and odd_byte (the ORIGINAL bytes) in ascending position, and folds d_bases in
+ *        place.  LEON_E_STATE when the buffer does not hold exactly n_runs runs and n_odd odd bytes: nothing has changed then.
+ * apply: the inverse on a folded (decoded) buffer: inside every run a byte in 'A'..'Z' gets | 0x20, then every odd record overwrites
+ *        its position.  Both forms check the tables before anything is touched and refuse with LEON_E_INVALID and the same words:
+ *        begin < end <= n_bytes, runs ascending and not overlapping (end[i] <= begin[i + 1]), odd_pos strictly ascending and
+ *        < n_bytes, null pointers with non-zero counts.
+ * n_bytes == 0 and empty tables are LEON_OK without a launch.  Errors: leon_last_error(NULL). */
+int leon_letters_count_device(int device_id, const uint8_t* d_bases, uint64_t n_bytes, uint64_t* n_runs, uint64_t* n_odd);
+int leon_letters_take_device(int device_id, uint8_t* d_bases, uint64_t n_bytes, uint64_t* runs, uint64_t n_runs, uint64_t* odd_pos, uint8_t* odd_byte,
+                             uint64_t n_odd);
+int leon_letters_apply_device(int device_id, uint8_t* d_bases, uint64_t n_bytes, const uint64_t* runs, uint64_t n_runs, const uint64_t* odd_pos,
+                              const uint8_t* odd_byte, uint64_t n_odd);
+/* apply on n_threads host threads (0 = all this process may use); needs no GPU */
+int leon_host_letters_apply(uint8_t* bases, uint64_t n_bytes, const uint64_t* runs, uint64_t n_runs, const uint64_t* odd_pos, const uint8_t* odd_byte,
+                            uint64_t n_odd, uint32_t n_threads);
+
 /* Start a new output file on the same context: forgets the anchor dictionary, the dictionary stream and the
  * read/block counters (a fresh Leon object upstream); keeps the bloom and the device buffers. */
 int leon_dna_reset_stream(leon_dna_ctx* ctx);

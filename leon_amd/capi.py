@@ -143,6 +143,10 @@ _EXPORTS = {
                                                    C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "leon_crc32_segments_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "leon_host_crc32_segments": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "leon_letters_count_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, _u64p, _u64p]),
+    "leon_letters_take_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "leon_letters_apply_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "leon_host_letters_apply": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
 }
 EXPORTED_SYMBOLS = tuple(_EXPORTS)
 _lib = None
@@ -363,6 +367,67 @@ def host_crc32_segments(data, seg_off, n_threads=0, n_bytes=None, n_seg=None, nu
     if rc:
         raise LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
     return crc[:n_seg]
+
+
+def letters_count_device(d_bases, n_bytes, device_id=0):
+    """leon_letters_count_device: (lower-case runs, bytes outside ACGTN) of the n_bytes at the device pointer d_bases (an integer)"""
+    lib = load_library()
+    n_runs, n_odd = C.c_uint64(), C.c_uint64()
+    rc = lib.leon_letters_count_device(device_id, C.c_void_p(int(d_bases)), int(n_bytes), C.byref(n_runs), C.byref(n_odd))
+    if rc:
+        raise LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+    return n_runs.value, n_odd.value
+
+
+def letters_take_device(d_bases, n_bytes, n_runs, n_odd, device_id=0, slack=0, fill=0):
+    """leon_letters_take_device: folds the buffer in place; (runs as an (n_runs, 2) uint64 array, odd_pos, odd_byte).  With `slack` the
+    three host arrays are that many elements longer, filled with `fill`, and come back whole: what lies behind the tables is the
+    caller's to inspect."""
+    lib = load_library()
+    runs = np.full(2 * (n_runs + slack) + 1, fill, dtype=np.uint64)
+    pos = np.full(n_odd + slack + 1, fill, dtype=np.uint64)
+    byte = np.full(n_odd + slack + 1, fill, dtype=np.uint8)
+    rc = lib.leon_letters_take_device(device_id, C.c_void_p(int(d_bases)), int(n_bytes), C.c_void_p(runs.ctypes.data), int(n_runs), C.c_void_p(pos.ctypes.data),
+                                      C.c_void_p(byte.ctypes.data), int(n_odd))
+    if rc:
+        err = LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+        err.tables = (runs, pos, byte)
+        raise err
+    if slack:
+        return runs, pos, byte
+    return runs[:2 * n_runs].reshape(-1, 2), pos[:n_odd], byte[:n_odd]
+
+
+def _letters_tables(runs, odd_pos, odd_byte, n_runs, n_odd):
+    """the tables (None = NULL) as contiguous arrays, and the counts the call is given"""
+    r = None if runs is None else np.ascontiguousarray(runs, dtype=np.uint64).reshape(-1)
+    p = None if odd_pos is None else np.ascontiguousarray(odd_pos, dtype=np.uint64)
+    b = None if odd_byte is None else np.ascontiguousarray(odd_byte, dtype=np.uint8)
+    n_runs = (0 if r is None else len(r) // 2) if n_runs is None else int(n_runs)
+    n_odd = (0 if p is None else len(p)) if n_odd is None else int(n_odd)
+    at = lambda a: C.c_void_p(0 if a is None or not len(a) else a.ctypes.data)
+    return (r, p, b), (at(r), n_runs, at(p), at(b), n_odd)
+
+
+def letters_apply_device(d_bases, n_bytes, runs, odd_pos, odd_byte, device_id=0, n_runs=None, n_odd=None):
+    """leon_letters_apply_device on the n_bytes at the device pointer d_bases (an integer, 0 = NULL); the tables are host arrays (None
+    passes NULL; n_runs / n_odd override the counts)"""
+    lib = load_library()
+    keep, (r, nr, p, b, no) = _letters_tables(runs, odd_pos, odd_byte, n_runs, n_odd)
+    rc = lib.leon_letters_apply_device(device_id, C.c_void_p(int(d_bases)), int(n_bytes), r, nr, p, b, no)
+    if rc:
+        raise LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+
+
+def host_letters_apply(bases, runs, odd_pos, odd_byte, n_threads=0, n_bytes=None, n_runs=None, n_odd=None):
+    """leon_host_letters_apply (no GPU) on a writable uint8 array (None passes NULL), in place; the rest as letters_apply_device"""
+    lib = load_library()
+    keep, (r, nr, p, b, no) = _letters_tables(runs, odd_pos, odd_byte, n_runs, n_odd)
+    if n_bytes is None:
+        n_bytes = 0 if bases is None else len(bases)
+    rc = lib.leon_host_letters_apply(C.c_void_p(0 if bases is None or not len(bases) else bases.ctypes.data), int(n_bytes), r, nr, p, b, no, n_threads)
+    if rc:
+        raise LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
 
 
 def kmer_auto_cutoff(histogram):

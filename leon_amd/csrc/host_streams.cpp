@@ -393,3 +393,48 @@ int leon_host_crc32_segments(const uint8_t* bytes, uint64_t n_bytes, const uint6
     }
     return LEON_OK;
 }
+
+// ---- lower-case runs and bytes outside ACGTN put back: the host form of leon_letters_apply_device ----
+namespace leon {
+// what both forms refuse, in the same words; nullptr: the tables are in order.  Reads the tables only.
+const char* letters_tables_refusal(const uint8_t* bases, uint64_t n_bytes, const uint64_t* runs, uint64_t n_runs, const uint64_t* odd_pos,
+                                   const uint8_t* odd_byte, uint64_t n_odd) {
+    if ((n_runs && !runs) || (n_odd && (!odd_pos || !odd_byte))) return "letters: null argument";
+    if ((n_bytes >> 62) || (n_runs >> 58) || (n_odd >> 58)) return "letters: implausible sizes";
+    for (uint64_t r = 0; r < n_runs; r++) {
+        if (runs[2 * r] >= runs[2 * r + 1]) return "letters: a run is empty or runs backwards";
+        if (runs[2 * r + 1] > n_bytes) return "letters: a run ends behind the bytes given";
+        if (r && runs[2 * r - 1] > runs[2 * r]) return "letters: the runs overlap or are not ascending";
+    }
+    for (uint64_t i = 0; i < n_odd; i++) {
+        if (odd_pos[i] >= n_bytes) return "letters: a position lies behind the bytes given";
+        if (i && odd_pos[i - 1] >= odd_pos[i]) return "letters: the positions are not strictly ascending";
+    }
+    if ((n_runs || n_odd) && !bases) return "letters: null argument";
+    return nullptr;
+}
+}  // namespace leon
+
+int leon_host_letters_apply(uint8_t* bases, uint64_t n_bytes, const uint64_t* runs, uint64_t n_runs, const uint64_t* odd_pos, const uint8_t* odd_byte,
+                            uint64_t n_odd, uint32_t n_threads) {
+    if (const char* why = leon::letters_tables_refusal(bases, n_bytes, runs, n_runs, odd_pos, odd_byte, n_odd)) return fail(LEON_E_INVALID, why);
+    // the case first, then the bytes: a lower-case odd byte inside a run is its own record's.  Pieces of 4 MiB of the buffer, so that
+    // one long run is shared among the threads; a piece looks its first run up
+    constexpr uint64_t kPiece = 4ull << 20;
+    if (n_runs) {
+        const uint64_t first = runs[0] / kPiece, last = (runs[2 * n_runs - 1] - 1) / kPiece;
+        parallel_blocks(last - first + 1, n_threads, [&](uint64_t i) {
+            const uint64_t a = (first + i) * kPiece, b = std::min(n_bytes, a + kPiece);
+            uint64_t lo = 0, hi = n_runs;                         // the first run that ends behind a
+            while (lo < hi) { const uint64_t mid = lo + (hi - lo) / 2; if (runs[2 * mid + 1] > a) hi = mid; else lo = mid + 1; }
+            for (uint64_t r = lo; r < n_runs && runs[2 * r] < b; r++)
+                for (uint64_t p = std::max(a, runs[2 * r]), e = std::min(b, runs[2 * r + 1]); p < e; p++)
+                    if ((uint8_t)(bases[p] - 'A') < 26) bases[p] |= 0x20;
+        });
+    }
+    constexpr uint64_t kRecords = 1ull << 16;
+    parallel_blocks((n_odd + kRecords - 1) / kRecords, n_threads, [&](uint64_t i) {
+        for (uint64_t j = i * kRecords, e = std::min(n_odd, j + kRecords); j < e; j++) bases[odd_pos[j]] = odd_byte[j];
+    });
+    return LEON_OK;
+}

@@ -241,4 +241,7 @@ uint64_t crc32_tile_count(const uint8_t* bytes, uint64_t first, uint64_t last);
 // off[n_seg + 1] (device); acc[n_seg] zeroed by the caller, holds every segment's CRC-32 afterwards
 void launch_crc32_segments(hipStream_t s, const uint8_t* bytes, const uint64_t* off, uint64_t n_seg, uint64_t n_tiles, uint32_t* acc);
 
+// ---- lower-case runs and bytes outside ACGTN of a device buffer (letters_kernels.hip), DESIGN.md 4.12 ----
+constexpr uint64_t LETTERS_MAX_GROUPS = 2048;                  // the grid's cap: a workgroup walks ceil(tiles / cap) consecutive 4 KiB tiles
+
 }  // namespace leon

@@ -28,6 +28,10 @@ constexpr const char* DS_HEADER_TABLE = "leon/metadata/header_blocksizes";   // 
 constexpr const char* DS_QUAL_TABLE = "leon/metadata/qual_blocksizes";       // u64[3 n]: payload bytes, reads, quality bytes
 constexpr const char* DS_CHECKSUMS = "leon/metadata/checksums";        // u64[1 + 3 n]: the kind (CHECKSUM_*), then per block the digest of its bases, headers, qualities;
                                                                         // optional (`-c -checksum`); 0 for a stream the file does not have
+// optional (`-c -letters`, and only for a file that has such letters); positions index the file's bases, all blocks in file order
+constexpr const char* DS_LETTER_RUNS = "leon/metadata/letter_runs";            // u64[1 + 2 R]: the kind (LETTERS_*), then begin, end of every lower-case run
+constexpr const char* DS_LETTER_ODD_POS = "leon/metadata/letter_odd_pos";      // u64[X]: the positions of the bytes outside ACGTN (absent: X = 0)
+constexpr const char* DS_LETTER_ODD_BYTES = "leon/metadata/letter_odd_bytes";  // u8[X]: the original bytes
 constexpr const char* DS_ANCHOR_DICT = "leon/anchors/dict";            // u8[]: the anchor-dictionary stream
 constexpr const char* DS_BLOOM_BITS = "bloom/bits";                    // u8[nchar]
 constexpr const char* BLOCK_PREFIX = "block_";
@@ -44,6 +48,7 @@ constexpr uint64_t CONTAINER_REV = 2;
 enum QualEnc : uint64_t { QUAL_ENC_NONE = 0,          // no quality stream (or a revision-1 file: not recorded)
                           QUAL_ENC_ZLIB = 1,          // zlib's compress2 at its default level (what upstream writes [RECALLED]): the default
                           QUAL_ENC_DEVICE_RLE = 2 };  // the device's deflate (runs + dynamic Huffman codes): inflates to the same text, other bytes
+enum LettersKind : uint64_t { LETTERS_RUNS_AND_BYTES = 1 };   // the rule of DESIGN.md 4.12
 enum ChecksumKind : uint64_t { CHECKSUM_CRC32 = 1 };  // zlib's crc32 over the block's bytes of the stream as the decoder returns them
 // info byte: bit 0 FASTA input (else FASTQ), bit 1 no header stream, bit 2 no quality stream, bit 3 lossless qualities
 enum Info : uint8_t { INFO_FASTA = 1, INFO_NO_HEADER = 2, INFO_NO_QUAL = 4, INFO_LOSSLESS = 8 };

@@ -30,6 +30,7 @@
 #include <future>
 #include <iostream>
 #include <memory>
+#include <map>
 #include <mutex>
 #include <thread>
 
@@ -79,7 +80,9 @@ CtxPtr make_ctx(uint32_t k, uint64_t tai, int device, uint32_t n_hash = 7, uint3
 }
 
 // One stream's blocks on their way into the container (Leon::writeBlock / writeBlockLena).  Blocks of one stream come from
-// one thread in increasing id, or -- DNA blocks of a multi-GPU run -- from one thread per GPU with disjoint ids.
+// one thread in increasing id, or -- DNA blocks of a multi-GPU run -- from one thread per GPU with disjoint ids.  `in_order`: such a
+// run's blocks are written in increasing id all the same -- a block that arrives ahead of its turn waits in `ahead` -- so that the
+// container is the bytes `-gpus 1` writes (the file's layout follows the order in which its datasets are made).
 struct StreamWriter {
     Container* out = nullptr;
     std::mutex* mu = nullptr;
@@ -87,14 +90,27 @@ struct StreamWriter {
     std::vector<uint64_t> sizes, reads;          // per block id
     uint64_t bytes = 0;
     std::string error;
+    bool in_order = false;
+    uint64_t next_id = 0;
+    std::map<uint64_t, std::pair<std::vector<uint8_t>, uint32_t>> ahead;
+    void put(uint64_t block_id, const uint8_t* payload, uint64_t size, uint32_t n_reads) {
+        if (block_id >= sizes.size()) { sizes.resize(block_id + 1, ~0ull); reads.resize(block_id + 1, 0); }
+        out->putBytes(Container::blockPath(group, block_id), payload, size);
+        sizes[block_id] = size; reads[block_id] = n_reads; bytes += size;
+    }
     static int sink(void* user, uint64_t block_id, const uint8_t* payload, uint64_t size, uint32_t n_reads) {
         StreamWriter* w = static_cast<StreamWriter*>(user);
         try {
             std::lock_guard<std::mutex> g(*w->mu);
-            if (block_id >= w->sizes.size()) { w->sizes.resize(block_id + 1, ~0ull); w->reads.resize(block_id + 1, 0); }
-            if (w->sizes[block_id] != ~0ull) throw Exception("block " + std::to_string(block_id) + " arrived twice");
-            w->out->putBytes(Container::blockPath(w->group, block_id), payload, size);
-            w->sizes[block_id] = size; w->reads[block_id] = n_reads; w->bytes += size;
+            if ((block_id < w->sizes.size() && w->sizes[block_id] != ~0ull) || w->ahead.count(block_id)) throw Exception("block " + std::to_string(block_id) + " arrived twice");
+            if (w->in_order && block_id != w->next_id) { w->ahead[block_id] = std::make_pair(std::vector<uint8_t>(payload, payload + size), n_reads); return 0; }
+            w->put(block_id, payload, size, n_reads);
+            if (w->in_order)
+                for (w->next_id++; !w->ahead.empty() && w->ahead.begin()->first == w->next_id; w->next_id++) {
+                    const auto& b = w->ahead.begin()->second;
+                    w->put(w->next_id, b.first.data(), b.first.size(), b.second);
+                    w->ahead.erase(w->ahead.begin());
+                }
             return 0;
         } catch (const std::exception& e) {        // no exception may cross the C boundary
             w->error = e.what();
@@ -286,6 +302,7 @@ void Leon::run(int argc, char* argv[]) {
             else if (a == "-test-file") _testFile = true;
             else if (a == "-checksum") _checksum = true;
             else if (a == "-ignore-checksum") _ignoreChecksum = true;
+            else if (a == "-letters") _letters = true;
             else if (a == "-qual-deflate") { _qualDeflate = need("-qual-deflate"); (void)qual_encoder_choice(_qualDeflate); }
             else if (a == "-header-text") { _headerText = need("-header-text"); (void)header_text_choice(_headerText); }
             else if (a == "-record-text") { _recordText = need("-record-text"); (void)record_text_choice(_recordText); }
@@ -296,6 +313,7 @@ void Leon::run(int argc, char* argv[]) {
         if (_compress == _decompress) throw Exception("choose one of -c (compress) or -d (decompress)");
         if (_checksum && _decompress) throw Exception("option -checksum belongs to -c: -d verifies whenever the container holds checksums (-ignore-checksum to go on past a mismatch)");
         if (_ignoreChecksum && _compress) throw Exception("option -ignore-checksum belongs to -d");
+        if (_letters && _decompress) throw Exception("option -letters belongs to -c: -d restores the letters whenever the container holds them");
         if (_seqOnly) _noHeader = _noQual = true;             // "same as -noheader -noqual", /root/reference/README.md:56
         execute();
     } catch (const Exception&) {
@@ -331,6 +349,7 @@ void Leon::executeCompression() {
 
     // ---- the pass over the file ----
     const int n_gpus = _gpus;
+    wd.in_order = n_gpus > 1;
     std::vector<std::unique_ptr<DeviceReads>> store;
     for (int g = 0; g < n_gpus; g++) { store.emplace_back(new DeviceReads()); store.back()->device = device_for(g); }
     CtxPtr hdr_ctx;
@@ -459,6 +478,34 @@ void Leon::executeCompression() {
         sum_dna.assign(n_blocks, 0); sum_hdr.resize(n_blocks, 0); sum_qual.resize(n_blocks, 0);
         sums_on_device(store[0]->device, store[0]->d_bases, n_bases, file_block_off.data(), n_blocks, sum_dna.data());
     }
+    // `-letters`: lower-case runs and bytes outside ACGTN out of every device's resident copy, which is folded to what the coder carries
+    // (DESIGN.md 4.12).  Behind the checksum: the stored digest is of the ORIGINAL bytes.  Slices of at most 1 GiB bound the calls' tables.
+    std::vector<uint64_t> letter_runs, letter_odd_pos;           // begin, end pairs; positions in the file's bases
+    std::vector<uint8_t> letter_odd_bytes;
+    if (_letters) {
+        uint64_t slice = 1ull << 30;
+        if (const char* e = getenv("LEON_LETTERS_SLICE")) { const long long v = atoll(e); if (v > 0) slice = (uint64_t)v; }   // (tests: several slices on a small file)
+        std::vector<uint64_t> runs, pos;
+        std::vector<uint8_t> bytes;
+        for (size_t g = 0; g < store.size(); g++)
+            for (uint64_t at = 0; at < n_bases; at += slice) {
+                const uint64_t nb = std::min(slice, n_bases - at);
+                uint64_t nr = 0, no = 0;
+                check(nullptr, leon_letters_count_device(store[g]->device, store[g]->d_bases + at, nb, &nr, &no), "leon_letters_count_device");
+                if (!nr && !no) continue;
+                runs.resize(2 * nr); pos.resize(no); bytes.resize(no);
+                check(nullptr, leon_letters_take_device(store[g]->device, store[g]->d_bases + at, nb, runs.data(), nr, pos.data(), bytes.data(), no), "leon_letters_take_device");
+                if (g) continue;                                 // the replicas hold the same bytes: device 0's tables are the file's
+                for (uint64_t r = 0; r < nr; r++) {
+                    if (r == 0 && !letter_runs.empty() && letter_runs.back() == at && runs[0] == 0) letter_runs.back() = at + runs[1];   // a run across the slices' join
+                    else { letter_runs.push_back(at + runs[2 * r]); letter_runs.push_back(at + runs[2 * r + 1]); }
+                }
+                for (uint64_t i = 0; i < no; i++) letter_odd_pos.push_back(at + pos[i]);
+                letter_odd_bytes.insert(letter_odd_bytes.end(), bytes.begin(), bytes.end());
+            }
+    }
+    const bool has_letters = !letter_runs.empty() || !letter_odd_pos.empty();
+    const uint64_t letter_table_bytes = has_letters ? 8 * (1 + letter_runs.size()) + 9 * letter_odd_pos.size() : 0;
     hdr_ctx.reset();
     const double t_parse = seconds_since(t_start);
 
@@ -650,6 +697,15 @@ void Leon::executeCompression() {
         for (uint64_t b = 0; b < n_blocks; b++) { table.push_back(sum_dna[b]); table.push_back(keep_header ? sum_hdr[b] : 0); table.push_back(keep_qual ? sum_qual[b] : 0); }
         out.putU64(DS_CHECKSUMS, table.data(), table.size());
     }
+    if (has_letters) {                                           // kind, then begin, end of every run; the odd bytes' two tables when there are any
+        table.assign(1, LETTERS_RUNS_AND_BYTES);
+        table.insert(table.end(), letter_runs.begin(), letter_runs.end());
+        out.putU64(DS_LETTER_RUNS, table.data(), table.size());
+        if (!letter_odd_pos.empty()) {
+            out.putU64(DS_LETTER_ODD_POS, letter_odd_pos.data(), letter_odd_pos.size());
+            out.putBytes(DS_LETTER_ODD_BYTES, letter_odd_bytes.data(), letter_odd_bytes.size());
+        }
+    }
     out.putBytes(DS_ANCHOR_DICT, dict, dict_size);
     out.putBytes(DS_BLOOM_BITS, bloom.data(), bloom.size());
     const uint8_t info = (uint8_t)((fastq ? 0 : INFO_FASTA) | (keep_header ? 0 : INFO_NO_HEADER) | (keep_qual ? 0 : INFO_NO_QUAL) | (_lossless ? INFO_LOSSLESS : 0));
@@ -674,6 +730,10 @@ void Leon::executeCompression() {
                              << (qual_on_device ? " (deflated on the device: runs + dynamic Huffman codes)" : " (zlib on the host threads)") << "\n";
     if (checksum) std::cout << "checksums: CRC-32 of " << n_blocks << " blocks (dna" << (keep_header ? ", header" : "") << (keep_qual ? ", quality" : "") << ")\n";
     std::cout << "written to " << _outputFilename << std::endl;
+    if (_verbose && _letters) {
+        if (has_letters) std::cout << "letters: " << letter_runs.size() / 2 << " lower-case run(s), " << letter_odd_pos.size() << " other byte(s) kept (" << letter_table_bytes << " bytes)\n";
+        else std::cout << "letters: none\n";
+    }
     if (_verbose)
         std::cout << "time: parse + headers" << (keep_qual && _lossless ? " + qualities " : " ") << t_parse << " s, k-mer counting " << t_kmers << " s, contexts + bloom "
                   << t_bloom - t_kmers << " s, DNA encode " << t_encode << " s, total " << seconds_since(t_start) << " s\n"
@@ -746,6 +806,34 @@ void Leon::executeDecompression() {
         if (tsum[0] != CHECKSUM_CRC32) throw Exception(_inputFilename + ": unknown checksum kind " + std::to_string(tsum[0]) + " in " + DS_CHECKSUMS + " (this build knows 1 = CRC-32)");
         if (tsum.size() != 1 + 3 * n_blocks) throw Exception(_inputFilename + ": the checksum table does not match the read count");
     }
+    // the letters the coder does not carry (`-c -letters`): put back whenever the tables are there, round by round, where
+    // the decoded bases lie, before the round is verified and formatted.  Checked here, before anything is decoded.
+    std::vector<uint64_t> lt_runs, lt_pos;                       // begin, end pairs (the kind word taken off); positions in the file's bases
+    std::vector<uint8_t> lt_bytes;
+    const bool has_letters = in.exists(DS_LETTER_RUNS);
+    if (has_letters) {
+        auto bad = [&](const char* ds, const std::string& what) { return Exception(std::string("letters: ") + ds + " " + what); };
+        lt_runs = in.getU64(DS_LETTER_RUNS);
+        if (lt_runs.empty()) throw bad(DS_LETTER_RUNS, "is empty");
+        if (lt_runs[0] != LETTERS_RUNS_AND_BYTES) throw bad(DS_LETTER_RUNS, "is of unknown kind " + std::to_string(lt_runs[0]) + " (this build knows 1)");
+        if (lt_runs.size() % 2 != 1) throw bad(DS_LETTER_RUNS, "does not hold pairs");
+        lt_runs.erase(lt_runs.begin());
+        for (size_t r = 0; r < lt_runs.size(); r += 2) {
+            if (lt_runs[r] >= lt_runs[r + 1]) throw bad(DS_LETTER_RUNS, "run " + std::to_string(r / 2) + " is empty or runs backwards");
+            if (lt_runs[r + 1] > total_bases) throw bad(DS_LETTER_RUNS, "run " + std::to_string(r / 2) + " ends behind the file's " + std::to_string(total_bases) + " bases");
+            if (r && lt_runs[r - 1] > lt_runs[r]) throw bad(DS_LETTER_RUNS, "run " + std::to_string(r / 2) + " overlaps the run before it");
+        }
+        const bool has_pos = in.exists(DS_LETTER_ODD_POS), has_bytes = in.exists(DS_LETTER_ODD_BYTES);
+        if (has_pos != has_bytes) throw bad(has_pos ? DS_LETTER_ODD_BYTES : DS_LETTER_ODD_POS, "is missing");
+        if (has_pos) { lt_pos = in.getU64(DS_LETTER_ODD_POS); lt_bytes = in.getBytes(DS_LETTER_ODD_BYTES); }
+        if (lt_pos.size() != lt_bytes.size()) throw bad(DS_LETTER_ODD_BYTES, "holds " + std::to_string(lt_bytes.size()) + " bytes for " + std::to_string(lt_pos.size()) + " positions");
+        for (size_t i = 0; i < lt_pos.size(); i++) {
+            if (lt_pos[i] >= total_bases) throw bad(DS_LETTER_ODD_POS, "position " + std::to_string(i) + " lies behind the file's " + std::to_string(total_bases) + " bases");
+            if (i && lt_pos[i - 1] >= lt_pos[i]) throw bad(DS_LETTER_ODD_POS, "position " + std::to_string(i) + " is not behind the one before it");
+        }
+    }
+    enum : uint32_t { LT_ON_DEVICE = 1, LT_ON_HOST = 2 };
+    std::atomic<uint32_t> lt_ways{0};
     enum : uint32_t { SUM_ON_DEVICE = 1, SUM_ON_HOST = 2 };
     std::atomic<uint32_t> sum_ways[3] = {{0}, {0}, {0}};         // dna, header, quality: where the rounds' digests were taken
     std::atomic<uint64_t> sum_mismatches{0};
@@ -848,6 +936,7 @@ void Leon::executeDecompression() {
     struct Round {
         uint64_t read_index = 0, file_off = 0, g_reads = 0, g_bases = 0, n_text = 0, nb = 0, hdr_text_bytes = 0, block0 = 0;
         std::shared_ptr<DnaGroup> dna; uint64_t base0 = 0, read0 = 0;   // this round's share of them
+        uint64_t file_base0 = 0;                                 // the round's first base in the file's bases (the letter tables' positions)
         const uint8_t* bases() const { return own_bases.p ? own_bases.p.get() : dna->bases.p.get() + base0; }
         bool on_device = false;                                  // `-record-text device`: the round's bases are in dna->d_bases
         bool hdr_in_set = false;                                 // ... and its header text lies in the device's header-text set:
@@ -1122,7 +1211,7 @@ void Leon::executeDecompression() {
             uint64_t g_reads = 0, g_bases = 0;
             for (uint64_t b = 0; b < nb; b++) { g_reads += R->blk_reads[b]; g_bases += R->blk_bases[b]; }
             R->read_index = read_index; R->g_reads = g_reads; R->g_bases = g_bases;
-            R->dna = G; R->base0 = base0; R->read0 = read0;
+            R->dna = G; R->base0 = base0; R->read0 = read0; R->file_base0 = bases_out;
             R->on_device = g_device;
             if (g_device) G->rounds_left++;
             if (has_header && !hdr_on_device) gather(GROUP_HEADER, thdr, 3, g0, nb, R->pay_h, R->off_h);
@@ -1285,6 +1374,28 @@ void Leon::executeDecompression() {
                 const uint64_t g_reads = R->g_reads, g_bases = R->g_bases;
                 // (`-record-text device`: the call's device buffers go when its last round is written, or has failed)
                 struct Left { DnaGroup* g; ~Left() { if (g && --g->rounds_left == 0) g->release_device(); } } left{R->on_device ? R->dna.get() : nullptr};
+                if (has_letters) {
+                    // the round's share of the tables: runs clipped to the round, positions from its first base
+                    const uint64_t b0 = R->file_base0, b1 = b0 + g_bases;
+                    const uint64_t n_all = lt_runs.size() / 2;
+                    uint64_t ra = 0, rb = n_all;                 // the first run that ends behind b0 .. the first that begins at or behind b1
+                    for (uint64_t hi = n_all; ra < hi;) { const uint64_t mid = ra + (hi - ra) / 2; if (lt_runs[2 * mid + 1] > b0) hi = mid; else ra = mid + 1; }
+                    for (uint64_t lo = ra; lo < rb;) { const uint64_t mid = lo + (rb - lo) / 2; if (lt_runs[2 * mid] >= b1) rb = mid; else lo = mid + 1; }
+                    std::vector<uint64_t> runs;
+                    for (uint64_t r = ra; r < rb; r++) { runs.push_back(std::max(lt_runs[2 * r], b0) - b0); runs.push_back(std::min(lt_runs[2 * r + 1], b1) - b0); }
+                    const size_t pa = std::lower_bound(lt_pos.begin(), lt_pos.end(), b0) - lt_pos.begin(), pb = std::lower_bound(lt_pos.begin(), lt_pos.end(), b1) - lt_pos.begin();
+                    std::vector<uint64_t> pos(lt_pos.begin() + pa, lt_pos.begin() + pb);
+                    for (uint64_t& p : pos) p -= b0;
+                    if (R->on_device) {
+                        check(nullptr, leon_letters_apply_device(rt_dev, (uint8_t*)R->dna->d_bases + R->base0, g_bases, runs.data(), runs.size() / 2, pos.data(), lt_bytes.data() + pa, pos.size()),
+                              "leon_letters_apply_device");
+                        lt_ways |= LT_ON_DEVICE;
+                    } else {
+                        check(nullptr, leon_host_letters_apply(const_cast<uint8_t*>(R->bases()), g_bases, runs.data(), runs.size() / 2, pos.data(), lt_bytes.data() + pa, pos.size(), cores),
+                              "leon_host_letters_apply");
+                        lt_ways |= LT_ON_HOST;
+                    }
+                }
                 if (has_sums) {
                     // the restored bases where the decoder left them; the headers' and qualities' digests are stage B's
                     const uint64_t nb = R->nb;
@@ -1363,6 +1474,11 @@ void Leon::executeDecompression() {
         };
         std::cout << "checksums: " << n_blocks << " blocks verified (dna: " << way(0, true) << ", header: " << way(1, has_header) << ", quality: " << way(2, has_qual && fastq_out) << ")"
                   << (sum_mismatches.load() ? ", " + std::to_string(sum_mismatches.load()) + " mismatch(es) ignored (-ignore-checksum)" : std::string()) << std::endl;
+    }
+    if (_verbose && has_letters) {
+        const uint32_t w = lt_ways.load();
+        std::cout << "letters: " << lt_runs.size() / 2 << " run(s), " << lt_pos.size() << " byte(s) restored ("
+                  << (w == LT_ON_DEVICE ? "device" : w == LT_ON_HOST ? "host threads" : w ? "device and host threads" : "nothing to restore") << ")" << std::endl;
     }
     if (_verbose && has_header)
         std::cout << "header text: " << (hdr_text_device ? "device (k_hdr_text), " + std::to_string(hdr_blocks_fell_back.load()) + " of " + std::to_string(n_blocks) + " blocks fell back to the host decoder"
