@@ -2475,6 +2475,8 @@ int leon_rc_encode_streams(leon_dna_ctx* c, const uint8_t* syms, const uint64_t*
     for (uint64_t b = 0; b < n_streams; b++) longest = std::max(longest, begin[b + 1] - begin[b]);
     // (test hook, LEON_RC_STREAMS_ON_HOST=1: the same streams through the host chains fed by the device's modelers -- host_blocks.h --
     // so that the tests hold the two coders against each other and against the oracle on the same symbols)
+    // (the hand-over is rc_on_host's: a longest stream of 2^22 - 1025 symbols still goes to the host chains, one more to the device; tests/rc_edges.py's pack22_host /
+    // pack22_device are of these two lengths and are held to the oracle's bytes, whichever coder takes them)
     if (const char* e = getenv("LEON_RC_STREAMS_ON_HOST")) if (e[0] == '1' && longest + 1024 < (1ull << HB_COUNT_BITS)) {
         if (int rc = rc_blocks_on_host(c, dsyms.as<uint8_t>(), dbegin.as<uint64_t>(), n_streams, n_syms, SMALL_SIZES_DNA, N_SMALL_MODELS))
             return rc == 1 ? fail(c, LEON_E_HIP, "no memory for the host chains' records") : rc;

@@ -582,6 +582,8 @@ void launch_rc_encode(hipStream_t s, const uint8_t* syms, const uint64_t* blk_be
     uint32_t fast_total = RC_MAX_TOTAL;
     if (const char* e = getenv("LEON_RC_FAST_TOTAL_LOG2")) { const int v = atoi(e); if (v >= 4 && v <= 30) fast_total = 1u << v; }
     const bool big = max_block_syms + 512 >= fast_total;      // (a model's total is at most its block's symbol count + 256)
+    // (streams of 2^22 - 1024 symbols and more come here, not to the host chains' 22-bit records; tests/rc_edges.py has a stream of 2^22 - 1025 symbols and one of
+    // one more, each held to the oracle's bytes -- which coder took which is not observed there)
     // counts_apart (the read blocks' symbols, made by k_symbols: a numeric group's first model only ever sees 0..8): the byte-count models apart from
     // the 256-symbol slots (round 5); every other caller's streams -- the header stream's 14 byte models, leon_rc_encode_streams' arbitrary symbols --
     // as before.  LEON_RC_CMP=0: measurement / test, the round-4 layout for the read blocks too

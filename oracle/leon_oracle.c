@@ -842,6 +842,44 @@ int lo_rc_encode_stream(lo_rc* r, const uint8_t* models, const uint8_t* syms, ui
     free(m);
     return 0;
 }
+/* lo_rc_encode_stream with a record of every step (tests/rc_edges.py builds its directed streams from it): enc_encode's own
+ * arithmetic, its loop written with the two conditions apart so that the range-below-BOTTOM reset can be told from a byte that
+ * leaves because the ends agree on it */
+int lo_rc_profile_stream(lo_rc* r, const uint8_t* models, const uint8_t* syms, uint64_t n,
+                         const uint32_t* sizes, uint32_t n_models,
+                         uint8_t* step_bytes, uint8_t* step_reset, uint32_t* step_total, uint64_t* end_state) {
+    o0model* m = (o0model*)malloc(sizeof(o0model) * n_models);
+    for (uint32_t i = 0; i < n_models; i++) m_init(&m[i], sizes[i]);
+    rcenc* e = &r->e;
+    enc_clear(e);
+    for (uint64_t i = 0; i < n; i++) {
+        if (models[i] >= n_models || syms[i] >= m[models[i]].n) { free(m); return -1; }
+        o0model* mm = &m[models[i]];
+        const uint8_t c = syms[i];
+        const uint64_t at = e->buf.n, total = mm->r[mm->n];
+        uint8_t reset = 0;
+        e->range /= total;
+        e->low += mm->r[c] * e->range;
+        e->range *= mm->r[c + 1] - mm->r[c];
+        for (;;) {
+            if ((e->low ^ (e->low + e->range)) < RC_TOP) { /* the ends agree on the top byte */ }
+            else if (e->range < RC_BOTTOM) { e->range = (0 - e->low) & (RC_BOTTOM - 1); reset = 1; }
+            else break;
+            bv_push(&e->buf, (uint8_t)(e->low >> 56));
+            e->range <<= 8;
+            e->low <<= 8;
+        }
+        m_update(mm, c);
+        e->n_sym++;
+        if (step_bytes) step_bytes[i] = (uint8_t)(e->buf.n - at);
+        if (step_reset) step_reset[i] = reset;
+        if (step_total) step_total[i] = (uint32_t)total;
+    }
+    if (end_state) { end_state[0] = e->low; end_state[1] = e->range; }
+    enc_flush(e);
+    free(m);
+    return 0;
+}
 const uint8_t* lo_rc_bytes(const lo_rc* r, uint64_t* size) { *size = r->e.buf.n; return r->e.buf.p; }
 int lo_rc_decode_stream(const uint8_t* payload, uint64_t size, const uint8_t* models, uint8_t* out,
                         uint64_t n, const uint32_t* sizes, uint32_t n_models) {

@@ -110,6 +110,12 @@ void     lo_rc_free(lo_rc* r);
 /* encodes syms[i] with model models[i]; model_sizes[m] gives alphabet size of model m */
 int      lo_rc_encode_stream(lo_rc* r, const uint8_t* models, const uint8_t* syms, uint64_t n,
                              const uint32_t* model_sizes, uint32_t n_models);
+/* the same stream and the same bytes (lo_rc_bytes), with a record of every step: the bytes that left in it (0..8), whether the
+ * range-below-BOTTOM reset fired in it, the model's total before it; end_state[2]: low and range before the flush.  Any of the
+ * four may be NULL. */
+int      lo_rc_profile_stream(lo_rc* r, const uint8_t* models, const uint8_t* syms, uint64_t n,
+                              const uint32_t* model_sizes, uint32_t n_models,
+                              uint8_t* step_bytes, uint8_t* step_reset, uint32_t* step_total, uint64_t* end_state);
 const uint8_t* lo_rc_bytes(const lo_rc* r, uint64_t* size);
 int      lo_rc_decode_stream(const uint8_t* payload, uint64_t size, const uint8_t* models, uint8_t* out_syms,
                              uint64_t n, const uint32_t* model_sizes, uint32_t n_models);

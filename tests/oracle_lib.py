@@ -69,6 +69,7 @@ def _load():
         "lo_rc_new": (C.c_void_p, []),
         "lo_rc_free": (None, [C.c_void_p]),
         "lo_rc_encode_stream": (C.c_int, [C.c_void_p, u8p, u8p, C.c_uint64, u32p, C.c_uint32]),
+        "lo_rc_profile_stream": (C.c_int, [C.c_void_p, u8p, u8p, C.c_uint64, u32p, C.c_uint32, u8p, u8p, u32p, u64p]),
         "lo_rc_bytes": (u8p, [C.c_void_p, u64p]),
         "lo_rc_decode_stream": (C.c_int, [u8p, C.c_uint64, u8p, u8p, C.c_uint64, u32p, C.c_uint32]),
     }
@@ -260,6 +261,34 @@ def rc_encode_stream(models, syms, model_sizes):
         return _copy(p, sz.value, np.uint8).tobytes()
     finally:
         lib.lo_rc_free(r)
+
+
+class RcProfile:
+    """lo_rc_profile_stream's record: payload (== rc_encode_stream's), per step n_bytes uint8, reset uint8 (the range-below-BOTTOM
+    reset fired), total uint32 (the model's, before the step); low and range as they stand before the flush"""
+
+
+def rc_profile_stream(models, syms, model_sizes):
+    models = np.ascontiguousarray(models, dtype=np.uint8)
+    syms = np.ascontiguousarray(syms, dtype=np.uint8)
+    sizes = np.ascontiguousarray(model_sizes, dtype=np.uint32)
+    n = len(syms)
+    res = RcProfile()
+    res.n_bytes, res.reset, res.total = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint32)
+    end = np.zeros(2, dtype=np.uint64)
+    r = lib.lo_rc_new()
+    try:
+        rc = lib.lo_rc_profile_stream(r, _p(models, u8p), _p(syms, u8p), n, _p(sizes, u32p), len(sizes), _p(res.n_bytes, u8p),
+                                      _p(res.reset, u8p), _p(res.total, u32p), _p(end, u64p))
+        if rc:
+            raise ValueError("bad symbol stream")
+        sz = C.c_uint64()
+        p = lib.lo_rc_bytes(r, C.byref(sz))
+        res.payload = _copy(p, sz.value, np.uint8).tobytes()
+    finally:
+        lib.lo_rc_free(r)
+    res.low, res.range = int(end[0]), int(end[1])
+    return res
 
 
 def rc_decode_stream(payload, models, model_sizes):
