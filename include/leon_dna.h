@@ -354,6 +354,23 @@ int leon_qual_deflate_blocks_device(int device_id, const uint8_t* d_quals, const
                                     uint32_t reads_per_block, leon_block_sink sink, void* user, uint64_t first_block_id);
 /* It keeps its device buffers (about 1.5 GB after a large call) for the next call: this returns them. */
 void leon_qual_deflate_release(void);
+/* Any text in DEVICE memory written as BGZF, the blocked gzip of SAM / htslib: a series of independent gzip members
+ * of LEON_BGZF_MEMBER_TEXT bytes of text each (the last one what is left), every one a block of the same encoder as above with its own
+ * CRC-32 and ISIZE, and -- with `last` -- the 28-byte BGZF EOF marker behind them; any gzip reader reads the concatenation.
+ * The call compresses *n_taken = last ? n_text : n_text - n_text % LEON_BGZF_MEMBER_TEXT bytes; the caller carries the rest in front of
+ * the text of its next call, so the output is a function of the whole text alone, however it was split into calls.  d_text needs no
+ * alignment and is never written.  The sink follows leon_device_download_pieces' contract: pieces of at most 16 MiB, every byte of
+ * [0, *out_bytes) exactly once, in no particular order, from up to LEON_UPLOAD_THREADS threads at once; offsets count from this
+ * call's first output byte.  Non-zero from the sink: LEON_E_SINK; after any failure the caller discards what it has received.
+ * n_text == 0 (or below one member) without `last`: LEON_OK, nothing delivered; n_text == 0 with `last`: the EOF marker alone.
+ * *n_members (may be NULL): the members written, the EOF marker not counted.
+ * Refused before a device is touched, LEON_E_INVALID: d_text NULL with n_text != 0, a NULL sink, n_taken or out_bytes, a `last` other
+ * than 0 or 1.  The text goes through in slices of 512 MiB (LEON_BGZF_SLICE in the environment: bytes, rounded down to whole
+ * members), one after the other; the temporaries of a slice (about 2 bytes per byte of its text) are kept per device for the next call
+ * and go with leon_qual_deflate_release.  The call works on a stream of its own.  Errors: leon_last_error(NULL). */
+#define LEON_BGZF_MEMBER_TEXT 32768u
+int leon_text_bgzf_device(int device_id, const uint8_t* d_text, uint64_t n_text, int last, leon_piece_sink sink, void* user,
+                          uint64_t* n_taken, uint64_t* out_bytes, uint64_t* n_members);
 /* inverse: block_n_bytes = quality bytes per block without the newlines; out_off[total reads + 1] */
 int leon_host_qual_decode_blocks(const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads,
                                  const uint64_t* block_n_bytes, uint64_t n_blocks, uint8_t* out, uint64_t out_cap,

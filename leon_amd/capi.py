@@ -1,6 +1,7 @@
 """ctypes binding of include/leon_dna.h.  Mirrors the C-ABI one to one; no compute happens in Python."""
 import ctypes as C
 import os
+import threading
 
 import numpy as np
 
@@ -137,6 +138,7 @@ _EXPORTS = {
                                                 C.c_uint64]),
     "leon_qual_deflate_blocks_device": (C.c_int, [C.c_int, C.c_void_p, _u64p, C.c_uint64, C.c_uint32, SINK, C.c_void_p, C.c_uint64]),
     "leon_qual_deflate_release": (None, []),
+    "leon_text_bgzf_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_int, PIECE_SINK, C.c_void_p, _u64p, _u64p, _u64p]),
     "leon_device_trim": (None, []),
     "leon_host_qual_decode_blocks": (C.c_int, [_u8p, _u64p, _u32p, _u64p, C.c_uint64, _u8p, C.c_uint64, _u64p, C.c_uint32]),
     "leon_qual_inflate_blocks_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
@@ -541,6 +543,50 @@ def device_download_pieces(d_ptr, n_bytes, sink, device_id=0):
         if raised:
             raise err from raised[0]
         raise err
+
+
+BGZF_MEMBER_TEXT = 32768     # LEON_BGZF_MEMBER_TEXT
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def text_bgzf_device(d_text, n_text, last=1, device_id=0, sink=None):
+    """leon_text_bgzf_device: the n_text bytes at the device pointer d_text (an integer, 0 = NULL) as BGZF.  Returns (bytes of this call's
+    output, n_taken, n_members); the pieces are collected into one bytes object, every offset checked to arrive once.  sink (tests): called
+    as sink(offset, size) before a piece is kept, non-zero stops the call."""
+    lib = load_library()
+    pieces, raised = [], []
+    lock = threading.Lock()
+
+    def thunk(user, offset, address, size):
+        try:
+            if sink is not None:
+                rc = int(sink(int(offset), int(size)) or 0)
+                if rc:
+                    return rc
+            data = C.string_at(address, size) if size else b""
+            with lock:
+                pieces.append((int(offset), data))
+            return 0
+        except Exception as e:                         # noqa: BLE001 -- nothing may cross the C boundary
+            raised.append(e)
+            return 1
+    taken, out_bytes, members = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    rc = lib.leon_text_bgzf_device(device_id, C.c_void_p(int(d_text) if d_text else 0), int(n_text), int(last), PIECE_SINK(thunk), None,
+                                   C.byref(taken), C.byref(out_bytes), C.byref(members))
+    if rc:
+        err = LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+        if raised:
+            raise err from raised[0]
+        raise err
+    pieces.sort()
+    at = 0
+    for off, data in pieces:
+        if off != at:
+            raise LeonDnaError(-5, "leon_text_bgzf_device: the pieces do not tile the output (offset %d, expected %d)" % (off, at))
+        at += len(data)
+    if at != out_bytes.value:
+        raise LeonDnaError(-5, "leon_text_bgzf_device: %d bytes delivered, out_bytes = %d" % (at, out_bytes.value))
+    return b"".join(d for _, d in pieces), taken.value, members.value
 
 
 def records_format_device(d_bases, d_len, n_reads, n_bases, d_text, text_cap, lead=b"@", fastq=True, plus_kind=0, wrap=0, first_read_index=0,

@@ -371,6 +371,53 @@ __global__ void k_deflate_gather(const uint8_t* chunks, const uint32_t* sizes, c
     }
 }
 
+// ---- BGZF: any text as a series of independent gzip members (leon_text_bgzf_device) ----
+// One member = one chunk of k_deflate_chunks (LEON_BGZF_MEMBER_TEXT == DF_CHUNK bytes of text, the last one what is left):
+//   18 bytes of header (1f 8b 08 04, no time, XFL 0, OS ff, XLEN 6, the extra field 'B' 'C' 2 0 BSIZE = member bytes - 1),
+//   the sizes[c] bytes the chunk kernel wrote (its block and the empty stored block behind it, or the stored form: BFINAL 0 both),
+//   03 00 (the empty fixed block, BFINAL 1), CRC-32 and ISIZE of the chunk's text: sizes[c] + 28 bytes, at most 32 801.
+static_assert(DF_CHUNK == LEON_BGZF_MEMBER_TEXT, "a BGZF member is one chunk of k_deflate_chunks");
+constexpr uint32_t BGZF_FRAME = 28;                            // header 18 + 03 00 + CRC-32 + ISIZE
+constexpr uint32_t BGZF_MEMBER_MAX = DF_CHUNK + 5 + BGZF_FRAME;   // the stored form
+constexpr uint64_t BGZF_MAX_GROUPS = 4096;                     // k_bgzf_members' grid cap: a workgroup frames members c, c + cap, ...
+static_assert(BGZF_MEMBER_MAX <= 65536, "BSIZE is 16 bits");
+const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+__device__ const uint8_t bgzf_head[16] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0};
+
+// the chunk table of a slice of n_text bytes: begin[c] = c * DF_CHUNK for c <= n (the last entry = n_text: the CRC's segment bounds too)
+__global__ void k_bgzf_table(uint64_t n_text, uint64_t n, uint64_t* begin, uint32_t* len) {
+    const uint64_t c = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (c > n) return;
+    const uint64_t a = c * DF_CHUNK < n_text ? c * DF_CHUNK : n_text;
+    begin[c] = a;
+    if (c < n) len[c] = (uint32_t)(n_text - a < DF_CHUNK ? n_text - a : DF_CHUNK);
+}
+// member sizes as 64-bit words for the scan; msize[n] = 0, so that the exclusive sum's entry n is the slice's size
+__global__ void k_bgzf_sizes(const uint32_t* sizes, uint64_t n, uint64_t* msize) {
+    const uint64_t c = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (c <= n) msize[c] = c < n ? (uint64_t)sizes[c] + BGZF_FRAME : 0;
+}
+// Member-driven, one workgroup per member, like k_deflate_gather.  Bounds: chunks is read at [c * DF_OUT_STRIDE, + sizes[c]) with
+// sizes[c] <= len[c] + 5 (k_deflate_chunks keeps the stored form when the dynamic one is not smaller); dst is written at
+// [moff[c], moff[c + 1]) = sizes[c] + 28 bytes, moff[n] <= n * BGZF_MEMBER_MAX = what the caller allocated.  No atomics, nothing waits.
+__global__ void __launch_bounds__(256) k_bgzf_members(const uint8_t* chunks, const uint32_t* sizes, const uint32_t* len, const uint32_t* crc, const uint64_t* moff,
+                                                      uint64_t n, uint8_t* dst) {
+    const uint32_t t = threadIdx.x;
+    for (uint64_t c = blockIdx.x; c < n; c += gridDim.x) {
+        const uint8_t* s = chunks + c * (uint64_t)DF_OUT_STRIDE;
+        uint8_t* d = dst + moff[c];
+        const uint32_t m = sizes[c], bsize = m + BGZF_FRAME - 1;
+        if (t < 16) d[t] = bgzf_head[t];
+        else if (t < 18) d[t] = (uint8_t)(bsize >> (8 * (t - 16)));
+        for (uint32_t i = t; i < m; i += 256) d[18 + i] = s[i];
+        if (t >= 32 && t < 42) {                                  // (another wave than the header's)
+            const uint32_t j = t - 32;
+            const uint32_t v = j == 0 ? 3u : j == 1 ? 0u : j < 6 ? crc[c] >> (8 * (j - 2)) : len[c] >> (8 * (j - 6));
+            d[18 + m + j] = (uint8_t)v;
+        }
+    }
+}
+
 // Device buffers kept from call to call (one set per process, taken under a lock): a call per batch of a file would otherwise
 // allocate and free ~1.5 GB each time, and memory this process has freed comes back from hipMalloc at the driver's wiping
 // rate (~43 GB/s), for this call and for whoever allocates next.  Large calls go through in slices, so the set stays small.
@@ -488,6 +535,56 @@ int deflate_slice(DeflateScratch& S, int device_id, const uint8_t* d_quals, cons
     return LEON_OK;
 }
 
+// ---- leon_text_bgzf_device: the buffers it keeps (one set per device, like DeflateScratch) and a slice of its text ----
+struct BgzfScratch {
+    std::mutex mu;
+    int device = -1;
+    Grow begin, len, out, sizes, adler, crc, msize, moff, tmp, framed;
+    void drop() { for (Grow* g : {&begin, &len, &out, &sizes, &adler, &crc, &msize, &moff, &tmp, &framed}) { if (g->p) (void)hipFree(g->p); g->p = nullptr; g->cap = 0; } }
+};
+BgzfScratch* bgzf_table() { static BgzfScratch* t = new BgzfScratch[DF_MAX_DEVICES]; return t; }
+constexpr uint64_t BGZF_SLICE_TEXT = 512ull << 20;
+
+// text bytes per slice: LEON_BGZF_SLICE (tests), rounded down to whole members, at least one
+uint64_t bgzf_slice_text() {
+    uint64_t v = BGZF_SLICE_TEXT;
+    if (const char* e = getenv("LEON_BGZF_SLICE")) { const long long x = atoll(e); if (x > 0) v = (uint64_t)x; }
+    return std::max<uint64_t>(v / DF_CHUNK, 1) * DF_CHUNK;
+}
+
+// the n_text bytes at d_text as ceil(n_text / DF_CHUNK) members, delivered at `base` of the call's output; *out_size = their bytes
+int bgzf_slice(BgzfScratch& S, int device_id, hipStream_t s, const uint8_t* d_text, uint64_t n_text, uint64_t base, leon_piece_sink sink, void* user, uint64_t* out_size) {
+    const uint64_t n = (n_text + DF_CHUNK - 1) / DF_CHUNK;
+    DCHK(S.begin.ensure((n + 1) * 8)); DCHK(S.len.ensure(n * 4)); DCHK(S.sizes.ensure(n * 4)); DCHK(S.adler.ensure(n * 4)); DCHK(S.crc.ensure(n * 4));
+    DCHK(S.msize.ensure((n + 1) * 8)); DCHK(S.moff.ensure((n + 1) * 8));
+    DCHK(S.out.ensure(n * (uint64_t)DF_OUT_STRIDE)); DCHK(S.framed.ensure(n * (uint64_t)BGZF_MEMBER_MAX));
+    size_t tmp_bytes = 0;
+    DCHK(prim::ExclusiveSum(nullptr, tmp_bytes, S.msize.as<uint64_t>(), S.moff.as<uint64_t>(), n + 1, s));
+    DCHK(S.tmp.ensure(tmp_bytes));
+    const uint32_t tgrid = (uint32_t)((n + 1 + 255) / 256);
+    hipLaunchKernelGGL(k_bgzf_table, dim3(tgrid), dim3(256), 0, s, n_text, n, S.begin.as<uint64_t>(), S.len.as<uint32_t>());
+    hipLaunchKernelGGL(k_deflate_chunks, dim3((uint32_t)std::min<uint64_t>(n, 1u << 20)), dim3(DF_T), 0, s, d_text, S.begin.as<uint64_t>(), S.len.as<uint32_t>(), n,
+                       S.out.as<uint8_t>(), S.sizes.as<uint32_t>(), S.adler.as<uint32_t>());
+    DCHK(hipGetLastError());
+    DCHK(hipMemsetAsync(S.crc.p, 0, n * 4, s));
+    launch_crc32_segments(s, d_text, S.begin.as<uint64_t>(), n, crc32_tile_count(d_text, 0, n_text), S.crc.as<uint32_t>());
+    DCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_bgzf_sizes, dim3(tgrid), dim3(256), 0, s, S.sizes.as<uint32_t>(), n, S.msize.as<uint64_t>());
+    DCHK(prim::ExclusiveSum(S.tmp.p, tmp_bytes, S.msize.as<uint64_t>(), S.moff.as<uint64_t>(), n + 1, s));
+    hipLaunchKernelGGL(k_bgzf_members, dim3((uint32_t)std::min<uint64_t>(n, BGZF_MAX_GROUPS)), dim3(256), 0, s, S.out.as<uint8_t>(), S.sizes.as<uint32_t>(), S.len.as<uint32_t>(),
+                       S.crc.as<uint32_t>(), S.moff.as<uint64_t>(), n, S.framed.as<uint8_t>());
+    DCHK(hipGetLastError());
+    uint64_t total = 0;
+    DCHK(hipMemcpyAsync(&total, S.moff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
+    DCHK(hipStreamSynchronize(s));
+    if (total > n * (uint64_t)BGZF_MEMBER_MAX || total < n * (uint64_t)BGZF_FRAME) { set_create_error("leon_text_bgzf_device: the members' sizes do not add up"); return LEON_E_OVERFLOW; }
+    const int rc = staged_d2h_pieces(device_id, S.framed.p, total, [&](uint64_t offset, const void* p, uint64_t size) { return sink(user, base + offset, p, size); });
+    if (rc == 2) { set_create_error("leon_text_bgzf_device: the sink returned non-zero"); return LEON_E_SINK; }
+    if (rc) { set_create_error("leon_text_bgzf_device: copy to the host failed"); return LEON_E_HIP; }
+    *out_size = total;
+    return LEON_OK;
+}
+
 }  // namespace
 }  // namespace leon
 
@@ -519,6 +616,48 @@ extern "C" int leon_qual_deflate_blocks_device(int device_id, const uint8_t* d_q
     return LEON_OK;
 }
 
+/* any text in device memory as BGZF: the whole members of it, or with `last` all of it and the EOF marker */
+extern "C" int leon_text_bgzf_device(int device_id, const uint8_t* d_text, uint64_t n_text, int last, leon_piece_sink sink, void* user,
+                                     uint64_t* n_taken, uint64_t* out_bytes, uint64_t* n_members) {
+    auto refuse = [](const char* why) { set_create_error(std::string("leon_text_bgzf_device: ") + why); return (int)LEON_E_INVALID; };
+    if (!d_text && n_text) return refuse("d_text is NULL with n_text != 0");
+    if (!sink) return refuse("sink is NULL");
+    if (!n_taken) return refuse("n_taken is NULL");
+    if (!out_bytes) return refuse("out_bytes is NULL");
+    if (last != 0 && last != 1) return refuse("last is neither 0 nor 1");
+    const uint64_t taken = last ? n_text : n_text - n_text % DF_CHUNK;
+    *n_taken = taken; *out_bytes = 0;
+    if (n_members) *n_members = 0;
+    uint64_t at = 0, members = 0;
+    if (taken) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) { (void)hipGetLastError(); set_create_error("leon_text_bgzf_device: no such HIP device"); return LEON_E_NO_DEVICE; }
+        if (device_id >= DF_MAX_DEVICES) return refuse("device ordinal beyond the scratch table");
+        DCHK(hipSetDevice(device_id));
+        BgzfScratch& S = bgzf_table()[device_id];
+        std::lock_guard<std::mutex> lock(S.mu);
+        S.device = device_id;
+        // a stream of its own: the call runs beside calls on the contexts' streams
+        struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
+        DCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+        const uint64_t slice = bgzf_slice_text();
+        for (uint64_t a = 0; a < taken; a += slice) {              // sequential: a slice's base is the sum of the sizes before it
+            const uint64_t m = std::min(slice, taken - a);
+            uint64_t size = 0;
+            const int rc = bgzf_slice(S, device_id, st.s, d_text + a, m, at, sink, user, &size);
+            if (rc) return rc;
+            at += size; members += (m + DF_CHUNK - 1) / DF_CHUNK;
+        }
+    }
+    if (last) {
+        if (sink(user, at, kBgzfEof, sizeof kBgzfEof)) { set_create_error("leon_text_bgzf_device: the sink returned non-zero"); return LEON_E_SINK; }
+        at += sizeof kBgzfEof;
+    }
+    *out_bytes = at;
+    if (n_members) *n_members = members;
+    return LEON_OK;
+}
+
 /* the device buffers leon_qual_deflate_blocks_device keeps from call to call (about 1.5 GB after a large call) */
 extern "C" void leon_qual_deflate_release(void) {
     int before = -1;
@@ -529,6 +668,10 @@ extern "C" void leon_qual_deflate_release(void) {
         if (S.device >= 0 && hipSetDevice(S.device) == hipSuccess) S.drop();
         S.device = -1;
         std::vector<uint8_t>().swap(S.h);
+        BgzfScratch& B = bgzf_table()[d];                        // (leon_text_bgzf_device's set goes with it)
+        std::lock_guard<std::mutex> lock_b(B.mu);
+        if (B.device >= 0 && hipSetDevice(B.device) == hipSuccess) B.drop();
+        B.device = -1;
     }
     if (had_device) (void)hipSetDevice(before);
 }

@@ -303,6 +303,7 @@ void Leon::run(int argc, char* argv[]) {
             else if (a == "-checksum") _checksum = true;
             else if (a == "-ignore-checksum") _ignoreChecksum = true;
             else if (a == "-letters") _letters = true;
+            else if (a == "-gz") _gz = true;
             else if (a == "-qual-deflate") { _qualDeflate = need("-qual-deflate"); (void)qual_encoder_choice(_qualDeflate); }
             else if (a == "-header-text") { _headerText = need("-header-text"); (void)header_text_choice(_headerText); }
             else if (a == "-record-text") { _recordText = need("-record-text"); (void)record_text_choice(_recordText); }
@@ -314,6 +315,7 @@ void Leon::run(int argc, char* argv[]) {
         if (_checksum && _decompress) throw Exception("option -checksum belongs to -c: -d verifies whenever the container holds checksums (-ignore-checksum to go on past a mismatch)");
         if (_ignoreChecksum && _compress) throw Exception("option -ignore-checksum belongs to -d");
         if (_letters && _decompress) throw Exception("option -letters belongs to -c: -d restores the letters whenever the container holds them");
+        if (_gz && _compress) throw Exception("option -gz belongs to -d");
         if (_seqOnly) _noHeader = _noQual = true;             // "same as -noheader -noqual", /root/reference/README.md:56
         execute();
     } catch (const Exception&) {
@@ -865,14 +867,16 @@ void Leon::executeDecompression() {
     // X.fastq.leon -> X.fastq.d (/root/reference/scripts/simple_test.sh:54,62)
     std::string stem = _inputFilename;
     if (ends_with(stem, ".leon")) stem.resize(stem.size() - 5);
-    _outputFilename = stem + ".d";
+    // `-gz`: X.fastq.d.gz, BGZF written under a temporary name and renamed at the very end
+    _outputFilename = stem + (_gz ? ".d.gz" : ".d");
+    const std::string out_path = _gz ? _outputFilename + ".tmp" : _outputFilename;
     struct Fd {
         int fd = -1; std::string path; bool keep = false;
         ~Fd() { if (fd >= 0) ::close(fd); if (!keep && !path.empty()) std::remove(path.c_str()); }     // a failed run leaves no partial output behind
     } ofd;
-    ofd.fd = ::open(_outputFilename.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    ofd.fd = ::open(out_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
     if (ofd.fd < 0) throw Exception("cannot write " + _outputFilename);
-    ofd.path = _outputFilename;
+    ofd.path = out_path;
     const bool fastq_out = !fasta_in && has_qual;               // "-noqual ... will decompress to fasta"
     PlusLines plus;                                             // FASTQ '+' lines that are not bare (absent: all of them are)
     if (fastq_out && has_header && in.exists(DS_PLUS_LINES)) {
@@ -939,6 +943,7 @@ void Leon::executeDecompression() {
         uint64_t file_base0 = 0;                                 // the round's first base in the file's bases (the letter tables' positions)
         const uint8_t* bases() const { return own_bases.p ? own_bases.p.get() : dna->bases.p.get() + base0; }
         bool on_device = false;                                  // `-record-text device`: the round's bases are in dna->d_bases
+        bool last = false;                                       // the file's last round (`-gz`: its text closes the BGZF stream)
         bool hdr_in_set = false;                                 // ... and its header text lies in the device's header-text set:
         const uint8_t* d_hdr = nullptr; const uint64_t* d_hdr_off = nullptr; uint64_t d_hdr_size = 0;
         RawBytes own_bases;                                      // (a round that had to come back to the host: no device memory for its text)
@@ -954,6 +959,58 @@ void Leon::executeDecompression() {
     };
     std::unique_ptr<char[]> text;                                // the writing stage's records (never zero-filled)
     uint64_t text_cap = 0;
+    // `-gz`: a round's text leaves as BGZF members of LEON_BGZF_MEMBER_TEXT bytes, compressed where the device has it
+    // (leon_text_bgzf_device); what does not fill a member waits in gz_carry and goes in front of the next round's text, so the file is
+    // the same bytes however the text was cut into rounds and whoever formatted them.  All of it is stage C's (one round at a time).
+    constexpr uint64_t GZ_HEAD = LEON_BGZF_MEMBER_TEXT;         // room in front of a round's text for the carry (always below one member)
+    struct GzOut { int fd; uint64_t at; };
+    std::vector<uint8_t> gz_carry;
+    uint64_t gz_file_at = 0, gz_members = 0, gz_text = 0;
+    bool gz_closed = false;
+    const leon_piece_sink gz_piece = [](void* user, uint64_t offset, const void* bytes, uint64_t n) -> int {
+        const GzOut* o = static_cast<const GzOut*>(user);
+        for (uint64_t done = 0; done < n;) {
+            const ssize_t got = ::pwrite(o->fd, static_cast<const char*>(bytes) + done, (size_t)(n - done), (off_t)(o->at + offset + done));
+            if (got <= 0) return 1;
+            done += (uint64_t)got;
+        }
+        return 0;
+    };
+    // n_all bytes of device memory (the carry and a text behind it) through the call; returns the bytes it took
+    auto gz_compress = [&](const uint8_t* d_all, uint64_t n_all, bool last) -> uint64_t {
+        GzOut o{ofd.fd, gz_file_at};
+        uint64_t taken = 0, out_bytes = 0, members = 0;
+        const int rc = leon_text_bgzf_device(device_for(0), d_all, n_all, last ? 1 : 0, gz_piece, &o, &taken, &out_bytes, &members);
+        if (rc == LEON_E_SINK) throw Exception("cannot write " + _outputFilename);
+        if (rc != LEON_OK) throw Exception(std::string("leon_text_bgzf_device: ") + leon_last_error(nullptr));
+        gz_file_at += out_bytes; gz_members += members; gz_text += taken;
+        if (last) gz_closed = true;
+        return taken;
+    };
+    // a text the host formatted, with GZ_HEAD bytes of room in front of it: up it goes behind the carry, in pieces of whole members of at
+    // most one slice of the call; a piece the device has no memory for is halved
+    auto gz_from_host = [&](uint8_t* p_text, uint64_t n_text, bool last) {
+        const uint64_t nc = gz_carry.size();
+        uint8_t* const all = p_text - nc;
+        if (nc) memcpy(all, gz_carry.data(), nc);
+        const uint64_t n_all = nc + n_text, todo = last ? n_all : n_all - n_all % GZ_HEAD;
+        uint64_t piece = 512ull << 20;
+        if (const char* e = getenv("LEON_BGZF_SLICE")) { const long long v = atoll(e); if (v > 0) piece = (uint64_t)v; }
+        piece = std::max<uint64_t>(piece / GZ_HEAD, 1) * GZ_HEAD;
+        for (uint64_t at = 0; at < todo;) {
+            const uint64_t m = std::min(piece, todo - at);
+            struct Dev { void* p = nullptr; ~Dev() { leon_device_free(p); } } d;
+            if (leon_device_alloc(device_for(0), m + 64, &d.p) != LEON_OK) {
+                if (piece <= GZ_HEAD) throw Exception("-gz: the device has no memory for the text of one BGZF member");
+                piece = std::max<uint64_t>(piece / 2 / GZ_HEAD, 1) * GZ_HEAD;
+                continue;
+            }
+            if (leon_device_upload(device_for(0), d.p, all + at, m) != LEON_OK) throw Exception(std::string("leon_device_upload: ") + leon_last_error(nullptr));
+            if (gz_compress((const uint8_t*)d.p, m, last && at + m == todo) != m) throw Exception("leon_text_bgzf_device: a piece of whole members was not taken whole");
+            at += m;
+        }
+        gz_carry.assign(all + todo, all + n_all);
+    };
     double t_read = 0, t_dna = 0, t_hdr = 0, t_qual = 0, t_text = 0, t_write = 0, t_writer_wait = 0;
     auto lap = [](std::chrono::steady_clock::time_point& t, double& acc) { const auto n = std::chrono::steady_clock::now(); acc += std::chrono::duration<double>(n - t).count(); t = n; };
     // the writing stage: every read's place in the text is known from the lengths, so a round is formatted by all cores at
@@ -973,14 +1030,16 @@ void Leon::executeDecompression() {
         }
         const uint64_t n_text = rec_off[g_reads];
         if (n_text != R->n_text) throw Exception(_inputFilename + ": the decoded reads do not add up to their blocks' sizes");
-        if (n_text > text_cap) { text.reset(); text_cap = n_text + n_text / 16; text.reset(new char[text_cap]); }
+        const uint64_t head = _gz ? GZ_HEAD : 0;
+        if (head + n_text > text_cap) { text.reset(); text_cap = head + n_text + n_text / 16; text.reset(new char[text_cap]); }
+        char* const tbase = text.get() + head;
         const uint32_t n_fmt = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_cpu, g_reads / 4096 + 1));
         std::mutex err_mu;
         std::string werr;
         auto format_range = [&](uint64_t ra, uint64_t rb) {
             size_t hint = plus.lower(R->read_index + ra);
             for (uint64_t r = ra; r < rb; r++) {
-                char* w = text.get() + rec_off[r];
+                char* w = tbase + rec_off[r];
                 *w++ = lead;
                 if (has_header) { const uint64_t hl = R->hdr_off[r + 1] - R->hdr_off[r]; memcpy(w, R->hdr.data() + R->hdr_off[r], hl); w += hl; }
                 else { const std::string idx = std::to_string(R->read_index + r); memcpy(w, idx.data(), idx.size()); w += idx.size(); }
@@ -1001,11 +1060,12 @@ void Leon::executeDecompression() {
                     *w++ = '\n'; memcpy(w, R->qual.data() + R->qual_off[r], len); w += len; *w++ = '\n';
                 }
             }
+            if (_gz) return;                                      // (compressed below, once the whole round is there)
             // this thread's share of the text goes out as soon as it is formatted
             uint64_t at = rec_off[ra];
             const uint64_t end = rec_off[rb];
             while (at < end) {
-                const ssize_t got = ::pwrite(ofd.fd, text.get() + at, (size_t)std::min<uint64_t>(end - at, 1ull << 30), (off_t)(R->file_off + at));
+                const ssize_t got = ::pwrite(ofd.fd, tbase + at, (size_t)std::min<uint64_t>(end - at, 1ull << 30), (off_t)(R->file_off + at));
                 if (got <= 0) { std::lock_guard<std::mutex> g(err_mu); werr = "cannot write " + _outputFilename; return; }
                 at += (uint64_t)got;
             }
@@ -1017,6 +1077,7 @@ void Leon::executeDecompression() {
             for (auto& t : th) t.join();
         }
         if (!werr.empty()) throw Exception(werr);
+        if (_gz) gz_from_host(reinterpret_cast<uint8_t*>(tbase), n_text, R->last);
         lap(tl, t_text);
     };
     // Three stages, each round through them in turn, the stages of different rounds side by side:
@@ -1056,7 +1117,9 @@ void Leon::executeDecompression() {
         auto upload = [&](void* d, const void* src, uint64_t n) {
             if (leon_device_upload(rt_dev, d, src, n) != LEON_OK) throw Exception(std::string("leon_device_upload: ") + leon_last_error(nullptr));
         };
-        if (leon_device_alloc(rt_dev, n_text + 64, &d_text.p) != LEON_OK) return false;
+        const uint64_t head = _gz ? GZ_HEAD : 0;                  // `-gz`: room for the carry right in front of the text
+        if (leon_device_alloc(rt_dev, head + n_text + 64, &d_text.p) != LEON_OK) return false;
+        uint8_t* const d_txt = (uint8_t*)d_text.p + head;
         if (fastq_out && !R->d_qual) {
             if (leon_device_alloc(rt_dev, g_bases + 64, &d_qual.p) != LEON_OK) return false;
             upload(d_qual.p, R->qual.data(), g_bases);
@@ -1077,10 +1140,22 @@ void Leon::executeDecompression() {
         lay.wrap = (uint32_t)std::min<uint64_t>(wrap, 0xFFFFFFFFull); lay.first_read_index = R->read_index; lay.hdr_bytes = hb;
         uint64_t size = 0;
         const int rc = leon_records_format_device(rt_dev, &lay, (const uint8_t*)R->dna->d_bases + R->base0, (const uint32_t*)R->dna->d_lens + R->read0, g_reads, g_bases,
-                                                  hp, ho, quals, (uint8_t*)d_text.p, n_text, nullptr, &size);
+                                                  hp, ho, quals, d_txt, n_text, nullptr, &size);
         if (rc == LEON_E_OVERFLOW || (rc == LEON_OK && size != n_text)) throw Exception(_inputFilename + ": the decoded reads do not add up to their blocks' sizes");
         if (rc != LEON_OK) throw Exception(std::string("leon_records_format_device: ") + leon_last_error(nullptr));
         R->release_quals();
+        if (_gz) {                                               // the text never crosses to the host uncompressed: one call instead of the downloads
+            const uint64_t nc = gz_carry.size(), n_all = nc + n_text;
+            uint8_t* const d_all = d_txt - nc;
+            if (nc) upload(d_all, gz_carry.data(), nc);
+            const uint64_t taken = gz_compress(d_all, n_all, R->last);
+            gz_carry.resize(n_all - taken);
+            if (!gz_carry.empty() && leon_device_download(rt_dev, gz_carry.data(), d_all + taken, gz_carry.size()) != LEON_OK)
+                throw Exception(std::string("leon_device_download: ") + leon_last_error(nullptr));
+            rt_rounds_on_device++;
+            lap(tl, t_text);
+            return true;
+        }
         // the text comes back in pinned pieces, each pwritten where it landed; a download keeps up to three copies in flight (PCIe's
         // rate), the page cache takes more writers than that: four downloads side by side, each its own quarter of the text
         struct Out { int fd; uint64_t at; };
@@ -1100,7 +1175,7 @@ void Leon::executeDecompression() {
         auto download = [&](uint32_t i) {
             const uint64_t a = n_pieces * i / n_dl * piece, b = std::min(n_text, n_pieces * (i + 1) / n_dl * piece);
             Out out{ofd.fd, R->file_off + a};
-            dl_rc[i] = leon_device_download_pieces(rt_dev, (const uint8_t*)d_text.p + a, b - a, piece_out, &out);
+            dl_rc[i] = leon_device_download_pieces(rt_dev, d_txt + a, b - a, piece_out, &out);
             if (dl_rc[i] != LEON_OK) dl_err[i] = leon_last_error(nullptr);       // (the message is the calling thread's)
         };
         {
@@ -1213,6 +1288,7 @@ void Leon::executeDecompression() {
             R->read_index = read_index; R->g_reads = g_reads; R->g_bases = g_bases;
             R->dna = G; R->base0 = base0; R->read0 = read0; R->file_base0 = bases_out;
             R->on_device = g_device;
+            R->last = g1 == n_blocks;
             if (g_device) G->rounds_left++;
             if (has_header && !hdr_on_device) gather(GROUP_HEADER, thdr, 3, g0, nb, R->pay_h, R->off_h);
             R->block0 = g0;
@@ -1458,9 +1534,14 @@ void Leon::executeDecompression() {
         while (!pending.empty()) { pending.front().get(); pending.pop_front(); }
         lap(tl, t_write);
     }
+    if (_gz && !gz_closed) {                                    // (a file without a round: the EOF marker alone)
+        if (!gz_carry.empty()) throw Exception("-gz: text was left over behind the last round");
+        (void)gz_compress(nullptr, 0, true);
+    }
     if (::close(ofd.fd) != 0) { ofd.fd = -1; throw Exception("cannot write " + _outputFilename); }
     ofd.fd = -1;
     if (read_index != n_reads) throw Exception("the block tables do not add up to the header's read count");
+    if (_gz && std::rename(out_path.c_str(), _outputFilename.c_str()) != 0) throw Exception("cannot write " + _outputFilename);
     ofd.keep = true;
     std::cout << n_reads << " reads, " << bases_out << " bases decoded from " << n_blocks << " blocks, written to " << _outputFilename << std::endl;
     if (_verbose)
@@ -1494,14 +1575,16 @@ void Leon::executeDecompression() {
                                                             (qi_rounds_no_memory.load() ? ", " + std::to_string(qi_rounds_no_memory.load()) + " round(s) on the host threads for want of device memory" : std::string())
                                                       : std::string("host threads"))
                   << std::endl;
+    if (_verbose && _gz)
+        std::cout << "output: BGZF on the device (k_deflate_chunks, k_bgzf_members), " << gz_members << " member(s), " << gz_text << " -> " << gz_file_at << " bytes" << std::endl;
     if (_testFile) testDecompressedFile();
 }
 
 // -test-file: "check decompressed file against original" (/root/reference/INSTALL:22): X.fastq.d against X.fastq (or X.fastq.gz) beside it
 void Leon::testDecompressedFile() {
-    std::string orig = _outputFilename.substr(0, _outputFilename.size() - 2);
+    std::string orig = _outputFilename.substr(0, _outputFilename.size() - (_gz ? 5 : 2));      // X.fastq.d or, under -gz, X.fastq.d.gz
     struct stat st_o, st_d;
-    const bool plain = ::stat(orig.c_str(), &st_o) == 0 && S_ISREG(st_o.st_mode);
+    const bool plain = !_gz && ::stat(orig.c_str(), &st_o) == 0 && S_ISREG(st_o.st_mode);       // (-gz: read through gzread below)
     if (plain && ::stat(_outputFilename.c_str(), &st_d) == 0) {
         // both files are plain: compared in slices by all cores (pread at disjoint offsets); the first difference is the lowest one found
         int fa = ::open(orig.c_str(), O_RDONLY), fb = ::open(_outputFilename.c_str(), O_RDONLY);

@@ -49,6 +49,7 @@ public:
     bool _checksum = false;               // -c: -checksum: a CRC-32 per read block and stream in leon/metadata/checksums; -d verifies it whenever it is there
     bool _ignoreChecksum = false;         // -d: -ignore-checksum: a mismatch is a WARNING on stderr, the file is kept
     bool _letters = false;                // -c: -letters: lower-case runs and bytes outside ACGTN kept in leon/metadata/letter_*; -d puts them back whenever they are there
+    bool _gz = false;                     // -d: -gz: the restored file written as BGZF (X.d.gz), compressed on the device
     std::string _qualDeflate;             // -qual-deflate host|device|auto; empty = not given: zlib on the host threads (the reference's bytes)
     std::string _headerText;              // -d: -header-text host|device|auto; empty = not given: the header text on the host threads
     std::string _recordText;              // -d: -record-text host|device|auto; empty = not given: the records formatted on the host threads

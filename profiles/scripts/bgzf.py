@@ -1,0 +1,132 @@
+"""The restored file written as BGZF on the device (k_deflate_chunks, k_crc32_tiles, k_bgzf_members; `leon -d -gz`).
+
+  bgzf.py --kernel [N]                 the FASTQ text of N synthetic reads x 150 bp (default 10 M: 3.65 GB) in device memory: one warm-up
+                                       call of leon_text_bgzf_device on its first member and TWO whole calls whose output is counted and
+                                       dropped by the sink; then, for the first 64 MiB, the output kept and read back with gzip.decompress,
+                                       and the same text through zlib (level 6, and Z_RLE) on one thread for the sizes.  The run to put under
+                                       `rocprofv3 --kernel-trace --stats` (kernel times come from there; the JSON line carries the calls'
+                                       wall times, which include the copy of the output to the host); text bytes / a kernel's time is to be
+                                       read against the float4 copy measured on this chip, 6.29 TB/s
+  bgzf.py --cli N --parent LEON        `leon -d`, `leon -d -gz` and the parent commit's `leon -d` on the lossless container of an N-read
+                                       150 bp FASTQ in a RAM-backed directory, alternating, three each, -header-text device -record-text
+                                       device -qual-inflate device on every side; the output sizes and the `time:` and `output:` lines of
+                                       -verbose 1
+Prints one JSON line."""
+import argparse
+import ctypes as C
+import gzip
+import json
+import os
+import subprocess
+import sys
+import threading
+import time
+import zlib
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+from leon_amd import capi  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--kernel", type=int, nargs="?", const=10_000_000, default=0)
+ap.add_argument("--cli", type=int, default=0)
+ap.add_argument("--parent", default="")
+ap.add_argument("--dir", default="/dev/shm/leon_bgzf")
+args = ap.parse_args()
+assert torch.cuda.is_available(), "needs the GPU"
+dev = torch.device("cuda", 0)
+L = 150
+COPY_TBS = 6.29                                                   # the float4 copy on this chip
+SAMPLE = 64 << 20
+
+
+def kernel():
+    N = args.kernel
+    os.makedirs(args.dir, exist_ok=True)
+    fq = os.path.join(args.dir, "reads.fastq")
+    bench.write_fastq(fq, N, L, dev)
+    text = np.fromfile(fq, dtype=np.uint8)
+    n = len(text)
+    d = torch.empty(n + 64, dtype=torch.uint8, device=dev)
+    d[:n] = torch.from_numpy(text).to(dev)
+    torch.cuda.synchronize()
+    os.remove(fq)
+    lib = capi.load_library()
+    counted, lock = [0], threading.Lock()
+
+    def drop(user, offset, address, size):                        # (called from the library's copy threads)
+        with lock:
+            counted[0] += size
+        return 0
+    sink = capi.PIECE_SINK(drop)
+    taken, out_bytes, members = C.c_uint64(), C.c_uint64(), C.c_uint64()
+
+    def call(n_text):
+        counted[0] = 0
+        rc = lib.leon_text_bgzf_device(0, C.c_void_p(d.data_ptr()), n_text, 1, sink, None, C.byref(taken), C.byref(out_bytes), C.byref(members))
+        assert rc == 0, lib.leon_last_error(None)
+        assert counted[0] == out_bytes.value and taken.value == n_text
+    call(capi.BGZF_MEMBER_TEXT)                                   # (code objects loaded, scratch for one member)
+    ms = []
+    for _ in range(2):
+        t0 = time.perf_counter()
+        call(n)
+        ms.append(round((time.perf_counter() - t0) * 1e3, 2))
+    whole = {"members": members.value, "out_bytes": out_bytes.value}
+    m = min(n, SAMPLE)
+    sample = text[:m].tobytes()
+    got, _, _ = capi.text_bgzf_device(d.data_ptr(), m)
+    t0 = time.perf_counter()
+    z6 = len(zlib.compress(sample, 6))
+    z6_s = time.perf_counter() - t0
+    c = zlib.compressobj(6, zlib.DEFLATED, -15, 9, zlib.Z_RLE)
+    zrle = len(c.compress(sample) + c.flush())
+    print(json.dumps({"reads": N, "text_bytes": n, "leon_text_bgzf_device_ms": ms, **whole, "text_per_out": round(n / whole["out_bytes"], 4),
+                      "sample_bytes": m, "sample_out_bytes": len(got), "sample_reads_back": gzip.decompress(got) == sample,
+                      "sample_zlib6_bytes": z6, "sample_zlib6_one_thread_gb_s": round(m / z6_s / 1e9, 4), "sample_zlib_rle_bytes": zrle,
+                      "float4_copy_tb_s": COPY_TBS,
+                      "note": "kernel times: the rocprofv3 --kernel-trace --stats run around this process; text bytes / a kernel's time against float4_copy_tb_s"}))
+
+
+def cli():
+    N = args.cli
+    assert args.parent, "--cli needs --parent: the parent commit's leon"
+    os.makedirs(args.dir, exist_ok=True)
+    fq = os.path.join(args.dir, "reads.fastq")
+    bench.write_fastq(fq, N, L, dev)
+    torch.cuda.empty_cache()
+    leon = os.path.join(ROOT, "leon_amd", "lib", "leon")
+    out = {"reads": N, "fastq_bytes": os.path.getsize(fq), "cpus": len(os.sched_getaffinity(0))}
+    device = ["-header-text", "device", "-record-text", "device", "-qual-inflate", "device"]
+
+    def timed(cmd):
+        t = time.time()
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        assert r.returncode == 0, (cmd, r.stdout[-400:], r.stderr[-400:])
+        return round(time.time() - t, 2), r.stdout
+    s, _ = timed([leon, "-file", fq, "-c", "-lossless", "-qual-deflate", "device"])
+    out["compress_s"] = s
+    container = fq + ".leon"
+    ways = [("plain", leon, [], ".d"), ("gz", leon, ["-gz"], ".d.gz"), ("parent", args.parent, [], ".d")]
+    times = {w: [] for w, _, _, _ in ways}
+    lines, sizes = {}, {}
+    for rep in range(3):
+        for w, binary, opts, suffix in ways:
+            s, log = timed([binary, "-file", container, "-d", "-verbose", "1"] + opts + device)
+            times[w].append(s)
+            print("decompress %s: %.2f s" % (w, s), file=sys.stderr, flush=True)
+            if rep == 0:
+                lines[w] = [l for l in log.splitlines() if l.startswith(("time:", "output:"))]
+                sizes[w] = os.path.getsize(fq + suffix)
+            os.remove(fq + suffix)
+    out["decompress_s"] = {"seconds": times, "verbose": lines, "output_bytes": sizes}
+    for f in os.listdir(args.dir):
+        os.remove(os.path.join(args.dir, f))
+    print(json.dumps(out))
+
+
+kernel() if args.kernel else cli()
