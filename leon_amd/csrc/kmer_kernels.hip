@@ -509,7 +509,7 @@ int leon_kmer_solid(int device_id, const uint8_t* bases, const uint64_t* offsets
                     uint64_t max_keys_per_pass, uint64_t* out, uint64_t out_cap, uint64_t* n_solid, uint64_t* histogram) {
     if (!n_solid || (n_reads && (!bases || !offsets))) return LEON_E_INVALID;
     *n_solid = 0;
-    if (!n_reads) return LEON_OK;
+    if (!n_reads) { if (histogram) memset(histogram, 0, 256 * sizeof(uint64_t)); return LEON_OK; }     // (as the device form leaves it)
     if (hipSetDevice(device_id) != hipSuccess) { set_create_error("kmer_solid: no such HIP device"); return LEON_E_NO_DEVICE; }
     const uint64_t nb = offsets[n_reads] - offsets[0];
     std::vector<uint64_t> rel(n_reads + 1);

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import common
+import kmer_shapes
 import oracle_lib as O
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("rc_chains")]
@@ -249,6 +250,12 @@ def test_final_key_filter_under_every_kmer_size(k0):
         reads.append(bytes(r))
     b2, off2 = O.reads_to_arrays(reads)
     _full_compare(b2, off2, k, 100, window=32)
+
+
+@pytest.mark.parametrize("k", [3, 4])
+def test_encode_path_below_k5(k):
+    # the two k-mer sizes the ABI allows below the 5 .. 63 of the test above (a minimizer of k bases, k-mers of 6 and 8 bits)
+    _full_compare(*common.synthetic(600, 90, 1500, seed=100 + k), k, 200, window=48)
 
 
 def test_other_kmer_sizes_and_lengths():
@@ -611,6 +618,8 @@ def test_device_solid_kmer_counting(k, min_ab, maxkeys):
     all1 = O.count_solid(bases, off, k, 1)
     assert int(hist.sum()) == len(all1) // w                      # every distinct k-mer lands in one histogram bin
     assert int(hist[min_ab:].sum()) == len(exp) // w
+    reads = tuple(bytes(bases[int(off[i]):int(off[i + 1])]) for i in range(len(off) - 1))
+    assert np.array_equal(hist, kmer_shapes.ref_hist(kmer_shapes.ref_counts(reads, k)))      # and every bin is an independent count's
     tai = max(len(got) // w * common.NB_BITS_PER_KMER, 1000)
     bl = O.Bloom(tai, k)
     bl.insert(exp)
