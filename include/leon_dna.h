@@ -404,6 +404,53 @@ int leon_crc32_segments_device(int device_id, const uint8_t* d_bytes, uint64_t n
 /* zlib's crc32 on n_threads host threads (0 = all this process may use); needs no GPU */
 int leon_host_crc32_segments(const uint8_t* bytes, uint64_t n_bytes, const uint64_t* seg_off, uint64_t n_seg, uint32_t n_threads, uint32_t* crc);
 
+/* -- BGZF input inflated on the device --
+ * A BGZF file is a series of gzip members of at most 64 KiB, each with an extra subfield B C 02 00 BSIZE (the member's size - 1) and,
+ * behind its raw deflate stream, CRC-32 and ISIZE of its text; an empty member (ISIZE 0) is the EOF marker and may stand anywhere.
+ *
+ * leon_host_bgzf_members walks the members of bytes[0, n_bytes) (no GPU).  A member must begin 1f 8b 08 with FLG exactly 4; the XLEN
+ * bytes of subfields are walked for B C 02 00 BSIZE, others in front of it are skipped; the deflate stream begins at 12 + XLEN and
+ * BSIZE + 1 must hold the header and the 8-byte trailer.  member_off (off_cap entries) receives the members' first bytes and, as entry
+ * *n_members, the end of the last whole one, which is also *consumed; *n_text = the sum of their ISIZE (a member whose ISIZE is above
+ * 65 536 counts none: the inflate refuses it).  *stop says why the walk ended:
+ *   LEON_BGZF_WHOLE      the range ends with a member's last byte (or is empty);
+ *   LEON_BGZF_PARTIAL    last == 0: the member at *consumed is cut short by the end of the range, in its header, its payload or its
+ *                        trailer -- "not consumed": the caller puts those bytes in front of the next range.  LEON_OK;
+ *   LEON_BGZF_TRUNCATED  the same with last == 1 (the range ends the file): LEON_E_INVALID "BGZF member N (at byte X) is truncated";
+ *   LEON_BGZF_FOREIGN    the bytes at *consumed are no BGZF member (a gzip member without the subfield, a BSIZE too small for its own
+ *                        header, anything else): LEON_E_INVALID "no BGZF member at byte X (member N)".
+ * The outputs are filled in every one of these cases.  LEON_E_OVERFLOW when the table needs more than off_cap entries (*n_members + 1).
+ *
+ * leon_host_bgzf_inflate (no GPU) inflates members [member_off[i], member_off[i + 1]) of bytes into text, back to back: zlib's inflate
+ * on a raw stream, one member per thread (n_threads, 0 = all this process may use).  A member decodes when it is a BGZF member of
+ * exactly its span, its stream ends with the last byte in front of the trailer, gives exactly ISIZE <= 65 536 bytes, and their CRC-32
+ * is the trailer's.  *n_text = the bytes of text; LEON_E_OVERFLOW "the text needs N bytes" when text_cap is smaller, nothing decoded.
+ * LEON_E_INVALID "BGZF member N (at byte X) does not decode" names the smallest member that fails.
+ *
+ * leon_bgzf_inflate_device does the same into DEVICE memory (inflate_kernels.hip: k_bgzf_inflate, one wave per member, into 16-byte
+ * aligned shares of a temporary; crc_kernels.hip over them; k_bgzf_gather to d_text, which needs no alignment).  bytes and member_off
+ * are HOST memory.  The verdict -- code and message -- is the host function's on the same arguments; arguments are refused before a
+ * device is touched.  The members go through in launches of at most max_members_per_launch (0 = 4 096) members; a launch writes to
+ * d_text only when every member of it has passed, so after a refusal of member N no byte of a member behind N's launch is written.
+ * The kernels and the small copies run on a stream of the call's own; a launch's bytes go up in one blocking copy (through pinned
+ * pieces from 64 MiB on, staging.h), complete before its kernel is launched; the temporaries live for the call and are bounded by
+ * the launch size (at most 64 KiB of text and of payload per member).  n_symbols (host, may be NULL): the literal/length symbols
+ * decoded (measurement).  Errors: leon_last_error(NULL). */
+#define LEON_BGZF_WHOLE 0u
+#define LEON_BGZF_PARTIAL 1u
+#define LEON_BGZF_TRUNCATED 2u
+#define LEON_BGZF_FOREIGN 3u
+int leon_host_bgzf_members(const uint8_t* bytes, uint64_t n_bytes, int last, uint64_t* member_off, uint64_t off_cap, uint64_t* n_members,
+                           uint64_t* n_text, uint64_t* consumed, uint32_t* stop);
+int leon_host_bgzf_inflate(const uint8_t* bytes, uint64_t n_bytes, const uint64_t* member_off, uint64_t n_members, uint8_t* text, uint64_t text_cap,
+                           uint64_t* n_text, uint32_t n_threads);
+int leon_bgzf_inflate_device(int device_id, const uint8_t* bytes, uint64_t n_bytes, const uint64_t* member_off, uint64_t n_members, uint8_t* d_text,
+                             uint64_t text_cap, uint64_t* n_text, uint32_t max_members_per_launch, uint64_t* n_symbols);
+/* Page-locked host memory for a caller that downloads into the same buffers again and again (the reader of `leon -c -input-inflate
+ * device`): leon_device_download into it is one direct copy.  Freed with leon_host_pinned_free (NULL is allowed). */
+int leon_host_pinned_alloc(int device_id, uint64_t bytes, void** ptr);
+void leon_host_pinned_free(void* ptr);
+
 /* -- every sequence letter kept: lower-case runs and bytes outside ACGTN --
  * For the n_bytes bases at d_bases (the reads' bases one after another): a RUN is a maximal interval [begin, end) of bytes in
  * 'a'..'z'; an ODD byte is one that, folded to upper case when it is lower-case, is none of A C G T N; the FOLDED buffer holds the

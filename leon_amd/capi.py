@@ -145,6 +145,12 @@ _EXPORTS = {
                                                    C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "leon_crc32_segments_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "leon_host_crc32_segments": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "leon_host_bgzf_members": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, _u64p, _u64p, _u64p, _u32p]),
+    "leon_host_bgzf_inflate": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
+    "leon_bgzf_inflate_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                            C.c_void_p]),
+    "leon_host_pinned_alloc": (C.c_int, [C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "leon_host_pinned_free": (None, [C.c_void_p]),
     "leon_letters_count_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, _u64p, _u64p]),
     "leon_letters_take_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]),
     "leon_letters_apply_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]),
@@ -371,6 +377,77 @@ def host_crc32_segments(data, seg_off, n_threads=0, n_bytes=None, n_seg=None, nu
     return crc[:n_seg]
 
 
+BGZF_WHOLE, BGZF_PARTIAL, BGZF_TRUNCATED, BGZF_FOREIGN = 0, 1, 2, 3
+
+
+def _host_bytes(data):
+    """bytes-like or a uint8 array (used as it lies) as a uint8 array that is never empty; None stays None"""
+    if data is None:
+        return None
+    if isinstance(data, np.ndarray) and data.dtype == np.uint8:
+        return data
+    return np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)
+
+
+def host_bgzf_members(data, last=False, off_cap=None, n_bytes=None):
+    """leon_host_bgzf_members (no GPU) over data[:n_bytes]: a dict of rc, message, member_off (the members' first bytes and the end of
+    the last whole one), n_text, consumed and stop (BGZF_*).  off_cap: the entries the table has room for (default: enough)."""
+    lib = load_library()
+    buf = _host_bytes(data)
+    if n_bytes is None:
+        n_bytes = 0 if data is None else len(data)
+    if off_cap is None:
+        off_cap = n_bytes // 20 + 2
+    off = np.zeros(max(off_cap, 1), dtype=np.uint64)
+    n, text, used, stop = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
+    rc = lib.leon_host_bgzf_members(C.c_void_p(0 if buf is None else buf.ctypes.data), int(n_bytes), int(last), C.c_void_p(off.ctypes.data if off_cap else 0),
+                                    int(off_cap), C.byref(n), C.byref(text), C.byref(used), C.byref(stop))
+    return {"rc": rc, "message": (lib.leon_last_error(None) or b"").decode() if rc else "", "member_off": off[:min(n.value + 1, off_cap)].copy(),
+            "n_members": n.value, "n_text": text.value, "consumed": used.value, "stop": stop.value}
+
+
+def host_bgzf_inflate(data, member_off, n_threads=0, text_cap=None, n_members=None, n_bytes=None):
+    """leon_host_bgzf_inflate (no GPU): the members' text as bytes.  text_cap: the room given (default: 65 536 bytes per member)"""
+    lib = load_library()
+    buf = _host_bytes(data)
+    off = None if member_off is None else np.ascontiguousarray(member_off, dtype=np.uint64)
+    if n_members is None:
+        n_members = 0 if off is None else max(len(off) - 1, 0)
+    if n_bytes is None:
+        n_bytes = 0 if data is None else len(data)
+    if text_cap is None:
+        text_cap = 65536 * n_members
+    text = np.zeros(text_cap + 1, dtype=np.uint8)
+    n_text = C.c_uint64()
+    rc = lib.leon_host_bgzf_inflate(C.c_void_p(0 if buf is None else buf.ctypes.data), int(n_bytes), C.c_void_p(0 if off is None else off.ctypes.data),
+                                    int(n_members), C.c_void_p(text.ctypes.data), int(text_cap), C.byref(n_text), n_threads)
+    if rc:
+        err = LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+        err.n_text = n_text.value
+        raise err
+    return text[:n_text.value].tobytes()
+
+
+def bgzf_inflate_device(data, member_off, d_text, text_cap, device_id=0, max_members_per_launch=0, n_members=None, n_bytes=None):
+    """leon_bgzf_inflate_device: data and member_off on the host, d_text a device pointer (an integer, 0 = NULL) with room for text_cap
+    bytes.  Returns (bytes of text, literal/length symbols decoded)."""
+    lib = load_library()
+    buf = _host_bytes(data)
+    off = None if member_off is None else np.ascontiguousarray(member_off, dtype=np.uint64)
+    if n_members is None:
+        n_members = 0 if off is None else max(len(off) - 1, 0)
+    if n_bytes is None:
+        n_bytes = 0 if data is None else len(data)
+    n_text, n_syms = C.c_uint64(), C.c_uint64()
+    rc = lib.leon_bgzf_inflate_device(device_id, C.c_void_p(0 if buf is None else buf.ctypes.data), int(n_bytes), C.c_void_p(0 if off is None else off.ctypes.data),
+                                      int(n_members), C.c_void_p(int(d_text)), int(text_cap), C.byref(n_text), int(max_members_per_launch), C.byref(n_syms))
+    if rc:
+        err = LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+        err.n_text = n_text.value
+        raise err
+    return n_text.value, n_syms.value
+
+
 def letters_count_device(d_bases, n_bytes, device_id=0):
     """leon_letters_count_device: (lower-case runs, bytes outside ACGTN) of the n_bytes at the device pointer d_bases (an integer)"""
     lib = load_library()
@@ -503,6 +580,35 @@ def device_upload_bytes(data, device_id=0):
     if rc:
         raise LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
     return p.value
+
+
+def device_count():
+    """leon_device_count: the HIP devices the library sees; 0 when it sees none (or cannot ask)"""
+    n = C.c_int(0)
+    return n.value if load_library().leon_device_count(C.byref(n)) == 0 and n.value > 0 else 0
+
+
+def host_pinned_alloc(n_bytes, device_id=0):
+    """leon_host_pinned_alloc: page-locked host memory as an integer address; the caller frees it with host_pinned_free"""
+    lib = load_library()
+    p = C.c_void_p()
+    rc = lib.leon_host_pinned_alloc(device_id, int(n_bytes), C.byref(p))
+    if rc:
+        raise LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+    return p.value
+
+
+def host_pinned_free(ptr):
+    """leon_host_pinned_free (0 / None passes NULL, which is allowed)"""
+    load_library().leon_host_pinned_free(C.c_void_p(int(ptr or 0)))
+
+
+def device_download_to(host_ptr, d_ptr, n_bytes, device_id=0):
+    """leon_device_download into the host memory at the integer address host_ptr (a pinned buffer: one direct copy)"""
+    lib = load_library()
+    rc = lib.leon_device_download(device_id, C.c_void_p(int(host_ptr)), C.c_void_p(int(d_ptr)), int(n_bytes))
+    if rc:
+        raise LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
 
 
 def device_alloc(n_bytes, device_id=0):

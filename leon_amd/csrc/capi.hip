@@ -5,6 +5,7 @@
 #include "host_rc.h"
 #include "staging.h"
 #include "host_blocks.h"
+#include "host_bgzf.h"
 
 #include "prim.h"
 
@@ -2112,6 +2113,90 @@ int leon_crc32_segments_device(int device_id, const uint8_t* d_bytes, uint64_t n
     HIPCHK(nullptr, hipStreamSynchronize(s));
     return LEON_OK;
 }
+
+// ---- BGZF members inflated on the device (inflate_kernels.hip) ----
+int leon_bgzf_inflate_device(int device_id, const uint8_t* bytes, uint64_t n_bytes, const uint64_t* member_off, uint64_t n_members, uint8_t* d_text,
+                             uint64_t text_cap, uint64_t* n_text, uint32_t max_members_per_launch, uint64_t* n_symbols) {
+    if (n_symbols) *n_symbols = 0;
+    std::vector<BgzfMember> m;
+    {
+        std::string why;
+        if (const int rc = bgzf_prepare(bytes, n_bytes, member_off, n_members, d_text, text_cap, n_text, m, why)) return fail(nullptr, rc, why);
+    }
+    if (!n_members) return LEON_OK;
+    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_NO_DEVICE, "leon_bgzf_inflate_device: no such HIP device"); }
+    // a stream of its own: the call runs beside calls on the contexts' streams
+    struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
+    HIPCHK(nullptr, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    hipStream_t s = st.s;
+    // launches of at most `per` members: what bounds the temporaries (a member has at most 64 KiB of payload and of text)
+    const uint64_t per = max_members_per_launch ? max_members_per_launch : 4096;
+    auto share = [&](uint64_t i) { return ((uint64_t)m[i].isize + 15) & ~15ull; };
+    uint64_t max_pay = 0, max_tmp = 0, max_nb = 0;
+    for (uint64_t b0 = 0; b0 < n_members; b0 += per) {
+        const uint64_t b1 = std::min(n_members, b0 + per);
+        uint64_t tmp = 0;
+        for (uint64_t i = b0; i < b1; i++) tmp += share(i);
+        max_pay = std::max(max_pay, member_off[b1] - member_off[b0]); max_tmp = std::max(max_tmp, tmp); max_nb = std::max(max_nb, b1 - b0);
+    }
+    TmpBuf d_pay, d_tmp, d_blk, d_status, d_seg, d_acc, d_cnt;
+    HIPCHK(nullptr, d_pay.ensure(max_pay + 64)); HIPCHK(nullptr, d_tmp.ensure(max_tmp + 64));
+    HIPCHK(nullptr, d_blk.ensure((max_nb + 1) * sizeof(QiBlock)));
+    HIPCHK(nullptr, d_status.ensure(max_nb * 4)); HIPCHK(nullptr, d_seg.ensure((2 * max_nb + 1) * 8)); HIPCHK(nullptr, d_acc.ensure(2 * max_nb * 4));
+    HIPCHK(nullptr, d_cnt.ensure(8));
+    HIPCHK(nullptr, hipMemsetAsync(d_cnt.p, 0, 8, s));
+    std::vector<QiBlock> blk;
+    std::vector<uint64_t> seg;
+    std::vector<uint32_t> status, acc;
+    for (uint64_t b0 = 0; b0 < n_members; b0 += per) {
+        const uint64_t b1 = std::min(n_members, b0 + per), nb = b1 - b0, pay_bytes = member_off[b1] - member_off[b0];
+        blk.assign(nb + 1, QiBlock{}); seg.assign(2 * nb + 1, 0);
+        uint64_t tmp = 0, tiles = 0;
+        for (uint64_t i = b0; i <= b1; i++) {
+            QiBlock& K = blk[i - b0];
+            K.text0 = tmp; K.tile0 = tiles;
+            seg[2 * (i - b0)] = tmp;                              // the member's text, then the share's padding: two segments
+            if (i == b1) break;
+            if (m[i].ok) { K.pay0 = m[i].pay0 - member_off[b0]; K.pay_size = m[i].pay_size; K.text_size = m[i].isize; }   // (!ok: an empty stream, refused below)
+            K.q0 = m[i].text0;
+            seg[2 * (i - b0) + 1] = tmp + K.text_size;
+            tmp += share(i); tiles += (K.text_size + 4095) / 4096;
+        }
+        if (staged_h2d(device_id, d_pay.p, bytes + member_off[b0], pay_bytes) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_HIP, "leon_bgzf_inflate_device: the payloads' copy to the device failed"); }
+        HIPCHK(nullptr, hipMemcpyAsync(d_blk.p, blk.data(), (nb + 1) * sizeof(QiBlock), hipMemcpyHostToDevice, s));
+        HIPCHK(nullptr, hipMemcpyAsync(d_seg.p, seg.data(), (2 * nb + 1) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(nullptr, hipMemsetAsync(d_acc.p, 0, 2 * nb * 4, s));
+        launch_bgzf_inflate(s, d_pay.as<uint32_t>(), (pay_bytes + 3) / 4, d_blk.as<QiBlock>(), (uint32_t)nb, d_tmp.as<uint8_t>(), d_status.as<uint32_t>(),
+                            n_symbols ? d_cnt.as<unsigned long long>() : nullptr);
+        HIPCHK(nullptr, hipGetLastError());
+        // the CRC-32 of every member's text where the wave left it, before anything goes to d_text
+        launch_crc32_segments(s, d_tmp.as<uint8_t>(), d_seg.as<uint64_t>(), 2 * nb, crc32_tile_count(d_tmp.as<uint8_t>(), 0, tmp), d_acc.as<uint32_t>());
+        HIPCHK(nullptr, hipGetLastError());
+        status.assign(nb, 0); acc.assign(2 * nb, 0);
+        HIPCHK(nullptr, hipMemcpyAsync(status.data(), d_status.p, nb * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(nullptr, hipMemcpyAsync(acc.data(), d_acc.p, 2 * nb * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(nullptr, hipStreamSynchronize(s));
+        for (uint64_t i = 0; i < nb; i++)
+            if (!m[b0 + i].ok || status[i] != QI_OK || acc[2 * i] != m[b0 + i].crc) return fail(nullptr, LEON_E_INVALID, bgzf_refusal(b0 + i, member_off[b0 + i]));
+        launch_bgzf_gather(s, d_blk.as<QiBlock>(), (uint32_t)nb, tiles, d_tmp.as<uint8_t>(), d_text, *n_text);
+        HIPCHK(nullptr, hipGetLastError());
+        HIPCHK(nullptr, hipStreamSynchronize(s));                 // the next launch reuses the temporaries (and the host's tables)
+    }
+    if (n_symbols) {
+        HIPCHK(nullptr, hipMemcpyAsync(n_symbols, d_cnt.p, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(nullptr, hipStreamSynchronize(s));
+    }
+    return LEON_OK;
+}
+
+int leon_host_pinned_alloc(int device_id, uint64_t bytes, void** ptr) {
+    if (!ptr) return fail(nullptr, LEON_E_INVALID, "leon_host_pinned_alloc: null argument");
+    *ptr = nullptr;
+    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_NO_DEVICE, "leon_host_pinned_alloc: no such HIP device"); }
+    if (hipHostMalloc(ptr, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); *ptr = nullptr; return fail(nullptr, LEON_E_HIP, "leon_host_pinned_alloc: " + std::to_string(bytes) + " bytes of pinned memory refused"); }
+    return LEON_OK;
+}
+void leon_host_pinned_free(void* ptr) { if (ptr) (void)hipHostFree(ptr); }
 
 int leon_device_download_pieces(int device_id, const void* d_src, uint64_t bytes, leon_piece_sink sink, void* user) {
     if (!sink || (bytes && !d_src)) return fail(nullptr, LEON_E_INVALID, "leon_device_download_pieces: null argument");

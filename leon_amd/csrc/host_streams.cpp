@@ -18,6 +18,8 @@
 #include <thread>
 #include <vector>
 
+#include "host_bgzf.h"
+
 namespace leon { void set_create_error(const std::string& msg); }
 
 namespace {
@@ -349,7 +351,8 @@ int leon_host_qual_decode_blocks(const uint8_t* payloads, const uint64_t* payloa
             out_off[++r] = w;
         }
         if (ok && (w != o0[b + 1] || at != text.size())) ok = false;
-        if (!ok) { int64_t expect = -1; bad.compare_exchange_strong(expect, (int64_t)b); }
+        // the SMALLEST failing block is the one named, whichever thread fails first
+        if (!ok) { int64_t seen = bad.load(); while ((seen < 0 || (int64_t)b < seen) && !bad.compare_exchange_weak(seen, (int64_t)b)) {} }
     });
     if (bad.load() >= 0) return fail(LEON_E_INVALID, "quality block " + std::to_string(bad.load()) + " does not decode");
     return LEON_OK;
@@ -391,6 +394,126 @@ int leon_host_crc32_segments(const uint8_t* bytes, uint64_t n_bytes, const uint6
         for (uint64_t i = first[s]; i < first[s + 1]; i++) c = i == first[s] ? pieces[i].crc : crc32_combine(c, pieces[i].crc, (z_off_t)pieces[i].size);
         crc[s] = (uint32_t)c;
     }
+    return LEON_OK;
+}
+
+// ---- BGZF input: the member walk, and the host form of leon_bgzf_inflate_device ----
+namespace leon {
+
+// The member that begins at p, of which `avail` bytes are in sight: 1f 8b 08, FLG exactly 4, XLEN, the subfields walked for
+// B C 02 00 BSIZE (others in front of it are skipped), BSIZE + 1 at least the header and the 8-byte trailer.
+// BGZF_MEMBER: *size = BSIZE + 1 <= avail, *pay0 = 12 + XLEN; BGZF_PARTIAL: nothing in sight contradicts a member, but it does not end
+// inside the bytes in sight; BGZF_FOREIGN: not a BGZF member.
+int bgzf_header(const uint8_t* p, uint64_t avail, uint64_t* size, uint64_t* pay0) {
+    static const uint8_t magic[4] = {0x1f, 0x8b, 0x08, 0x04};
+    for (uint64_t i = 0; i < 4 && i < avail; i++) if (p[i] != magic[i]) return BGZF_FOREIGN;
+    if (avail < 12) return BGZF_PARTIAL;
+    const uint64_t xlen = p[10] | (uint64_t)p[11] << 8, head = 12 + xlen;
+    if (head + 8 > 65536) return BGZF_FOREIGN;                   // (BSIZE has 16 bits)
+    if (avail < head) return BGZF_PARTIAL;
+    uint64_t bsize = ~0ull;
+    for (uint64_t at = 12; at + 4 <= head;) {
+        const uint64_t slen = p[at + 2] | (uint64_t)p[at + 3] << 8;
+        if (at + 4 + slen > head) return BGZF_FOREIGN;
+        if (p[at] == 'B' && p[at + 1] == 'C' && slen == 2) { bsize = p[at + 4] | (uint64_t)p[at + 5] << 8; break; }
+        at += 4 + slen;
+    }
+    if (bsize == ~0ull || bsize + 1 < head + 8) return BGZF_FOREIGN;
+    if (bsize + 1 > avail) return BGZF_PARTIAL;
+    *size = bsize + 1; *pay0 = head;
+    return BGZF_MEMBER;
+}
+
+// What both forms of the inflate refuse, in the same words, before anything is decoded; fills m (a member that is no BGZF member of
+// exactly its span, or whose ISIZE is above 65 536, is marked !ok and counts no text: it "does not decode" when its turn comes) and
+// *n_text.  LEON_OK, or the code with `why`.
+int bgzf_prepare(const uint8_t* bytes, uint64_t n_bytes, const uint64_t* member_off, uint64_t n_members, const void* text, uint64_t text_cap,
+                 uint64_t* n_text, std::vector<BgzfMember>& m, std::string& why) {
+    if (!n_text) { why = "BGZF inflate: null argument"; return LEON_E_INVALID; }
+    *n_text = 0;
+    m.clear();
+    if (!n_members) return LEON_OK;
+    if (!bytes || !member_off) { why = "BGZF inflate: null argument"; return LEON_E_INVALID; }
+    if (n_members >> 31) { why = "BGZF inflate: implausible number of members"; return LEON_E_INVALID; }
+    for (uint64_t i = 0; i < n_members; i++)
+        if (member_off[i + 1] < member_off[i]) { why = "BGZF inflate: member offsets are not monotonic"; return LEON_E_INVALID; }
+    if (member_off[n_members] > n_bytes) { why = "BGZF inflate: the members end behind the bytes given"; return LEON_E_INVALID; }
+    m.resize(n_members);
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n_members; i++) {
+        const uint64_t at = member_off[i], span = member_off[i + 1] - at;
+        uint64_t size = 0, pay0 = 0;
+        BgzfMember& M = m[i];
+        M = BgzfMember{at, 0, total, 0, 0, 0, false};
+        if (bgzf_header(bytes + at, span, &size, &pay0) != BGZF_MEMBER || size != span) continue;
+        const uint8_t* t = bytes + at + span - 8;
+        M.crc = t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+        const uint32_t isize = t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24;
+        if (isize > 65536) continue;
+        M.pay0 = at + pay0; M.pay_size = span - pay0 - 8; M.isize = isize; M.ok = true;
+        total += isize;
+    }
+    *n_text = total;
+    if (total > text_cap || (total && !text)) { why = "BGZF inflate: the text needs " + std::to_string(total) + " bytes"; return LEON_E_OVERFLOW; }
+    return LEON_OK;
+}
+std::string bgzf_refusal(uint64_t member, uint64_t at) {
+    return "BGZF member " + std::to_string(member) + " (at byte " + std::to_string(at) + ") does not decode";
+}
+
+}  // namespace leon
+
+int leon_host_bgzf_members(const uint8_t* bytes, uint64_t n_bytes, int last, uint64_t* member_off, uint64_t off_cap, uint64_t* n_members,
+                           uint64_t* n_text, uint64_t* consumed, uint32_t* stop) {
+    if (!n_members || !n_text || !consumed || !stop || (n_bytes && !bytes) || (off_cap && !member_off) || (last != 0 && last != 1))
+        return fail(LEON_E_INVALID, "BGZF members: null argument, or a `last` other than 0 or 1");
+    uint64_t at = 0, n = 0, text = 0;
+    uint32_t why = LEON_BGZF_WHOLE;
+    while (at < n_bytes) {
+        uint64_t size = 0, pay0 = 0;
+        const int kind = leon::bgzf_header(bytes + at, n_bytes - at, &size, &pay0);
+        if (kind == leon::BGZF_PARTIAL) { why = last ? LEON_BGZF_TRUNCATED : LEON_BGZF_PARTIAL; break; }
+        if (kind == leon::BGZF_FOREIGN) { why = LEON_BGZF_FOREIGN; break; }
+        const uint8_t* t = bytes + at + size - 4;
+        const uint32_t isize = t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+        if (isize <= 65536) text += isize;                       // (a larger one is refused by the inflate: it counts no text there either)
+        if (n < off_cap) member_off[n] = at;
+        n++; at += size;
+    }
+    if (n < off_cap) member_off[n] = at;
+    *n_members = n; *n_text = text; *consumed = at; *stop = why;
+    if (n + 1 > off_cap) return fail(LEON_E_OVERFLOW, "BGZF members: the table needs " + std::to_string(n + 1) + " entries");
+    if (why == LEON_BGZF_TRUNCATED) return fail(LEON_E_INVALID, "BGZF member " + std::to_string(n) + " (at byte " + std::to_string(at) + ") is truncated");
+    if (why == LEON_BGZF_FOREIGN) return fail(LEON_E_INVALID, "no BGZF member at byte " + std::to_string(at) + " (member " + std::to_string(n) + ")");
+    return LEON_OK;
+}
+
+int leon_host_bgzf_inflate(const uint8_t* bytes, uint64_t n_bytes, const uint64_t* member_off, uint64_t n_members, uint8_t* text, uint64_t text_cap,
+                           uint64_t* n_text, uint32_t n_threads) {
+    std::vector<leon::BgzfMember> m;
+    std::string why;
+    if (const int rc = leon::bgzf_prepare(bytes, n_bytes, member_off, n_members, text, text_cap, n_text, m, why)) return fail(rc, why);
+    std::atomic<uint64_t> bad{~0ull};
+    parallel_blocks(n_members, n_threads, [&](uint64_t i) {
+        const leon::BgzfMember& M = m[i];
+        bool ok = M.ok;
+        if (ok) {
+            uint8_t none = 0;
+            uint8_t* const dst = M.isize ? text + M.text0 : &none;
+            z_stream z{};
+            ok = inflateInit2(&z, -15) == Z_OK;
+            if (ok) {
+                z.next_in = const_cast<Bytef*>(bytes + M.pay0); z.avail_in = (uInt)M.pay_size;
+                z.next_out = dst; z.avail_out = (uInt)M.isize;
+                // the stream ends with the payload's last byte and gives exactly ISIZE bytes, whose CRC-32 is the trailer's
+                ok = inflate(&z, Z_FINISH) == Z_STREAM_END && z.avail_in == 0 && z.total_out == M.isize;
+                inflateEnd(&z);
+                ok = ok && (uint32_t)crc32(crc32(0L, Z_NULL, 0), dst, (uInt)M.isize) == M.crc;
+            }
+        }
+        if (!ok) { uint64_t seen = bad.load(); while (i < seen && !bad.compare_exchange_weak(seen, i)) {} }
+    });
+    if (bad.load() != ~0ull) return fail(LEON_E_INVALID, leon::bgzf_refusal(bad.load(), member_off[bad.load()]));
     return LEON_OK;
 }
 

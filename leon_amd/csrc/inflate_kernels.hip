@@ -11,6 +11,11 @@
 //   k_qual_lines     every tile again: the text without its newlines to d_quals (through LDS, aligned 16-byte stores), the reads' offsets
 //   k_qual_lens      (d_len given) a lane per read: its line's length against d_len
 // The verdict is the one of leon_host_qual_decode_blocks (zlib's uncompress and the line rules), host_streams.cpp.
+//
+// The same decoder (qi_stream) reads the members of a BGZF file (leon_bgzf_inflate_device):
+//   k_bgzf_inflate   one wave per member, a raw RFC 1951 stream into the member's 16-byte aligned share of a temporary
+//   k_bgzf_gather    every 4 KiB tile of every share to its place in the contiguous text (through LDS, aligned 16-byte stores)
+// with the members' CRC-32 taken over the temporary by crc_kernels.hip.  The verdict is leon_host_bgzf_inflate's.
 #include "kernels.h"
 #include "prim.h"
 
@@ -130,34 +135,40 @@ __device__ __forceinline__ uint32_t qi_symbol(QiBits& B, const uint16_t* tab, ui
     return 0xFFFFu;
 }
 
-// One wave per block.  Bounds: the payload is read through QiBits (inside the buffer, and `left` says when the block's own bytes
-// are used up) or, for a stored block, byte by byte below the block's end; the text is written below text0 + size, size being the
-// block's share (a symbol that would pass it ends the block with QI_LONG before it is written); LDS indices are masked or checked
-// against the tables' sizes.  Every turn of every loop consumes at least one bit of `left` or is counted by a bounded index, so the
-// kernel ends on every input.
-__global__ __launch_bounds__(64) void k_qual_inflate(const uint32_t* __restrict__ pay, uint64_t pay_words, const QiBlock* __restrict__ blk,
-                                                     uint32_t n_blocks, uint8_t* __restrict__ text, uint32_t* __restrict__ status,
-                                                     uint32_t* __restrict__ adler_expect, unsigned long long* __restrict__ n_syms) {
+// What differs between the two streams the decoder reads: a quality block is an RFC 1950 stream the way zlib's uncompress reads it
+// (header, Adler-32, bytes behind the stream ignored, an empty destination given one byte of room); a BGZF member's payload is the
+// bare RFC 1951 stream, which has to end with the payload's last byte and to give exactly ISIZE bytes.
+struct QiZlib { static constexpr bool kZlib = true; };
+struct QiRaw { static constexpr bool kZlib = false; };
+
+// One deflate stream, decoded by one wave: block headers, tables, symbols, matches, stored blocks, the ring, its flush and the
+// bookkeeping of `left`.  The stream is pay_size bytes at byte pay0 of the payload buffer; its text goes to out_text[0, size)
+// (16-byte aligned).  Returns the status; `check` is the stream's own Adler-32 (QiZlib) or 0.
+// Bounds: the payload is read through QiBits (inside the buffer, and `left` says when the stream's own bytes
+// are used up) or, for a stored block, byte by byte below the stream's end; the text is written below out_text + size, size being the
+// stream's share (a symbol that would pass it ends the stream with QI_LONG before it is written); a distance is checked against
+// `out`, the bytes of THIS stream written so far, so that no match reads what another stream left in the ring; LDS indices are masked
+// or checked against the tables' sizes.  Every turn of every loop consumes at least one bit of `left` or is counted by a bounded
+// index, so the function returns on every input.
+template <class P>
+__device__ __forceinline__ uint32_t qi_stream(const uint32_t* __restrict__ pay, uint64_t pay_words, uint64_t pay0, uint64_t pay_size, uint64_t size,
+                                              uint8_t* __restrict__ out_text, uint32_t lane, uint32_t& check, uint64_t& syms) {
     __shared__ __attribute__((aligned(16))) uint8_t s_ring[QI_RING];
     __shared__ uint16_t s_lt[1u << QI_LBITS], s_dt[1u << QI_DBITS], s_ls[288], s_ds[32];
     __shared__ uint8_t s_lens[320], s_cl[19];
-    const uint32_t b = blockIdx.x, lane = threadIdx.x;
-    if (b >= n_blocks) return;
-    const QiBlock K = blk[b];
-    const uint64_t size = K.text_size;
-    const uint64_t limit = size ? size : 1;                      // (zlib's uncompress gives an empty destination one byte of room)
-    uint8_t* const out_text = text + K.text0;
+    const uint64_t limit = P::kZlib && !size ? 1 : size;         // (zlib's uncompress gives an empty destination one byte of room)
     const uint8_t* const pay_bytes = reinterpret_cast<const uint8_t*>(pay);
     QiBits B;
     B.words = pay; B.n_words = pay_words; B.lane = lane;
-    B.seek(K.pay0, K.pay_size);
+    B.seek(pay0, pay_size);
     uint32_t st = QI_OK;
-    uint64_t out = 0, flushed = 0, syms = 0;
+    uint64_t out = 0, flushed = 0;
     uint32_t cnt_l = 0, cnt_d = 0;
     bool fixed_built = false;
+    syms = 0;
 
     // RFC 1950: CMF, FLG
-    {
+    if constexpr (P::kZlib) {
         const uint32_t cmf = B.get(8), flg = B.get(8);
         if ((cmf & 15) != 8 || (cmf >> 4) > 7 || ((cmf << 8) | flg) % 31 != 0 || (flg & 0x20)) st = QI_HEADER;
         if (B.left < 0) st = QI_EARLY;
@@ -177,7 +188,7 @@ __global__ __launch_bounds__(64) void k_qual_inflate(const uint32_t* __restrict_
             const uint64_t bytes_left = (uint64_t)B.left >> 3;
             if (len > bytes_left) { st = QI_EARLY; break; }
             if (out + len > limit) { st = QI_LONG; break; }
-            const uint64_t src = K.pay0 + (K.pay_size - bytes_left);
+            const uint64_t src = pay0 + (pay_size - bytes_left);
             for (uint32_t done = 0; done < len;) {
                 const uint32_t step = min(len - done, 256u);
                 for (uint32_t k = lane; k < step; k += 64) s_ring[(out + k) & QI_RMASK] = pay_bytes[src + done + k];
@@ -293,18 +304,54 @@ __global__ __launch_bounds__(64) void k_qual_inflate(const uint32_t* __restrict_
     uint32_t adler = 0;
     if (st == QI_OK) {
         B.drop((uint32_t)(B.left & 7));
-        for (uint32_t i = 0; i < 4; i++) adler = adler << 8 | B.get(8);
-        if (B.left < 0) st = QI_EARLY;
-        else if (out != size) {
-            // an empty share: uncompress accepts a stream of one byte (it goes nowhere) when its checksum holds
-            const uint32_t d = qi_uni(s_ring[0]);
-            if (size || out != 1 || adler != ((1 + d) << 16 | (1 + d))) st = QI_SHORT; else adler = 1;
+        if constexpr (P::kZlib) {
+            for (uint32_t i = 0; i < 4; i++) adler = adler << 8 | B.get(8);
+            if (B.left < 0) st = QI_EARLY;
+            else if (out != size) {
+                // an empty share: uncompress accepts a stream of one byte (it goes nowhere) when its checksum holds
+                const uint32_t d = qi_uni(s_ring[0]);
+                if (size || out != 1 || adler != ((1 + d) << 16 | (1 + d))) st = QI_SHORT; else adler = 1;
+            }
+        } else {
+            if (B.left != 0) st = QI_SLACK;                      // bytes between the stream's end and the trailer
+            else if (out != size) st = QI_SHORT;
         }
     }
     QI_WAVE_ORDER();
     if (size) for (uint64_t k = flushed + lane; k < out; k += 64) out_text[k] = s_ring[k & QI_RMASK];       // out <= size
+    check = adler;
+    return st;
+}
+
+// One wave per quality block (an RFC 1950 stream).
+__global__ __launch_bounds__(64) void k_qual_inflate(const uint32_t* __restrict__ pay, uint64_t pay_words, const QiBlock* __restrict__ blk,
+                                                     uint32_t n_blocks, uint8_t* __restrict__ text, uint32_t* __restrict__ status,
+                                                     uint32_t* __restrict__ adler_expect, unsigned long long* __restrict__ n_syms) {
+    const uint32_t b = blockIdx.x, lane = threadIdx.x;
+    if (b >= n_blocks) return;
+    const QiBlock K = blk[b];
+    uint32_t adler; uint64_t syms;
+    const uint32_t st = qi_stream<QiZlib>(pay, pay_words, K.pay0, K.pay_size, K.text_size, text + K.text0, lane, adler, syms);
     if (lane == 0) {
         status[b] = st; adler_expect[b] = adler;
+        if (n_syms) atomicAdd(n_syms, (unsigned long long)syms);
+    }
+}
+
+// One wave per BGZF member (leon_bgzf_inflate_device): the member's payload is a raw deflate stream of pay_size bytes
+// that gives text_size (the trailer's ISIZE, at most 65 536) bytes, into the member's 16-byte aligned share of a temporary.  The
+// members know nothing of one another: qi_stream starts every stream with an empty window.  Bounds: qi_stream's, with the share
+// [text0, text0 + text_size) and the payload buffer of pay_words words; status is indexed below n_blocks.
+__global__ __launch_bounds__(64) void k_bgzf_inflate(const uint32_t* __restrict__ pay, uint64_t pay_words, const QiBlock* __restrict__ blk,
+                                                     uint32_t n_blocks, uint8_t* __restrict__ text, uint32_t* __restrict__ status,
+                                                     unsigned long long* __restrict__ n_syms) {
+    const uint32_t b = blockIdx.x, lane = threadIdx.x;
+    if (b >= n_blocks) return;
+    const QiBlock K = blk[b];
+    uint32_t none; uint64_t syms;
+    const uint32_t st = qi_stream<QiRaw>(pay, pay_words, K.pay0, K.pay_size, K.text_size, text + K.text0, lane, none, syms);
+    if (lane == 0) {
+        status[b] = st;
         if (n_syms) atomicAdd(n_syms, (unsigned long long)syms);
     }
 }
@@ -435,6 +482,38 @@ __global__ __launch_bounds__(256) void k_qual_lines(const QiBlock* __restrict__ 
     }
 }
 
+// A 4 KiB tile of a BGZF member's share to its place in the contiguous text (k_qual_lines without the newlines): the bytes are staged
+// in LDS at an index congruent to their address mod 16 and leave in aligned 16-byte stores, single bytes at the tile's two ends -- two
+// tiles that meet inside a 16-byte chunk each write their own bytes of it only.
+// Bounds: the temporary is read inside the member's share rounded up to 16 bytes (the shares are 16-byte aligned and the buffer is
+// allocated to the rounded sum); text is written at [q0 + toff, q0 + toff + the tile's bytes) and below text_end.
+__global__ __launch_bounds__(256) void k_bgzf_gather(const QiBlock* __restrict__ blk, uint32_t n_blocks, uint64_t n_tiles, const uint8_t* __restrict__ tmp,
+                                                     uint8_t* __restrict__ text, uint64_t text_end) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[QT_TILE + 16];
+    const uint64_t tile = blockIdx.x;
+    if (tile >= n_tiles) return;
+    const uint32_t b = qi_block_of(blk, n_blocks, tile);
+    const QiBlock K = blk[b];
+    const uint64_t n = K.text_size, toff = (tile - K.tile0) * QT_TILE, at = toff + threadIdx.x * 16u;
+    if (toff >= n) return;                                                  // (uniform; no tile of the table is empty)
+    const uint64_t o0 = K.q0 + toff;                                        // the tile's first byte in the text
+    const uint32_t mis = (uint32_t)((uintptr_t)(text + o0) & 15);
+    if (at < n) {
+        const uint32_t valid = (uint32_t)(n - at < 16 ? n - at : 16);
+        const uint4 v = *reinterpret_cast<const uint4*>(tmp + K.text0 + at);
+        const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+        for (uint32_t j = 0; j < valid; j++) s_out[mis + threadIdx.x * 16u + j] = (uint8_t)(w4[j >> 2] >> (8 * (j & 3)));
+    }
+    __syncthreads();
+    const uint32_t cnt = (uint32_t)(n - toff < QT_TILE ? n - toff : QT_TILE);
+    uint8_t* const g0 = text + o0 - mis;                                    // 16-byte aligned
+    for (uint32_t ch = threadIdx.x; ch * 16u < mis + cnt; ch += QT_THREADS) {
+        const uint32_t lo = ch * 16u, hi = lo + 16;
+        if (lo >= mis && hi <= mis + cnt && o0 + (hi - mis) <= text_end) *reinterpret_cast<uint4*>(g0 + lo) = *reinterpret_cast<const uint4*>(s_out + lo);
+        else for (uint32_t i = lo < mis ? mis : lo; i < hi && i < mis + cnt; i++) if (o0 + (i - mis) < text_end) g0[i] = s_out[i];
+    }
+}
+
 __global__ __launch_bounds__(256) void k_qual_lens(const uint64_t* __restrict__ qual_off, const uint32_t* __restrict__ len, uint64_t read0, uint64_t n,
                                                    unsigned long long* __restrict__ bad_read /* ~0 */) {
     const uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
@@ -447,6 +526,17 @@ void launch_qual_inflate(hipStream_t s, const uint32_t* pay, uint64_t pay_words,
                          uint32_t* adler_expect, unsigned long long* n_syms) {
     if (!n_blocks) return;
     hipLaunchKernelGGL(k_qual_inflate, dim3(n_blocks), dim3(64), 0, s, pay, pay_words, blk, n_blocks, text, status, adler_expect, n_syms);
+}
+
+void launch_bgzf_inflate(hipStream_t s, const uint32_t* pay, uint64_t pay_words, const QiBlock* blk, uint32_t n_blocks, uint8_t* tmp, uint32_t* status,
+                         unsigned long long* n_syms) {
+    if (!n_blocks) return;
+    hipLaunchKernelGGL(k_bgzf_inflate, dim3(n_blocks), dim3(64), 0, s, pay, pay_words, blk, n_blocks, tmp, status, n_syms);
+}
+
+void launch_bgzf_gather(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, uint64_t n_tiles, const uint8_t* tmp, uint8_t* text, uint64_t text_end) {
+    if (!n_tiles) return;
+    hipLaunchKernelGGL(k_bgzf_gather, dim3((uint32_t)n_tiles), dim3(QT_THREADS), 0, s, blk, n_blocks, n_tiles, tmp, text, text_end);
 }
 
 void launch_qual_tiles(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, uint64_t n_tiles, const uint8_t* text, uint32_t* tile_nl,

@@ -218,7 +218,7 @@ void launch_fmt_records(hipStream_t s, const FmtLayout& L, const FmtPair* off, c
 // its quality bytes + its reads: the lines with their newlines), its first 4 KiB tile of the text, its place in d_quals and d_qual_off
 struct QiBlock { uint64_t pay0, pay_size, text0, text_size, tile0, q0, read0, n_reads; };
 enum : uint32_t { QI_OK = 0, QI_HEADER = 1, QI_TYPE = 2, QI_STORED = 3, QI_TABLE = 4, QI_CODE = 5, QI_DIST = 6, QI_LONG = 7, QI_EARLY = 8,
-                  QI_SHORT = 9, QI_LINES = 10, QI_ADLER = 11 };
+                  QI_SHORT = 9, QI_LINES = 10, QI_ADLER = 11, QI_SLACK = 12 /* (BGZF) bytes between the stream's end and the trailer */ };
 // one wave per block; status[b] = QI_OK or why the stream was refused, adler_expect[b] = the stream's own checksum; n_syms: nullptr,
 // or a counter of the literal/length symbols decoded (measurement)
 void launch_qual_inflate(hipStream_t s, const uint32_t* pay, uint64_t pay_words, const QiBlock* blk /* n_blocks + 1 */, uint32_t n_blocks, uint8_t* text,
@@ -233,6 +233,15 @@ void launch_qual_check(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, con
 void launch_qual_lines(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, uint64_t n_tiles, const uint8_t* text, const uint64_t* nl_before,
                        uint8_t* quals, uint64_t quals_end, uint64_t* qual_off, uint64_t total_reads);
 void launch_qual_lens(hipStream_t s, const uint64_t* qual_off, const uint32_t* len, uint64_t read0, uint64_t n, unsigned long long* bad_read /* ~0 before */);
+
+// ---- BGZF members inflated on the device (inflate_kernels.hip), DESIGN.md 4.14 ----
+// A member is a QiBlock: pay0 / pay_size = its raw deflate stream in the launch's payload buffer, text0 = its 16-byte aligned share of
+// the temporary, text_size = its ISIZE, tile0 = its first 4 KiB tile, q0 = its first byte in the contiguous text (read0, n_reads: 0).
+// one wave per member, the decoder of launch_qual_inflate on a raw stream that ends with its payload; status[b] = QI_OK or why
+void launch_bgzf_inflate(hipStream_t s, const uint32_t* pay, uint64_t pay_words, const QiBlock* blk /* n_blocks + 1 */, uint32_t n_blocks, uint8_t* tmp,
+                         uint32_t* status, unsigned long long* n_syms);
+// the shares of the temporary to text[q0 ..), contiguous, whatever text's alignment; nothing at or behind text_end is written
+void launch_bgzf_gather(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, uint64_t n_tiles, const uint8_t* tmp, uint8_t* text, uint64_t text_end);
 
 // ---- zlib's CRC-32 of segments of a device buffer (crc_kernels.hip), DESIGN.md 4.11 ----
 constexpr uint64_t CRC32_MAX_GROUPS = 4096;                    // the grid's cap: a workgroup walks ceil(tiles / cap) consecutive tiles

@@ -19,7 +19,9 @@ struct ReadBatch {
 
 class Bank {
 public:
-    explicit Bank(const std::string& path);      // throws leon_host::Exception when the file cannot be opened
+    // throws leon_host::Exception when the file cannot be opened.  inflate_device >= 0 (`-c -input-inflate device`): a BGZF file is
+    // inflated by that device, chunk by chunk; any other file is read as without it, and `verbose` says so in one line
+    explicit Bank(const std::string& path, int inflate_device = -1, bool verbose = false);
     ~Bank();
     Bank(const Bank&) = delete;
     Bank& operator=(const Bank&) = delete;
@@ -36,11 +38,15 @@ public:
 private:
     bool getline(std::string& line);
     bool view(const char*& p, size_t& n);         // the next line where it lies (in the read buffer when it ends there), else assembled in spill_
+    bool refill();                                // the next piece of the text behind data_; false at the end of the file
+    struct BgzfSource;                            // BGZF input inflated on the device: chunks of the file, one in flight while the previous is parsed
+    BgzfSource* bz_ = nullptr;
     void* gz_ = nullptr;                          // gzFile (gzip input)
     int fd_ = -1;                                 // plain input: read(2) straight into buf_ (zlib's transparent mode copies every byte once more)
     std::string path_, pending_, spill_;
     bool have_pending_ = false, decided_ = false, fastq_ = false;
     std::vector<char> buf_;
+    const char* data_ = nullptr;                  // the piece being served: buf_, or one of the BGZF source's pinned buffers
     size_t buf_pos_ = 0, buf_len_ = 0;
     uint64_t file_bytes_ = 0, n_read_ = 0;
     uint64_t wrap_ = 0;

@@ -190,7 +190,7 @@ struct Compressor {
 
 Compressor::Compressor(Leon& leon)
     : o(leon), k((uint32_t)leon._kmerSize), cores((uint32_t)leon._nbCores), n_gpus(leon._gpus),
-      checksum(leon._checksum), bank(leon._inputFilename) {
+      checksum(leon._checksum), bank(leon._inputFilename, input_inflate_device(leon._inputInflate, leon._inputFilename), leon._verbose) {
     fastq = bank.isFastq();
     keep_header = !o._noHeader; keep_qual = fastq && !o._noQual;
     // X.fastq.gz -> X.fastq.leon, data/toy.fasta -> data/toy.fasta.leon (/root/reference/scripts/simple_test.sh:51,54, INSTALL:21-23)
@@ -474,7 +474,7 @@ void Compressor::lossy_quals_resident() {
 
 // The qualities did not stay on the device: a second pass over the file feeds them through, batch by batch.
 void Compressor::lossy_quals_second_pass() {
-    Bank again(o._inputFilename);
+    Bank again(o._inputFilename, input_inflate_device(o._inputInflate, o._inputFilename), o._verbose);      // (`-input-inflate`: the same choice)
     ReadBatch& batch = buffers[0];
     uint64_t r = 0;
     for (;;) {

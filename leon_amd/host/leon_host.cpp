@@ -56,6 +56,7 @@ void Leon::run(int argc, char* argv[]) {
             else if (a == "-letters") _letters = true;
             else if (a == "-gz") _gz = true;
             else if (a == "-qual-deflate") { _qualDeflate = need("-qual-deflate"); (void)qual_encoder_choice(_qualDeflate); }
+            else if (a == "-input-inflate") { _inputInflate = need("-input-inflate"); (void)parse_choice("-input-inflate", _inputInflate); }
             else if (a == "-header-text") { _headerText = need("-header-text"); (void)parse_choice("-header-text", _headerText); }
             else if (a == "-record-text") { _recordText = need("-record-text"); (void)parse_choice("-record-text", _recordText); }
             else if (a == "-qual-inflate") { _qualInflate = need("-qual-inflate"); (void)parse_choice("-qual-inflate", _qualInflate); }
@@ -67,6 +68,7 @@ void Leon::run(int argc, char* argv[]) {
         if (_ignoreChecksum && _compress) throw Exception("option -ignore-checksum belongs to -d");
         if (_letters && _decompress) throw Exception("option -letters belongs to -c: -d restores the letters whenever the container holds them");
         if (_gz && _compress) throw Exception("option -gz belongs to -d");
+        if (!_inputInflate.empty() && _decompress) throw Exception("option -input-inflate belongs to -c");
         if (_seqOnly) _noHeader = _noQual = true;             // "same as -noheader -noqual", /root/reference/README.md:56
         execute();
     } catch (const Exception&) {

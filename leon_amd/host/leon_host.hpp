@@ -51,6 +51,7 @@ public:
     bool _letters = false;                // -c: -letters: lower-case runs and bytes outside ACGTN kept in leon/metadata/letter_*; -d puts them back whenever they are there
     bool _gz = false;                     // -d: -gz: the restored file written as BGZF (X.d.gz), compressed on the device
     std::string _qualDeflate;             // -qual-deflate host|device|auto; empty = not given: zlib on the host threads (the reference's bytes)
+    std::string _inputInflate;            // -c: -input-inflate host|device|auto; empty = not given: a gzip input inflated by zlib on the reader's thread
     std::string _headerText;              // -d: -header-text host|device|auto; empty = not given: the header text on the host threads
     std::string _recordText;              // -d: -record-text host|device|auto; empty = not given: the records formatted on the host threads
     std::string _qualInflate;             // -d: -qual-inflate host|device|auto; empty = not given: the quality blocks inflated by zlib on the host threads

@@ -6,6 +6,7 @@
 #include "leon_container.hpp"
 #include "leon_plan.hpp"
 
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -79,6 +80,22 @@ inline Choice parse_choice(const char* flag_name, const std::string& value) {
 inline bool device_chosen(Choice c, uint64_t n_blocks, uint64_t auto_blocks) {
     return c == Choice::Device || (c == Choice::Auto && n_blocks >= auto_blocks);
 }
+// `-c -input-inflate`: which device inflates a BGZF input (k_bgzf_inflate), or -1: the file is read on the host, as
+// without the option.  `auto` chooses the device for files of at least kInputInflateAutoBytes (DESIGN.md 8 has the runs behind it);
+// LEON_INPUT_INFLATE_AUTO_KB in the environment overrides that size, so that a test's small file takes the device way under `auto`.
+constexpr uint64_t kInputInflateAutoBytes = 64ull << 20;
+inline int input_inflate_device(const std::string& value, const std::string& path) {
+    const Choice c = parse_choice("-input-inflate", value);
+    if (c == Choice::Host) return -1;
+    if (c == Choice::Auto) {
+        uint64_t least = kInputInflateAutoBytes;
+        if (const char* e = getenv("LEON_INPUT_INFLATE_AUTO_KB")) { const long long kb = atoll(e); if (kb >= 0) least = (uint64_t)kb << 10; }
+        struct stat st;
+        if (::stat(path.c_str(), &st) != 0 || (uint64_t)st.st_size < least) return -1;   // (a file that is not there: the reader says so)
+    }
+    return device_for(0);
+}
+
 // Which encoder writes the quality blocks.  The default is zlib itself on the host threads (leon_host_qual_encode_blocks: compress2 at
 // its default level, the bytes upstream writes [RECALLED] and the one stream of the file a third-party library can pin byte for byte).
 // `-qual-deflate device` hands them to the device's deflate (leon_qual_deflate_blocks_device), which looks for runs only -- zlib's
