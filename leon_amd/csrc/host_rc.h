@@ -11,16 +11,21 @@
 #endif
 #include <pthread.h>
 #include <sched.h>
+#if defined(__linux__)
+#include <sys/mman.h>
+#endif
 #include <chrono>
 #include <cstdio>
 #include <condition_variable>
 #include <cstdlib>
+#include <cstring>
 #include <new>
 #include <algorithm>
 #include <deque>
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 namespace leon {
@@ -143,14 +148,53 @@ struct ChainCpus {
 
 struct ChainRec16 { uint64_t c; uint32_t lo, fr; };          // streams below 2^32 symbols (every count fits 32 bits)
 struct ChainRec24 { uint64_t c, lo, fr; };
+// The carry form's record (AnchorDictCoder::encode_records_carry; streams below 2^32 symbols): qmm = floor((2^56 - 1) / fr), the
+// largest quotient whose range q * fr stays below 2^56 (ChainFeed::qmm_of, beside the 128-by-64-bit division that makes C).
+struct ChainRecCarry { uint64_t c, qmm; uint32_t lo, fr; };
+
+// How far ahead of the chain's read position its record loops prefetch, in bytes.  The records come from other cores' caches or
+// from memory, one line per 4 symbols (16-byte records) or per 2.7 (24-byte).  Swept over 2, 4, 8 and 16 KiB for both loops with
+// the records streaming from memory (profiles/scripts/chain_ab/ab_spec.cpp `sweep`, profiles/chain_carry_sweep.txt): no distance
+// differs from another by more than the passes of one distance differ among themselves, so it stays where it was.
+constexpr int kChainPrefetchBytes = 2048;
+
+// The ring's storage: one allocation, 2 MiB-aligned and, when `huge`, offered to the kernel for huge pages (a refusal changes nothing), of
+// n slots of `stride` bytes.  ~270-400 MB that the chain streams through once per ring round; pages are touched only as far as the
+// helpers get ahead.  (The sweep found 2 MiB pages worth nothing to either loop: the feed asks for them only under LEON_CHAIN_HUGEPAGES=1.)
+class ChainRing {
+public:
+    ChainRing() = default;
+    ChainRing(const ChainRing&) = delete;
+    ChainRing& operator=(const ChainRing&) = delete;
+    ~ChainRing() { free(p_); }
+    bool allocated() const { return p_ != nullptr; }
+    size_t stride() const { return stride_; }
+    void allocate(uint32_t n, size_t stride, bool huge) {
+        constexpr size_t kHuge = (size_t)2 << 20;
+        stride_ = (stride + 63) & ~(size_t)63;
+        const size_t bytes = ((size_t)n * stride_ + kHuge - 1) & ~(kHuge - 1);
+        void* q = nullptr;
+        if (posix_memalign(&q, kHuge, bytes) != 0) throw std::bad_alloc();
+        p_ = static_cast<char*>(q);
+#if defined(__linux__) && defined(MADV_HUGEPAGE)
+        if (huge) (void)madvise(p_, bytes, MADV_HUGEPAGE);
+#else
+        (void)huge;
+#endif
+    }
+    void* at(uint32_t b) const { return p_ + (size_t)b * stride_; }
+private:
+    char* p_ = nullptr;
+    size_t stride_ = 0;
+};
 
 class ChainFeed {
 public:
     static constexpr uint32_t kMaxBufs = 1024;                  // the ring's size is n_bufs_ (LEON_CHAIN_RING, default 512), at most this
     static constexpr uint64_t kPlainBelow = 512;               // symbols coded in the plain form at the start of a stream (m needs a total above 256)
     struct View {
-        const void* recs = nullptr; uint64_t n_syms = 0;       // produced records (null for a plain segment): ChainRec16, or ChainRec24 when `wide`
-        bool wide = false;
+        const void* recs = nullptr; uint64_t n_syms = 0;       // produced records (null for a plain segment): ChainRec24 when `wide`, else ChainRecCarry when `carry`, else ChainRec16
+        bool wide = false, carry = false;
         const uint64_t* kmers = nullptr; uint32_t n_kmers = 0;
         uint64_t t0 = 0;                                       // index of the segment's first symbol in the stream
         uint64_t c_end[4] = {};                                // the model's counts (1 + occurrences of A, C, T, G) after the segment
@@ -160,7 +204,23 @@ public:
         // every further busy core lowers the clock the chain's own gets (with the deep ring: 786-808 ms per step with 3 helpers,
         // 795-817 with 4, 821-848 with 5, 840-859 with 7; profiles/r3_chain_helpers_ab.txt).  So three work all the time and
         // three SPARES only while the look-ahead is thin (the start of a stream, a host whose other tenants slow the helpers down).
-        uint32_t n = 3, spares = 3;
+        // LEON_CHAIN_FORM=quotient|carry: which step the chain runs on streams below 2^32 symbols, and so which records the helpers
+        // make for it.  Both give the same bytes; both live in one binary so that they can alternate on one box:
+        // 1.61-1.62 ns per symbol with carry against 1.75-1.76 with quotient on an EPYC 9575F, 100 M reads, k = 31.
+        // The carry form's loop is written with BMI2 instructions: a CPU without them runs the quotient form whatever is asked for.
+        carry_ = kCarryByDefault;
+        if (const char* e = getenv("LEON_CHAIN_FORM")) { if (!strcmp(e, "carry")) carry_ = true; else if (!strcmp(e, "quotient")) carry_ = false; }
+#ifdef LEON_HOST_CHAIN_X86
+        if (carry_ && !__builtin_cpu_supports("bmi2")) carry_ = false;
+#else
+        carry_ = false;
+#endif
+        // LEON_CHAIN_HUGEPAGES=1: the ring is offered to the kernel for 2 MiB pages.  Off unless asked for: with records streaming
+        // from memory neither loop gained anything from them (profiles/chain_carry_sweep.txt).
+        if (const char* e = getenv("LEON_CHAIN_HUGEPAGES")) huge_ = e[0] == '1';
+        // (a carry record costs a helper a sixth more -- qmm_of -- and the chain takes them a twelfth faster: a fourth permanent helper.
+        //  With it the chain waits 2.3-2.7 ms of a step for records, 1.8-2.3 in the quotient form with three.)
+        uint32_t n = carry_ ? 4 : 3, spares = 3;
         if (const char* e = getenv("LEON_CHAIN_HELPERS")) { const int v = atoi(e); if (v >= 1 && v <= 32) n = (uint32_t)v; }
         if (const char* e = getenv("LEON_CHAIN_SPARES")) { const int v = atoi(e); if (v >= 0 && v <= 32) spares = (uint32_t)v; }
         n_threads_ = n; n_spares_ = spares;
@@ -171,11 +231,15 @@ public:
         if (const char* e = getenv("LEON_CHAIN_RING")) { const int v = atoi(e); if (v >= 4 && v <= (int)kMaxBufs) n_bufs_ = (uint32_t)v; }
     }
     ~ChainFeed() { stop(); }
+    static constexpr bool kCarryByDefault = true;               // adopted on the A/B of profiles/chain_carry_ab.txt: 728-739 ms per step against 786-801
+    bool carry() const { return carry_; }
     ChainCpus cpus_;                                           // (set by the owner before start())
     void start() {
         if (running_) return;
         quit_ = false;
-        for (uint32_t b = 0; b < n_bufs_; b++) if (!buf_[b]) buf_[b].reset(new ChainRec24[(size_t)seg_kmers_ * k_]);      // (0.8 MB each, untouched until used; only for contexts that code a dictionary)
+        // sized by the record type the narrow segments get (0.5 or 0.8 MB a slot, untouched until used; only for contexts that code
+        // a dictionary); a stream that reaches 2^32 symbols gets a ring of ChainRec24 slots when its first wide segment is filled
+        if (!ring_.allocated()) ring_.allocate(n_bufs_, (size_t)seg_kmers_ * k_ * (carry_ ? sizeof(ChainRecCarry) : sizeof(ChainRec16)), huge_);
         for (uint32_t j = 0; j < n_threads_ + n_spares_; j++) th_.emplace_back([this, j] { run(j >= n_threads_); });
         running_ = true;
     }
@@ -220,8 +284,8 @@ public:
         if (n_spares_ && (int64_t)(next_claim_ - next_take_) < (int64_t)low_water()) cv_spare_.notify_all();        // thin look-ahead: the spares join in
         cv_ready_.wait(g, [&] { return ready_[s % n_bufs_] == s + 1; });
         const Seg& sg = segs_[s - base_];
-        v.recs = sg.plain ? nullptr : buf_[s % n_bufs_].get();
-        v.wide = sg.wide;
+        v.recs = sg.plain ? nullptr : slot(sg.wide, s);
+        v.wide = sg.wide; v.carry = carry_ && !sg.wide;
         v.n_syms = (uint64_t)sg.n_kmers * k_; v.kmers = sg.kmers; v.n_kmers = sg.n_kmers; v.t0 = sg.t0;
         for (int i = 0; i < 4; i++) v.c_end[i] = sg.c_end[i];
     }
@@ -264,7 +328,13 @@ private:
                 for (int i = 0; i < 4; i++) { d.c0[i] = c[i]; d.c_end[i] = prefix_c_[i]; }
             }
             cv_prefix_.notify_all();
-            if (!sg.plain) { if (sg.wide) fill(buf_[s % n_bufs_].get(), sg, c); else fill(reinterpret_cast<ChainRec16*>(buf_[s % n_bufs_].get()), sg, c); }
+            if (!sg.plain) {
+                if (sg.wide) {
+                    { std::lock_guard<std::mutex> g(mu_); if (!wide_ring().allocated()) wide_ring_.allocate(n_bufs_, (size_t)seg_kmers_ * k_ * sizeof(ChainRec24), huge_); }
+                    fill(static_cast<ChainRec24*>(slot(true, s)), sg, c);
+                } else if (carry_) fill(static_cast<ChainRecCarry*>(slot(false, s)), sg, c);
+                else fill(static_cast<ChainRec16*>(slot(false, s)), sg, c);
+            }
             { std::lock_guard<std::mutex> g(mu_); ready_[s % n_bufs_] = s + 1; }
             cv_ready_.notify_all();
         }
@@ -277,6 +347,19 @@ private:
 #else
         return (uint64_t)((((unsigned __int128)fr) << 64) / d);
 #endif
+    }
+    // floor((2^56 - 1) / fr), 1 <= fr < 2^32: the carry form's fourth field
+    // By a double-precision estimate and an exact fix-up, not a second hardware division: the FP divider works beside the integer one
+    // that makes C (4.4 ns per record with the division, 3.3 this way, 2.9 without the field; profiles/scripts/chain_ab/ab_fill.cpp).
+    // fr is exact as a double and the estimate within 8 of the quotient (within 1 from fr = 16 on): the remainder decides.
+    static inline uint64_t qmm_of(uint64_t fr) {
+        constexpr uint64_t kNum = (1ull << 56) - 1;
+        uint64_t m = (uint64_t)(int64_t)(0x1p56 / (double)(int64_t)fr);       // (signed conversions both ways: one instruction each)
+        int64_t r = (int64_t)(kNum - m * fr);
+        if (r < 0) { m--; r += (int64_t)fr; }
+        if (r >= (int64_t)fr) { m++; r -= (int64_t)fr; }
+        if (__builtin_expect((uint64_t)r >= fr, 0)) m = kNum / fr;
+        return m;
     }
     // (the cumulative counts stay in registers and the k-mer is shifted out two bits at a time: 3.0 ns per record on the EPYC 9575F
     // against 5.3-6.5 with the counts in an array and a variable shift per base -- profiles/scripts/chain_ab/ab_fill.cpp; what is
@@ -291,6 +374,7 @@ private:
                 const uint32_t sy = (uint32_t)(x >> 126);
                 const uint64_t lo = cum[sy], fr = cum[sy + 1] - lo;
                 out->c = scaled(fr, d);
+                if constexpr (std::is_same<Rec, ChainRecCarry>::value) out->qmm = qmm_of(fr);
                 out->lo = (decltype(out->lo))lo; out->fr = (decltype(out->fr))fr;
                 cum[1] += sy < 1; cum[2] += sy < 2; cum[3] += sy < 3; cum[4]++;
             }
@@ -299,7 +383,11 @@ private:
     }
     const uint32_t k_, W_, seg_kmers_;
     uint32_t n_threads_ = 5;
-    std::unique_ptr<ChainRec24[]> buf_[kMaxBufs];          // (holds either record type)
+    // a wide segment's slot is in a ring of its own unless the narrow ring's slots already hold 24-byte records
+    ChainRing& wide_ring() { return ring_.stride() >= (size_t)seg_kmers_ * k_ * sizeof(ChainRec24) ? ring_ : wide_ring_; }
+    void* slot(bool wide, uint64_t s) { return (wide ? wide_ring() : ring_).at((uint32_t)(s % n_bufs_)); }
+    ChainRing ring_, wide_ring_;
+    bool carry_ = false, huge_ = false;
     uint64_t ready_[kMaxBufs] = {};                            // segment index + 1 a buffer currently holds
     uint32_t n_bufs_ = 512, n_spares_ = 0;
     std::condition_variable cv_spare_;
@@ -361,6 +449,7 @@ public:
 #ifdef LEON_HOST_CHAIN_X86
         if (v.recs) {
             if (v.wide) encode_records(static_cast<const ChainRec24*>(v.recs), v.n_syms, v.t0);
+            else if (v.carry) encode_records_carry(static_cast<const ChainRecCarry*>(v.recs), v.n_syms, v.t0);
             else encode_records(static_cast<const ChainRec16*>(v.recs), v.n_syms, v.t0);
             for (int i = 0; i < 4; i++) cum_[i + 1] = cum_[i] + v.c_end[i];     // the model as the plain form would have left it
             cum_[5] = cum_[4] + 1;
@@ -385,7 +474,7 @@ private:
     // the next quotient is Phi when no byte leaves and Phi8 = (Phi << 8) | (Plo >> 56) when exactly one does (x < TOP) -- both formed,
     // selected by conditional moves.  The product's fraction within q of the next integer (see ChainFeed; rare), two bytes at
     // once or the carry-less coder's range < BOTTOM reset take a division.
-    template <typename Rec> void encode_records(const Rec* r, uint64_t n, uint64_t t0) {
+    template <typename Rec, int kAhead = kChainPrefetchBytes> void encode_records(const Rec* r, uint64_t n, uint64_t t0) {
         // Room for the worst case up front -- 8 bytes per symbol: the loop below shifts 64 bits out at most -- so that the fast path's
         // unchecked store can never run past the buffer, whatever mix of rare-path symbols (several bytes each) came before it.
         // (It was n + 64 on the argument that a genomic dictionary codes at ~2 bits per symbol: an unstated property of the input.)
@@ -398,7 +487,7 @@ private:
         const Rec* const e = r + n;
         for (; r < e; r++) {
             tot1++;                                            // ... from here on, the total of the NEXT symbol
-            __builtin_prefetch(reinterpret_cast<const char*>(r) + 2048);      // (the records come from other cores' caches or from memory)
+            __builtin_prefetch(reinterpret_cast<const char*>(r) + kAhead);    // (the records come from other cores' caches or from memory)
             const uint64_t lo = r->lo, lf = lo + r->fr;
             const uint64_t Lu = L + q * lo;
             uint64_t Tu = L + q * lf;
@@ -436,6 +525,105 @@ private:
         w_ = (size_t)(p - buf_.data());
         low_ = L; range_ = R; n_ += n;
     }
+    // The CARRY form of the same step (LEON_CHAIN_FORM=carry): the flag "exactly one byte leaves" without the exclusive-or.  With both
+    // ends shifted left by 8,
+    //     a8 = (L << 8) + q * (lo << 8) = (Lu << 8) mod 2^64,      r8 = q * (fr << 8) = (Ru << 8) mod 2^64,
+    // adding the range to the low end's low 56 bits carries out of a8 + r8 exactly when a byte boundary is crossed, that is when NO byte
+    // leaves: multiply, add, add-with-carry, select -- a carried path of 6 cycles instead of 7, and 28 instructions a symbol.  A range
+    // of 2^56 or more (no byte can leave; r8 has lost its top bits) is known from the quotient alone, q > qmm, and forces the carry by
+    // saturating r8; the carry is taken from a8 + r8 + 1 (stc; adc), the same for multiples of 256 and right for a8 = 0 under a
+    // saturated r8.  The quotient lives in rdx (mulx's implicit operand; the legacy mul leaves Phi8 there); two steps per turn so
+    // that no register is moved between steps.  What the fast step does not cover leaves the loop BEFORE anything of the symbol is
+    // committed and takes the plain step from (q, L):
+    //     a quotient in doubt (the low half of (q << 8) * C above ~q8max, q8max >= any q << 8 of the segment: conservative),
+    //     a range below 2^48 (which covers two or more bytes leaving: x < 2^48 implies Ru < 2^48) and its reset,
+    //     a segment's last symbol, which must leave the exact range behind.
+    struct PlainStep { uint64_t q, L, R; uint8_t* p; };
+    __attribute__((noinline)) PlainStep step_plain(const ChainRecCarry* r, uint64_t tot_next, uint64_t q, uint64_t L, uint8_t* p) {
+        uint64_t Lo = L + q * r->lo, R = q * r->fr;
+        uint8_t* p_end = buf_.data() + buf_.size() - 32;
+        while ((Lo ^ (Lo + R)) < kTop || (R < kBottom && ((R = (0 - Lo) & (kBottom - 1)), true))) {
+            if (p >= p_end) { const size_t used = (size_t)(p - buf_.data()); buf_.resize(buf_.size() * 2 + 4096); p = buf_.data() + used; p_end = buf_.data() + buf_.size() - 32; }
+            *p++ = (uint8_t)(Lo >> 56);
+            R <<= 8;
+            Lo <<= 8;
+        }
+        return PlainStep{R / tot_next, Lo, R, p};
+    }
+#define LEON_CARRY_STEP(OFF, LIN, LOUT, LOUT32, EXIT)                                                                  \
+                "movq  %%rdx, %%r14\n\t"                       /* the step's quotient, kept for a rare exit */           \
+                "mulxq " OFF "(%[r]), %%rbx, %%rbx\n\t"        /* Phi */                                                 \
+                "movl  " OFF "+16(%[r]), " LOUT32 "\n\t"       /* lo */                                                  \
+                "movl  " OFF "+20(%[r]), %%r13d\n\t"           /* fr */                                                  \
+                "shlxq %[eight], " LOUT ", %%r12\n\t"          /* lo << 8 */                                             \
+                "shlxq %[eight], %%r13, %%r13\n\t"             /* fr << 8 */                                             \
+                "imulq %%rdx, %%r12\n\t"                       /* q * (lo << 8) */                                       \
+                "imulq %%rdx, %%r13\n\t"                       /* r8 = q * (fr << 8) */                                  \
+                "imulq %%rdx, " LOUT "\n\t"                    /* q * lo */                                              \
+                "cmpq  %%rdx, " OFF "+8(%[r])\n\t"             /* CF = qmm < q: the range is 2^56 or more */             \
+                "sbbq  %%rax, %%rax\n\t"                                                                               \
+                "orq   %%rax, %%r13\n\t"                       /* r8, saturated */                                       \
+                "shlxq %[eight], %%rdx, %%rax\n\t"             /* q8 */                                                  \
+                "mulq  " OFF "(%[r])\n\t"                      /* rdx = Phi8, rax = the low half */                      \
+                "cmpq  %[dbt], %%rax\n\t"                                                                              \
+                "ja    " EXIT "\n\t"                           /* quotient in doubt */                                   \
+                "shlxq %[eight], " LIN ", %%rax\n\t"           /* L << 8 */                                              \
+                "addq  %%rax, %%r12\n\t"                       /* a8 = (Lu << 8) mod 2^64 */                             \
+                "addq  " LIN ", " LOUT "\n\t"                  /* Lu */                                                  \
+                "cmpq  %[top], %%r13\n\t"                                                                              \
+                "jb    " EXIT "\n\t"                           /* range below 2^48 */                                    \
+                "rorxq $56, " LOUT ", %%rax\n\t"                                                                       \
+                "movb  %%al, (%[p])\n\t"                       /* Lu's top byte, kept only if p moves on */              \
+                "stc\n\t"                                                                                              \
+                "adcq  %%r12, %%r13\n\t"                       /* CF = a byte boundary is crossed: NO byte leaves */     \
+                "cmovcq %%rbx, %%rdx\n\t"                      /* q' = one byte ? Phi8 : Phi, in rdx */                  \
+                "cmovncq %%r12, " LOUT "\n\t"                  /* L' = one byte ? Lu << 8 : Lu */                        \
+                "sbbq  $-1, %[p]\n\t"                          /* p += one byte */
+    template <int kAhead = kChainPrefetchBytes> void encode_records_carry(const ChainRecCarry* r, uint64_t n, uint64_t t0) {
+        if (!n) return;
+        if (buf_.size() < w_ + 8 * n + 64) buf_.resize(buf_.size() * 2 + 8 * n + 4096);      // the worst case up front, as in encode_records
+        settle();
+        uint8_t* p = buf_.data() + w_;
+        uint64_t L = low_;
+        const ChainRecCarry* const r0 = r;
+        uint64_t q = range_ / (5 + t0);
+        const ChainRecCarry* const e = r + n - 1;                // the last symbol goes the plain way
+        const ChainRecCarry* const e2 = e - 1;                   // a turn of the loop needs two records before it
+        // q <= (2^64 - 1) / total, total >= 5 + t0 > 256: q << 8 <= 2^72 / (5 + t0)
+        const uint64_t doubt_above = ~(uint64_t)((((unsigned __int128)1) << 72) / (5 + t0));
+        while (r < e) {
+            if (r < e2) {
+                asm volatile(
+                    ".p2align 5\n"
+                    "1:\n\t"
+                    LEON_CARRY_STEP("0", "%[L]", "%%rcx", "%%ecx", "2f")
+                    LEON_CARRY_STEP("24", "%%rcx", "%[L]", "%k[L]", "3f")
+                    "prefetcht0 %c[ahead](%[r])\n\t"
+                    "addq  $48, %[r]\n\t"
+                    "cmpq  %[e], %[r]\n\t"
+                    "jb    1b\n\t"
+                    "jmp   4f\n"
+                    "3:\n\t"                                   // left in the second step: the first one's low end is the state, one record on
+                    "movq  %%rcx, %[L]\n\t"
+                    "addq  $24, %[r]\n"
+                    "2:\n\t"
+                    "movq  %%r14, %%rdx\n"                      // the quotient the step that was left began with
+                    "4:\n"
+                    : [r] "+r"(r), [q] "+d"(q), [L] "+r"(L), [p] "+r"(p)
+                    : [e] "m"(e2), [top] "r"(kTop), [dbt] "r"(doubt_above), [eight] "r"((uint64_t)8), [ahead] "i"(kAhead)
+                    : "rax", "rbx", "rcx", "r12", "r13", "r14", "cc", "memory");     // (13 registers: one to spare with a frame pointer)
+            }
+            if (r >= e) break;
+            // the record the loop stopped at (a rare case, or the odd record before the last)
+            const PlainStep s = step_plain(r, 5 + t0 + (uint64_t)(r - r0) + 1, q, L, p);
+            q = s.q; L = s.L; p = s.p;
+            r++;
+        }
+        const PlainStep s = step_plain(r, 5 + t0 + n, q, L, p);
+        w_ = (size_t)(s.p - buf_.data());
+        low_ = s.L; range_ = s.R; n_ += n;
+    }
+#undef LEON_CARRY_STEP
 #endif
     // the renormalisation the last symbol owes (the state is kept un-normalised between symbols, see encode_kmer)
     inline void settle() {

@@ -48,6 +48,54 @@ template <bool FP> static void fill_new(Rec* out, const uint64_t* km, size_t n, 
     }
     c[0] = cum[1]; c[1] = cum[2] - cum[1]; c[2] = cum[3] - cum[2]; c[3] = cum[4] - cum[3];
 }
+// the carry form's 24-byte record: the same, plus qmm = floor((2^56 - 1) / fr) -- by a 64-bit hardware division, or by a
+// double-precision estimate (the FP divider works beside the integer one that makes C) with an exact fix-up
+struct CarryRec { uint64_t c, qmm; uint32_t lo, fr; };
+static inline uint64_t qmm_div(uint64_t fr) { return ((1ull << 56) - 1) / fr; }
+static inline uint64_t qmm_fp(uint64_t fr) {                    // fr < 2^32 is exact as a double; the estimate is within 8 of the quotient, within 1 from fr = 16 on
+    uint64_t m = (uint64_t)(int64_t)(0x1p56 / (double)(int64_t)fr);   // (signed conversions both ways: one instruction each)
+    int64_t r = (int64_t)(((1ull << 56) - 1) - m * fr);
+    if (r < 0) { m--; r += (int64_t)fr; }
+    if (r >= (int64_t)fr) { m++; r -= (int64_t)fr; }
+    if ((uint64_t)r >= fr) m = qmm_div(fr);
+    return m;
+}
+template <int Q> static void fill_carry(CarryRec* out, const uint64_t* km, size_t n, uint32_t k, uint64_t t0, uint64_t* c) {
+    uint64_t d = 5 + t0 + 1;
+    uint64_t cum[5] = {0, c[0], c[0] + c[1], c[0] + c[1] + c[2], c[0] + c[1] + c[2] + c[3]};
+    for (size_t a = 0; a < n; a++) {
+        uint64_t x = km[a] << (64 - 2 * k);
+        for (uint32_t i = 0; i < k; i++, d++, out++, x <<= 2) {
+            const uint32_t sy = (uint32_t)(x >> 62);
+            const uint64_t lo = cum[sy], fr = cum[sy + 1] - lo;
+            out->c = scaled_div(fr, d); out->qmm = Q == 0 ? 0 : Q == 1 ? qmm_div(fr) : qmm_fp(fr); out->lo = (uint32_t)lo; out->fr = (uint32_t)fr;
+            cum[1] += sy < 1; cum[2] += sy < 2; cum[3] += sy < 3; cum[4]++;
+        }
+    }
+    c[0] = cum[1]; c[1] = cum[2] - cum[1]; c[2] = cum[3] - cum[2]; c[3] = cum[4] - cum[3];
+}
+static void carry_variants(const std::vector<uint64_t>& km, size_t n, uint32_t k) {
+    std::vector<CarryRec> a(n * k), b(n * k);
+    for (int rep = 0; rep < 2; rep++) for (int variant = 0; variant < 3; variant++) {
+        uint64_t c[4] = {1, 1, 1, 1};
+        std::vector<CarryRec>& out = variant == 2 ? b : a;
+        auto t0 = std::chrono::steady_clock::now();
+        if (variant == 0) fill_carry<0>(out.data(), km.data(), n, k, 600, c);
+        else if (variant == 1) fill_carry<1>(out.data(), km.data(), n, k, 600, c);
+        else fill_carry<2>(out.data(), km.data(), n, k, 600, c);
+        const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        bool same = true;
+        if (variant == 2) for (size_t i = 0; i < n * k; i++) if (a[i].qmm != b[i].qmm || a[i].c != b[i].c) { same = false; break; }
+        printf("24-byte carry record, %s: %.2f ns per symbol%s\n", variant == 0 ? "qmm left out (the record's size alone)" : variant == 1 ? "qmm by a 64-bit division" : "qmm by a double estimate + exact fix-up",
+               dt / (n * k) * 1e9, variant == 2 ? (same ? "  == the division's" : "  DIFFERS") : "");
+    }
+    std::mt19937_64 r2(7);
+    uint64_t bad = 0;
+    for (uint64_t fr = 1; fr < 70000; fr++) if (qmm_fp(fr) != qmm_div(fr)) bad++;
+    for (int i = 0; i < 30000000; i++) { const uint64_t fr = 1 + (r2() >> (32 + r2() % 31)); if (qmm_fp(fr) != qmm_div(fr)) bad++; }
+    for (int s = 1; s < 32; s++) for (int64_t o = -3; o <= 3; o++) { const uint64_t fr = (uint64_t)((1ll << s) + o); if (fr >= 1 && fr < (1ull << 32) && qmm_fp(fr) != qmm_div(fr)) bad++; }
+    printf("qmm mismatches, fr = 1 .. 70 000, 30 M random fr below 2^32, powers of two +- 3: %llu\n", (unsigned long long)bad);
+}
 int main() {
     const uint32_t k = 31;
     const size_t n = 1500000;
@@ -67,6 +115,7 @@ int main() {
         printf("%s: %.2f ns per symbol%s\n", variant == 0 ? "division, counts in memory (first build)" : variant == 1 ? "division, cumulative counts in registers" : "double estimate + exact fix-up, cumulative counts in registers",
                dt / (n * k) * 1e9, variant ? (same ? "  == first build" : "  DIFFERS") : "");
     }
+    carry_variants(km, n, k);
     std::mt19937_64 r2(5);                                       // exactness of the estimate on operands up to 2^34
     uint64_t bad = 0;
     for (int i = 0; i < 30000000; i++) {

@@ -480,6 +480,77 @@ struct SpecCoder {
     }
 };
 
+// ---- the library's two record loops, records from DRAM, at each prefetch distance, with and without huge pages ----------------
+//   ./ab_spec [n_kmers] [skew] sweep
+// "as it stands" = AnchorDictCoder::encode_records on ChainRec16 (LEON_CHAIN_FORM=quotient), "carry, 24-byte records" =
+// AnchorDictCoder::encode_records_carry on ChainRecCarry (LEON_CHAIN_FORM=carry), both called as the library calls them: segment by
+// segment of ~32 k symbols.  The records lie in one 2 MiB-aligned allocation each, written once beforehand (2-3 GB: nothing of it is
+// in a cache when the chain gets there), madvise(MADV_HUGEPAGE) or madvise(MADV_NOHUGEPAGE).  Three passes per line; the bytes of
+// every pass are compared with the plain form's.
+template <typename T> static T* sweep_alloc(size_t count, bool huge) {
+    const size_t two_mb = (size_t)2 << 20, bytes = (count * sizeof(T) + two_mb - 1) & ~(two_mb - 1);
+    void* q = nullptr;
+    if (posix_memalign(&q, two_mb, bytes) != 0) { printf("allocation of %zu bytes failed\n", bytes); exit(2); }
+    const int rc = madvise(q, bytes, huge ? MADV_HUGEPAGE : MADV_NOHUGEPAGE);
+    if (rc != 0) printf("(madvise(%s) refused)\n", huge ? "MADV_HUGEPAGE" : "MADV_NOHUGEPAGE");
+    return static_cast<T*>(q);
+}
+template <int D> static double sweep_pass(bool carry, const ChainRec16* r16, const ChainRecCarry* rc, const uint64_t* km, size_t n, uint32_t k, const std::vector<uint8_t>& ref, bool* same) {
+    const size_t plain = 20;
+    AnchorDictCoder cd;
+    cd.encode_kmers(km, plain, k);
+    cd.buf_.resize(cd.w_ + 8 * n * k + 4096);
+    memset(cd.buf_.data() + cd.w_, 0, ref.size() + 64);                 // (room made and touched outside the timed region)
+    auto t0 = std::chrono::steady_clock::now();
+    for (uint64_t at = plain * k, end = n * k; at < end;) {
+        const uint64_t m = std::min<uint64_t>(32767, end - at);
+        if (carry) cd.encode_records_carry<D>(rc + at, m, at); else cd.encode_records<ChainRec16, D>(r16 + at, m, at);
+        at += m;
+    }
+    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    cd.flush();
+    *same = cd.size() == ref.size() && memcmp(cd.data(), ref.data(), ref.size()) == 0;
+    return dt / ((n - plain) * (double)k) * 1e9;
+}
+static int sweep(const std::vector<uint64_t>& km, size_t n, uint32_t k) {
+    std::vector<uint8_t> ref;
+    {
+        AnchorDictCoder cd;
+        cd.encode_kmers(km.data(), n, k);
+        cd.flush();
+        ref.assign(cd.data(), cd.data() + cd.size());
+    }
+    for (int huge = 0; huge < 2; huge++) {
+        ChainRec16* r16 = sweep_alloc<ChainRec16>(n * k, huge != 0);
+        ChainRecCarry* rc = sweep_alloc<ChainRecCarry>(n * k, huge != 0);
+        uint64_t c[4] = {1, 1, 1, 1}, t = 0;
+        for (size_t a = 0; a < n; a++) for (uint32_t i = 0; i < k; i++, t++) {
+            const uint32_t sy = (uint32_t)(km[a] >> (2 * (k - 1 - i))) & 3u;
+            const uint64_t c01 = c[0] + c[1], lo = sy == 0 ? 0 : sy == 1 ? c[0] : sy == 2 ? c01 : c01 + c[2], fr = c[sy];
+            uint64_t q, r; const uint64_t d = 5 + t + 1;
+            asm("divq %[d]" : "=a"(q), "=d"(r) : "a"(0ull), "d"(fr), [d] "r"(d) : "cc");
+            r16[t] = ChainRec16{q, (uint32_t)lo, (uint32_t)fr};
+            rc[t] = ChainRecCarry{q, ((1ull << 56) - 1) / fr, (uint32_t)lo, (uint32_t)fr};
+            c[sy]++;
+        }
+        for (int carry = 0; carry < 2; carry++) for (int di = 0; di < 4; di++) {
+            double ns[3]; bool all_same = true;
+            for (int rep = 0; rep < 3; rep++) {
+                bool same = false;
+                ns[rep] = di == 0 ? sweep_pass<2048>(carry, r16, rc, km.data(), n, k, ref, &same) : di == 1 ? sweep_pass<4096>(carry, r16, rc, km.data(), n, k, ref, &same)
+                        : di == 2 ? sweep_pass<8192>(carry, r16, rc, km.data(), n, k, ref, &same) : sweep_pass<16384>(carry, r16, rc, km.data(), n, k, ref, &same);
+                all_same = all_same && same;
+            }
+            printf("%s, records from DRAM, %s pages, prefetch %5d B ahead: %.3f %.3f %.3f ns/symbol, %s\n", carry ? "CARRY, 24-byte records" : "AS IT STANDS (16-byte)",
+                   huge ? "2 MiB" : "4 KiB", 2048 << di, ns[0], ns[1], ns[2], all_same ? "IDENTICAL" : "DIFFERENT");
+            fflush(stdout);
+            if (!all_same) return 1;
+        }
+        free(r16); free(rc);
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const uint32_t k = 31;
     const size_t n = argc > 1 ? atol(argv[1]) : 4000000;
@@ -491,6 +562,7 @@ int main(int argc, char** argv) {
         if (skew == 1) { const uint64_t m = rng() & rng() & rng(); x &= m >> 2; }           // mostly A
         if (skew == 2) x &= 0x5555555555555555ull >> 2;                                      // A and C only
     }
+    if (argc > 3 && !strcmp(argv[3], "sweep")) return sweep(km, n, k);
     std::vector<ChainRec16> recs(n * k);
     std::vector<SpecRec> srecs(n * k + 1);
     uint64_t c[4] = {1, 1, 1, 1}, t = 0;
