@@ -371,6 +371,39 @@ void leon_qual_deflate_release(void);
 #define LEON_BGZF_MEMBER_TEXT 32768u
 int leon_text_bgzf_device(int device_id, const uint8_t* d_text, uint64_t n_text, int last, leon_piece_sink sink, void* user,
                           uint64_t* n_taken, uint64_t* out_bytes, uint64_t* n_members);
+/* The same stream with its members cut at RECORD STARTS, and a table of where every member lies.
+ * d_text: n_head bytes of head, then n_body bytes whose records start at d_rec_off[0 .. n_records] -- DEVICE memory, relative to the
+ * body, [0] = 0, [n_records] = n_body, strictly ascending: what leon_records_format_device writes into its d_rec_off.  The head is what
+ * the call before did not take (n_head <= W = LEON_BGZF_MEMBER_TEXT): whole records from a record start; the records inside it need not
+ * be known again.  The cut rule, from a cut p = s_i of the record starts s_0 = 0 < s_1 < ... < s_R = n_text:
+ *   s_{i+1} - s_i > W (an oversized record): floor(len / W) members of W bytes and one of len % W when that is not 0; next cut s_{i+1};
+ *   otherwise the next cut is the largest record start s_j <= p + W, j > i (as many whole records as fit; ending exactly at p + W fits).
+ * Without `last` members are cut from p while n_text - p > W; the rest (at most W bytes of whole records) is not taken: *n_taken (head
+ * included) says where it begins, and the caller puts it in front of its next call as that call's head.  With `last` the rest is the
+ * final member when it is not empty, and the EOF marker follows.  The output is a function of the whole text and its record starts
+ * alone, however they are split into calls and slices (LEON_BGZF_SLICE: a slice ends at a cut).
+ * Every member has 1 .. W bytes of text; a call writes at most 3 * (n_text / W) + 2 of them, n_text = n_head + n_body: two neighbours
+ * hold more than W bytes together unless the first is an oversized record's remainder, of which there are at most n_text / W; so
+ * members <= 2 * (n_text / W) + 1 + n_text / W.
+ * d_rec_off == NULL with n_records == 0 and n_head == 0: the fixed cuts and the bytes of leon_text_bgzf_device on (d_text, n_body).
+ * member_out_off / member_text_off (HOST memory, members_cap entries each; both NULL with members_cap == 0: no table): per data member
+ * its offset in this call's output and in this call's text.  *n_members is always the count; a table that is too small: LEON_E_OVERFLOW,
+ * *n_members = the entries needed, nothing delivered to the sink.
+ * Refused before a device is touched, LEON_E_INVALID: leon_text_bgzf_device's list (n_members must not be NULL here), n_head > W,
+ * records given with d_rec_off NULL, a body without records in record mode (d_rec_off given, or a head), a half-given member table.
+ * Refused on the device (k_bgzf_check_recs) before a byte is compressed or delivered, LEON_E_INVALID: offsets that are not strictly
+ * ascending, do not start at 0 or do not end at n_body.  Sink, stream and temporaries: as leon_text_bgzf_device. */
+int leon_text_bgzf_records_device(int device_id, const uint8_t* d_text, uint64_t n_head, uint64_t n_body,
+                                  const uint64_t* d_rec_off, uint64_t n_records, int last,
+                                  leon_piece_sink sink, void* user,
+                                  uint64_t* n_taken, uint64_t* out_bytes,
+                                  uint64_t* member_out_off, uint64_t* member_text_off, uint64_t members_cap, uint64_t* n_members);
+/* The same cut rule on HOST memory (no GPU): rec_off[0 .. n_records] as above (NULL with n_records == 0: a head alone), n_body =
+ * rec_off[n_records].  begin / len (cap entries each; both NULL with cap == 0: count only): every member's offset in the call's text
+ * (head included) and its bytes.  *n_members = the count, *n_taken as above.  LEON_E_OVERFLOW when a given table is too small
+ * (*n_members = the need); LEON_E_INVALID in the device call's words for what both refuse. */
+int leon_host_bgzf_record_cuts(const uint64_t* rec_off, uint64_t n_records, uint64_t n_head, int last, uint64_t* begin, uint32_t* len,
+                               uint64_t cap, uint64_t* n_members, uint64_t* n_taken);
 /* inverse: block_n_bytes = quality bytes per block without the newlines; out_off[total reads + 1] */
 int leon_host_qual_decode_blocks(const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads,
                                  const uint64_t* block_n_bytes, uint64_t n_blocks, uint8_t* out, uint64_t out_cap,

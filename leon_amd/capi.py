@@ -139,6 +139,9 @@ _EXPORTS = {
     "leon_qual_deflate_blocks_device": (C.c_int, [C.c_int, C.c_void_p, _u64p, C.c_uint64, C.c_uint32, SINK, C.c_void_p, C.c_uint64]),
     "leon_qual_deflate_release": (None, []),
     "leon_text_bgzf_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_int, PIECE_SINK, C.c_void_p, _u64p, _u64p, _u64p]),
+    "leon_text_bgzf_records_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, PIECE_SINK, C.c_void_p,
+                                                 _u64p, _u64p, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    "leon_host_bgzf_record_cuts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, _u64p, _u64p]),
     "leon_device_trim": (None, []),
     "leon_host_qual_decode_blocks": (C.c_int, [_u8p, _u64p, _u32p, _u64p, C.c_uint64, _u8p, C.c_uint64, _u64p, C.c_uint32]),
     "leon_qual_inflate_blocks_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
@@ -693,6 +696,95 @@ def text_bgzf_device(d_text, n_text, last=1, device_id=0, sink=None):
     if at != out_bytes.value:
         raise LeonDnaError(-5, "leon_text_bgzf_device: %d bytes delivered, out_bytes = %d" % (at, out_bytes.value))
     return b"".join(d for _, d in pieces), taken.value, members.value
+
+
+def bgzf_members_bound(n_text):
+    """the most members leon_text_bgzf_records_device writes for n_text bytes (head included)"""
+    return 3 * (int(n_text) // BGZF_MEMBER_TEXT) + 2
+
+
+def text_bgzf_records_device(d_text, n_head, n_body, d_rec_off, n_records, last=1, device_id=0, sink=None, member_out=None, member_text=None,
+                             members_cap=None, tables=True, null=()):
+    """leon_text_bgzf_records_device: n_head + n_body bytes at the device pointer d_text as BGZF with members cut at the record starts
+    d_rec_off[0 .. n_records] (a device pointer; 0 = NULL, with no records and no head: the fixed cuts).  Returns (bytes of this call's
+    output, n_taken, n_members, member_out_off, member_text_off); the pieces are collected as text_bgzf_device collects them.
+    tables: give the call member tables (of bgzf_members_bound entries, or members_cap); member_out / member_text: uint64 arrays of the
+    caller's to use instead (either may be None: the pointer is NULL).  null (tests): names among 'sink', 'n_taken', 'out_bytes',
+    'n_members' passed as NULL.  A failed call raises LeonDnaError; its n_members attribute holds what the call left there."""
+    lib = load_library()
+    pieces, raised = [], []
+    lock = threading.Lock()
+
+    def thunk(user, offset, address, size):
+        try:
+            if sink is not None:
+                rc = int(sink(int(offset), int(size)) or 0)
+                if rc:
+                    return rc
+            data = C.string_at(address, size) if size else b""
+            with lock:
+                pieces.append((int(offset), data))
+            return 0
+        except Exception as e:                         # noqa: BLE001 -- nothing may cross the C boundary
+            raised.append(e)
+            return 1
+    if member_out is None and member_text is None and tables:
+        cap = bgzf_members_bound(n_head + n_body) if members_cap is None else int(members_cap)
+        member_out, member_text = np.zeros(max(cap, 1), dtype=np.uint64), np.zeros(max(cap, 1), dtype=np.uint64)
+        members_cap = cap
+    if members_cap is None:
+        members_cap = 0 if member_out is None and member_text is None else min(len(a) for a in (member_out, member_text) if a is not None)
+    for a in (member_out, member_text):
+        assert a is None or (a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"])
+    taken, out_bytes, members = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    vp = lambda a: C.c_void_p(0 if a is None else a.ctypes.data)
+    rc = lib.leon_text_bgzf_records_device(device_id, C.c_void_p(int(d_text) if d_text else 0), int(n_head), int(n_body),
+                                           C.c_void_p(int(d_rec_off) if d_rec_off else 0), int(n_records), int(last),
+                                           None if "sink" in null else PIECE_SINK(thunk), None,
+                                           None if "n_taken" in null else C.byref(taken), None if "out_bytes" in null else C.byref(out_bytes),
+                                           vp(member_out), vp(member_text), int(members_cap), None if "n_members" in null else C.byref(members))
+    if rc:
+        err = LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+        err.n_members = members.value
+        if raised:
+            raise err from raised[0]
+        raise err
+    pieces.sort()
+    at = 0
+    for off, data in pieces:
+        if off != at:
+            raise LeonDnaError(-5, "leon_text_bgzf_records_device: the pieces do not tile the output (offset %d, expected %d)" % (off, at))
+        at += len(data)
+    if at != out_bytes.value:
+        raise LeonDnaError(-5, "leon_text_bgzf_records_device: %d bytes delivered, out_bytes = %d" % (at, out_bytes.value))
+    n = members.value
+    return (b"".join(d for _, d in pieces), taken.value, n, None if member_out is None else member_out[:n].copy(),
+            None if member_text is None else member_text[:n].copy())
+
+
+def host_bgzf_record_cuts(rec_off, n_head=0, last=1, cap=None, n_records=None, tables=True):
+    """leon_host_bgzf_record_cuts (no GPU): the members of n_head bytes of head and a body whose records start at rec_off (n_records + 1
+    entries, or None: a head alone).  Returns (begin, len, n_taken): every member's offset in the call's text and its bytes.  cap: the
+    entries the tables have room for (default: enough); tables=False: count only, returns (n_members, n_taken)."""
+    lib = load_library()
+    off = None if rec_off is None else np.ascontiguousarray(rec_off, dtype=np.uint64)
+    if n_records is None:
+        n_records = 0 if off is None else len(off) - 1
+    n_body = 0 if off is None or not len(off) else int(off[min(n_records, len(off) - 1)])
+    if cap is None:
+        cap = bgzf_members_bound(n_head + n_body) if tables else 0
+    begin, length = np.zeros(max(cap, 1), dtype=np.uint64), np.zeros(max(cap, 1), dtype=np.uint32)
+    n, taken = C.c_uint64(), C.c_uint64()
+    rc = lib.leon_host_bgzf_record_cuts(C.c_void_p(0 if off is None else off.ctypes.data), int(n_records), int(n_head), int(last),
+                                        C.c_void_p(begin.ctypes.data if tables else 0), C.c_void_p(length.ctypes.data if tables else 0), int(cap),
+                                        C.byref(n), C.byref(taken))
+    if rc:
+        err = LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+        err.n_members = n.value
+        raise err
+    if not tables:
+        return n.value, taken.value
+    return begin[:n.value].copy(), length[:n.value].copy(), taken.value
 
 
 def records_format_device(d_bases, d_len, n_reads, n_bases, d_text, text_cap, lead=b"@", fastq=True, plus_kind=0, wrap=0, first_read_index=0,

@@ -27,10 +27,13 @@
 
 namespace leon {
 void set_create_error(const std::string& msg);
+// host_streams.cpp: what leon_text_bgzf_records_device and leon_host_bgzf_record_cuts both refuse, in the same words; nullptr = in order
+const char* bgzf_records_refusal(bool have_off, uint64_t n_records, uint64_t n_head, uint64_t n_body, int last);
+const char* bgzf_offsets_refusal(uint32_t flags);
 
 namespace {
 
-constexpr uint32_t DF_CHUNK = 32768;                          // text bytes per deflate block
+constexpr uint32_t DF_CHUNK = 32768;                         // text bytes per deflate block
 constexpr uint32_t DF_T = 256;
 constexpr uint32_t DF_PER = DF_CHUNK / DF_T;                  // consecutive positions per thread
 constexpr uint32_t DF_OUT_STRIDE = DF_CHUNK + 64;             // bytes a chunk may write (stored form: text + 5)
@@ -418,6 +421,160 @@ __global__ void __launch_bounds__(256) k_bgzf_members(const uint8_t* chunks, con
     }
 }
 
+// per member (its offset in the call's output, its offset in the call's text), then the slice's size: what the host fetches in one copy
+__global__ void k_bgzf_index(const uint64_t* moff, const uint64_t* begin, uint64_t n, uint64_t out_base, uint64_t text_base, uint64_t* idx) {
+    const uint64_t c = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (c < n) { idx[2 * c] = out_base + moff[c]; idx[2 * c + 1] = text_base + begin[c]; }
+    else if (c == n) idx[2 * n] = moff[n];
+}
+
+// ---- members cut at record starts (leon_text_bgzf_records_device) ----
+// The record starts of the call's text, S(0 .. n_starts): 0 when there is a head (one record as far as the rule goes), then
+// n_head + rec_off[0 .. n_records]; n_starts = (n_head != 0) + n_records + 1.
+__device__ __forceinline__ uint64_t bgzf_start(const uint64_t* rec_off, uint64_t n_head, uint64_t k) {
+    const uint64_t hs = n_head ? 1 : 0;
+    return k < hs ? 0 : n_head + (rec_off ? rec_off[k - hs] : 0);
+}
+// flags (zeroed by the caller): 1 the offsets run backwards or stand still somewhere, 2 the first is not 0, 4 the last is not n_body.
+// Runs before anything is indexed with them; every lane stores the same word, no atomics (k_fmt_sizes' discipline).
+__global__ void __launch_bounds__(256) k_bgzf_check_recs(const uint64_t* __restrict__ rec_off, uint64_t n_records, uint64_t n_body, uint32_t* __restrict__ flags) {
+    const uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (r > n_records) return;
+    if (r == n_records) {
+        if (rec_off[0] != 0) flags[1] = 1;
+        if (rec_off[n_records] != n_body) flags[2] = 1;
+        return;
+    }
+    if (rec_off[r + 1] <= rec_off[r]) flags[0] = 1;
+}
+
+// The cut table of a slice.  The greedy chain is serial (cut c + 1 follows from cut c), so ONE workgroup walks it, in phases separated
+// by barriers: all threads load the starts S(k .. k + cnt) into LDS as 32-bit offsets from S(k) (clamped: an offset the walk may take
+// as a cut is below 2^31, see below), then wave 0 walks the chain inside the tile -- per member one look at 64 starts around where
+// the member before would put the cut, a binary search in LDS when the cut is not among them -- until a step's
+// range p + W reaches past the tile's last start; the next phase begins at the current cut.  A tile holds 16 000 starts, so records of
+// two bytes and more advance by at least one member per phase; a step whose W bytes hold more starts than a tile (records of one
+// byte) does that one search in global memory.  An oversized record is walked with its two 64-bit starts from global memory.
+//   state in : k0 the start the slice's first cut is at, skip0 the bytes of record k0 already taken (a multiple of W, an oversized
+//              record cut by a slice's end); budget_end: a member that ends behind it is left to the next slice unless it is the
+//              first; cap: members begin / len have room for (begin: cap + 1).
+//   state out: [0] members, [1] k, [2] skip, [3] S(k) + skip = where the text taken ends (also begin[members]: the CRC's last bound),
+//              [4] 1 when the budget or cap stopped the walk (more may follow), 0 when the rule did.
+// begin == NULL: members are counted only.  32-bit range: after an oversized record the phase ends when the next start is at 2^31 or
+// more from S(k); an ordinary step adds at most W, and a phase has at most 16 000 of them: p + W < 2^31 + 2^29 + W, which does not
+// wrap, and a clamped entry (2^32 - 1) is above every p + W, so it is never taken for a cut.
+// Bounds: rec_off is read at [0, n_records], tile at [0, cnt), begin at [0, cap], len at [0, cap).  No atomics, nothing spins.
+constexpr uint32_t BGZF_CUT_TILE = 16000;
+constexpr uint32_t BGZF_CUT_T = 1024;
+// which of tile[w0 .. w0 + 64) are at most target and not behind hi, a bit per lane of the wave (the tile ascends: ones, then zeros);
+// at_cut = the last of them, read from the lane that holds it (no second trip to LDS on the chain)
+__device__ __forceinline__ uint64_t bgzf_window(const uint32_t* tile, uint32_t w0, uint32_t hi, uint32_t target, uint32_t lane, uint32_t& at_cut) {
+    const uint32_t j = w0 + lane;
+    const uint32_t v = j <= hi ? tile[j] : 0xFFFFFFFFu;           // (above every target)
+    const uint64_t in = __ballot(v <= target);
+    at_cut = in ? (uint32_t)__builtin_amdgcn_readlane((int)v, (int)__builtin_popcountll(in) - 1) : 0u;
+    return in;
+}
+__global__ void __launch_bounds__(BGZF_CUT_T) k_bgzf_cuts(const uint64_t* __restrict__ rec_off, uint64_t n_starts, uint64_t n_head, uint64_t k0, uint64_t skip0,
+                                                          uint64_t budget_end, uint64_t n_text, uint32_t last, uint64_t cap, uint64_t* __restrict__ begin,
+                                                          uint32_t* __restrict__ len, uint64_t* __restrict__ state) {
+    __shared__ uint32_t tile[BGZF_CUT_TILE];
+    __shared__ uint64_t sh_k;
+    __shared__ uint32_t sh_done;
+    constexpr uint32_t W = DF_CHUNK;
+    const uint32_t t = threadIdx.x;
+    uint64_t n = 0, skip = skip0;                                 // (wave 0's, the same in every lane)
+    uint32_t more = 0, guess = 64;
+    if (t == 0) { sh_k = k0; sh_done = 0; }
+    for (;;) {
+        __syncthreads();
+        const uint64_t k = sh_k;
+        if (sh_done) break;                                       // (uniform)
+        const uint64_t base = bgzf_start(rec_off, n_head, k), left = n_starts - k;
+        const uint32_t cnt = left < BGZF_CUT_TILE ? (uint32_t)left : BGZF_CUT_TILE;
+        for (uint32_t i0 = t; i0 < cnt; i0 += 4 * BGZF_CUT_T) {    // four loads in flight per thread: one workgroup has only latency to hide
+            uint64_t v[4];
+#pragma unroll
+            for (uint32_t u = 0; u < 4; u++) { const uint32_t i = i0 + u * BGZF_CUT_T; v[u] = i < cnt ? bgzf_start(rec_off, n_head, k + i) - base : 0; }
+#pragma unroll
+            for (uint32_t u = 0; u < 4; u++) { const uint32_t i = i0 + u * BGZF_CUT_T; if (i < cnt) tile[i] = v[u] < 0xFFFFFFFFull ? (uint32_t)v[u] : 0xFFFFFFFFu; }
+        }
+        __syncthreads();
+        if (t >= 64) continue;                                    // wave 0 walks, its lanes in step: the state is uniform, lane 0 stores
+        uint32_t i = 0, done = 0, p = 0;                          // p = tile[i], carried in a register (tile[0] = 0)
+        const uint32_t tail = tile[cnt - 1];
+        uint64_t next_k = 0;                                      // (a step that searched global memory: the next phase's first start)
+        for (;;) {
+            if (n >= cap) { more = 1; done = 1; break; }
+            if (k + i + 1 >= n_starts) { done = 1; break; }       // the whole text is taken
+            const uint64_t p_abs = base + p;
+            if (!skip && !last && n_text - p_abs <= W) { done = 1; break; }
+            if (i + 1 >= cnt) break;                              // (i != 0: a tile has two starts when the text goes on)
+            if (skip || tile[i + 1] - p > W) {                    // an oversized record: members of its own
+                const uint64_t a = bgzf_start(rec_off, n_head, k + i), L = bgzf_start(rec_off, n_head, k + i + 1) - a;
+                while (skip < L) {
+                    const uint64_t m = L - skip < W ? L - skip : W;
+                    if (n >= cap || (n && a + skip + m > budget_end)) { more = 1; done = 1; break; }
+                    if (begin && t == 0) { begin[n] = a + skip; len[n] = (uint32_t)m; }
+                    n++; skip += m;
+                }
+                if (done) break;
+                skip = 0; i++;
+                p = tile[i];
+                if (p >= 0x80000000u) break;                // the next phase counts from this cut
+                continue;
+            }
+            const uint32_t target = p + W;
+            uint64_t m;
+            if (tail <= target && k + cnt < n_starts) {  // the range reaches past the tile
+                if (i) break;
+                uint64_t lo = k + cnt - 1, hi = n_starts - 1 < k + W ? n_starts - 1 : k + W;     // (records have at least one byte)
+                while (lo < hi) {
+                    const uint64_t mid = lo + (hi - lo + 1) / 2;
+                    if (bgzf_start(rec_off, n_head, mid) <= p_abs + W) lo = mid; else hi = mid - 1;
+                }
+                m = bgzf_start(rec_off, n_head, lo) - p_abs;
+                if (n && p_abs + m > budget_end) { more = 1; done = 1; break; }
+                next_k = lo;
+            } else {
+                // the largest j in [lo, hi] with tile[j] <= target (tile[lo] is).  The 64 lanes look at 64 starts around where a member
+                // of as many records as the one before would end -- one LDS read whose address does not wait for p -- and the ballot
+                // is the answer when it changes inside the window; a binary search over what is left otherwise
+                uint32_t lo = i + 1, hi = cnt - 1;
+                uint32_t w0 = i + guess > lo + 32 ? i + guess - 32 : lo;
+                if (w0 + 63 > hi) w0 = hi >= lo + 63 ? hi - 63 : lo;
+                uint32_t q;
+                const uint64_t in = bgzf_window(tile, w0, hi, target, t, q);
+                if (in && (~in != 0 || w0 + 63 >= hi)) lo = w0 + (uint32_t)__builtin_popcountll(in) - 1;
+                else {
+                    if (!in) hi = w0 - 1; else lo = w0 + 63;      // (w0 != i + 1 when none is in: tile[i + 1] is)
+                    while (lo < hi) {
+                        const uint32_t mid = (lo + hi + 1) >> 1;
+                        if (tile[mid] <= target) lo = mid; else hi = mid - 1;
+                    }
+                    q = tile[lo];
+                }
+                m = q - p;
+                if (n && p_abs + m > budget_end) { more = 1; done = 1; break; }
+                guess = lo - i;
+                i = lo; p = q;
+            }
+            if (begin && t == 0) { begin[n] = p_abs; len[n] = (uint32_t)m; }
+            n++;
+            if (next_k) break;
+        }
+        const uint64_t kk = next_k ? next_k : k + i;
+        if (t == 0) {
+            if (done) {
+                const uint64_t end = bgzf_start(rec_off, n_head, kk) + skip;
+                state[0] = n; state[1] = kk; state[2] = skip; state[3] = end; state[4] = more;
+                if (begin) begin[n] = end;
+            }
+            sh_k = kk; sh_done = done;
+        }
+    }
+}
+
 // Device buffers kept from call to call (one set per process, taken under a lock): a call per batch of a file would otherwise
 // allocate and free ~1.5 GB each time, and memory this process has freed comes back from hipMalloc at the driver's wiping
 // rate (~43 GB/s), for this call and for whoever allocates next.  Large calls go through in slices, so the set stays small.
@@ -539,9 +696,13 @@ int deflate_slice(DeflateScratch& S, int device_id, const uint8_t* d_quals, cons
 struct BgzfScratch {
     std::mutex mu;
     int device = -1;
-    Grow begin, len, out, sizes, adler, crc, msize, moff, tmp, framed;
-    void drop() { for (Grow* g : {&begin, &len, &out, &sizes, &adler, &crc, &msize, &moff, &tmp, &framed}) { if (g->p) (void)hipFree(g->p); g->p = nullptr; g->cap = 0; } }
+    Grow begin, len, out, sizes, adler, crc, msize, moff, tmp, framed, idx, state;
+    std::vector<uint64_t> h_idx;
+    void drop() { for (Grow* g : {&begin, &len, &out, &sizes, &adler, &crc, &msize, &moff, &tmp, &framed, &idx, &state}) { if (g->p) (void)hipFree(g->p); g->p = nullptr; g->cap = 0; } }
 };
+// the member tables of a call (host memory), filled slice by slice; out == NULL: none asked for
+struct BgzfIndex { uint64_t* out = nullptr; uint64_t* text = nullptr; uint64_t at = 0; };
+struct BgzfStream { hipStream_t s = nullptr; ~BgzfStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } };
 BgzfScratch* bgzf_table() { static BgzfScratch* t = new BgzfScratch[DF_MAX_DEVICES]; return t; }
 constexpr uint64_t BGZF_SLICE_TEXT = 512ull << 20;
 
@@ -552,22 +713,23 @@ uint64_t bgzf_slice_text() {
     return std::max<uint64_t>(v / DF_CHUNK, 1) * DF_CHUNK;
 }
 
-// the n_text bytes at d_text as ceil(n_text / DF_CHUNK) members, delivered at `base` of the call's output; *out_size = their bytes
-int bgzf_slice(BgzfScratch& S, int device_id, hipStream_t s, const uint8_t* d_text, uint64_t n_text, uint64_t base, leon_piece_sink sink, void* user, uint64_t* out_size) {
-    const uint64_t n = (n_text + DF_CHUNK - 1) / DF_CHUNK;
-    DCHK(S.begin.ensure((n + 1) * 8)); DCHK(S.len.ensure(n * 4)); DCHK(S.sizes.ensure(n * 4)); DCHK(S.adler.ensure(n * 4)); DCHK(S.crc.ensure(n * 4));
+// The n members of S.begin / S.len -- offsets into d_text, member c = [begin[c], begin[c + 1]), [lo, hi) in all, as k_bgzf_table or
+// k_bgzf_cuts left them on stream s -- compressed, framed and delivered at `base` of the call's output; *out_size = their bytes.
+// ix (may be NULL): the call's member tables, which receive base + the members' offsets and text_base + begin[c].
+int bgzf_members_out(BgzfScratch& S, int device_id, hipStream_t s, const uint8_t* d_text, uint64_t n, uint64_t lo, uint64_t hi, uint64_t base, uint64_t text_base,
+                     leon_piece_sink sink, void* user, BgzfIndex* ix, const std::string& who, uint64_t* out_size) {
+    DCHK(S.sizes.ensure(n * 4)); DCHK(S.adler.ensure(n * 4)); DCHK(S.crc.ensure(n * 4));
     DCHK(S.msize.ensure((n + 1) * 8)); DCHK(S.moff.ensure((n + 1) * 8));
     DCHK(S.out.ensure(n * (uint64_t)DF_OUT_STRIDE)); DCHK(S.framed.ensure(n * (uint64_t)BGZF_MEMBER_MAX));
     size_t tmp_bytes = 0;
     DCHK(prim::ExclusiveSum(nullptr, tmp_bytes, S.msize.as<uint64_t>(), S.moff.as<uint64_t>(), n + 1, s));
     DCHK(S.tmp.ensure(tmp_bytes));
     const uint32_t tgrid = (uint32_t)((n + 1 + 255) / 256);
-    hipLaunchKernelGGL(k_bgzf_table, dim3(tgrid), dim3(256), 0, s, n_text, n, S.begin.as<uint64_t>(), S.len.as<uint32_t>());
     hipLaunchKernelGGL(k_deflate_chunks, dim3((uint32_t)std::min<uint64_t>(n, 1u << 20)), dim3(DF_T), 0, s, d_text, S.begin.as<uint64_t>(), S.len.as<uint32_t>(), n,
                        S.out.as<uint8_t>(), S.sizes.as<uint32_t>(), S.adler.as<uint32_t>());
     DCHK(hipGetLastError());
     DCHK(hipMemsetAsync(S.crc.p, 0, n * 4, s));
-    launch_crc32_segments(s, d_text, S.begin.as<uint64_t>(), n, crc32_tile_count(d_text, 0, n_text), S.crc.as<uint32_t>());
+    launch_crc32_segments(s, d_text, S.begin.as<uint64_t>(), n, crc32_tile_count(d_text, lo, hi), S.crc.as<uint32_t>());
     DCHK(hipGetLastError());
     hipLaunchKernelGGL(k_bgzf_sizes, dim3(tgrid), dim3(256), 0, s, S.sizes.as<uint32_t>(), n, S.msize.as<uint64_t>());
     DCHK(prim::ExclusiveSum(S.tmp.p, tmp_bytes, S.msize.as<uint64_t>(), S.moff.as<uint64_t>(), n + 1, s));
@@ -575,13 +737,57 @@ int bgzf_slice(BgzfScratch& S, int device_id, hipStream_t s, const uint8_t* d_te
                        S.crc.as<uint32_t>(), S.moff.as<uint64_t>(), n, S.framed.as<uint8_t>());
     DCHK(hipGetLastError());
     uint64_t total = 0;
-    DCHK(hipMemcpyAsync(&total, S.moff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
-    DCHK(hipStreamSynchronize(s));
-    if (total > n * (uint64_t)BGZF_MEMBER_MAX || total < n * (uint64_t)BGZF_FRAME) { set_create_error("leon_text_bgzf_device: the members' sizes do not add up"); return LEON_E_OVERFLOW; }
+    if (ix && ix->out) {                                          // the members' places come with the total, in the one small copy
+        DCHK(S.idx.ensure((2 * n + 1) * 8));
+        S.h_idx.resize(2 * n + 1);
+        hipLaunchKernelGGL(k_bgzf_index, dim3(tgrid), dim3(256), 0, s, S.moff.as<uint64_t>(), S.begin.as<uint64_t>(), n, base, text_base, S.idx.as<uint64_t>());
+        DCHK(hipGetLastError());
+        DCHK(hipMemcpyAsync(S.h_idx.data(), S.idx.p, (2 * n + 1) * 8, hipMemcpyDeviceToHost, s));
+        DCHK(hipStreamSynchronize(s));
+        total = S.h_idx[2 * n];
+        for (uint64_t c = 0; c < n; c++) { ix->out[ix->at + c] = S.h_idx[2 * c]; ix->text[ix->at + c] = S.h_idx[2 * c + 1]; }
+        ix->at += n;
+    } else {
+        DCHK(hipMemcpyAsync(&total, S.moff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
+        DCHK(hipStreamSynchronize(s));
+    }
+    if (total > n * (uint64_t)BGZF_MEMBER_MAX || total < n * (uint64_t)BGZF_FRAME) { set_create_error(who + ": the members' sizes do not add up"); return LEON_E_OVERFLOW; }
     const int rc = staged_d2h_pieces(device_id, S.framed.p, total, [&](uint64_t offset, const void* p, uint64_t size) { return sink(user, base + offset, p, size); });
-    if (rc == 2) { set_create_error("leon_text_bgzf_device: the sink returned non-zero"); return LEON_E_SINK; }
-    if (rc) { set_create_error("leon_text_bgzf_device: copy to the host failed"); return LEON_E_HIP; }
+    if (rc == 2) { set_create_error(who + ": the sink returned non-zero"); return LEON_E_SINK; }
+    if (rc) { set_create_error(who + ": copy to the host failed"); return LEON_E_HIP; }
     *out_size = total;
+    return LEON_OK;
+}
+
+// the n_text bytes at d_text as ceil(n_text / DF_CHUNK) members, delivered at `base` of the call's output; *out_size = their bytes
+int bgzf_slice(BgzfScratch& S, int device_id, hipStream_t s, const uint8_t* d_text, uint64_t n_text, uint64_t base, uint64_t text_base, leon_piece_sink sink, void* user,
+               BgzfIndex* ix, const std::string& who, uint64_t* out_size) {
+    const uint64_t n = (n_text + DF_CHUNK - 1) / DF_CHUNK;
+    DCHK(S.begin.ensure((n + 1) * 8)); DCHK(S.len.ensure(n * 4));
+    hipLaunchKernelGGL(k_bgzf_table, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, s, n_text, n, S.begin.as<uint64_t>(), S.len.as<uint32_t>());
+    return bgzf_members_out(S, device_id, s, d_text, n, 0, n_text, base, text_base, sink, user, ix, who, out_size);
+}
+
+// the fixed cuts of leon_text_bgzf_device and of leon_text_bgzf_records_device without records: `taken` bytes of d_text in slices
+int bgzf_fixed(int device_id, const uint8_t* d_text, uint64_t taken, leon_piece_sink sink, void* user, BgzfIndex* ix, const std::string& who, uint64_t* at, uint64_t* members) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) { (void)hipGetLastError(); set_create_error(who + ": no such HIP device"); return LEON_E_NO_DEVICE; }
+    if (device_id >= DF_MAX_DEVICES) { set_create_error(who + ": device ordinal beyond the scratch table"); return LEON_E_INVALID; }
+    DCHK(hipSetDevice(device_id));
+    BgzfScratch& S = bgzf_table()[device_id];
+    std::lock_guard<std::mutex> lock(S.mu);
+    S.device = device_id;
+    // a stream of its own: the call runs beside calls on the contexts' streams
+    BgzfStream st;
+    DCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    const uint64_t slice = bgzf_slice_text();
+    for (uint64_t a = 0; a < taken; a += slice) {                 // sequential: a slice's base is the sum of the sizes before it
+        const uint64_t m = std::min(slice, taken - a);
+        uint64_t size = 0;
+        const int rc = bgzf_slice(S, device_id, st.s, d_text + a, m, *at, a, sink, user, ix, who, &size);
+        if (rc) return rc;
+        *at += size; *members += (m + DF_CHUNK - 1) / DF_CHUNK;
+    }
     return LEON_OK;
 }
 
@@ -630,24 +836,8 @@ extern "C" int leon_text_bgzf_device(int device_id, const uint8_t* d_text, uint6
     if (n_members) *n_members = 0;
     uint64_t at = 0, members = 0;
     if (taken) {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) { (void)hipGetLastError(); set_create_error("leon_text_bgzf_device: no such HIP device"); return LEON_E_NO_DEVICE; }
-        if (device_id >= DF_MAX_DEVICES) return refuse("device ordinal beyond the scratch table");
-        DCHK(hipSetDevice(device_id));
-        BgzfScratch& S = bgzf_table()[device_id];
-        std::lock_guard<std::mutex> lock(S.mu);
-        S.device = device_id;
-        // a stream of its own: the call runs beside calls on the contexts' streams
-        struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
-        DCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-        const uint64_t slice = bgzf_slice_text();
-        for (uint64_t a = 0; a < taken; a += slice) {              // sequential: a slice's base is the sum of the sizes before it
-            const uint64_t m = std::min(slice, taken - a);
-            uint64_t size = 0;
-            const int rc = bgzf_slice(S, device_id, st.s, d_text + a, m, at, sink, user, &size);
-            if (rc) return rc;
-            at += size; members += (m + DF_CHUNK - 1) / DF_CHUNK;
-        }
+        const int rc = bgzf_fixed(device_id, d_text, taken, sink, user, nullptr, "leon_text_bgzf_device", &at, &members);
+        if (rc) return rc;
     }
     if (last) {
         if (sink(user, at, kBgzfEof, sizeof kBgzfEof)) { set_create_error("leon_text_bgzf_device: the sink returned non-zero"); return LEON_E_SINK; }
@@ -655,6 +845,98 @@ extern "C" int leon_text_bgzf_device(int device_id, const uint8_t* d_text, uint6
     }
     *out_bytes = at;
     if (n_members) *n_members = members;
+    return LEON_OK;
+}
+
+/* the same with members cut at record starts and the members' places */
+extern "C" int leon_text_bgzf_records_device(int device_id, const uint8_t* d_text, uint64_t n_head, uint64_t n_body, const uint64_t* d_rec_off, uint64_t n_records, int last,
+                                             leon_piece_sink sink, void* user, uint64_t* n_taken, uint64_t* out_bytes, uint64_t* member_out_off,
+                                             uint64_t* member_text_off, uint64_t members_cap, uint64_t* n_members) {
+    const std::string who = "leon_text_bgzf_records_device";
+    auto fail = [&](int code, const std::string& why) { set_create_error(who + ": " + why); return code; };
+    constexpr uint64_t W = DF_CHUNK;
+    if (!d_text && (n_head || n_body)) return fail(LEON_E_INVALID, "d_text is NULL with text given");
+    if (!sink) return fail(LEON_E_INVALID, "sink is NULL");
+    if (!n_taken) return fail(LEON_E_INVALID, "n_taken is NULL");
+    if (!out_bytes) return fail(LEON_E_INVALID, "out_bytes is NULL");
+    if (!n_members) return fail(LEON_E_INVALID, "n_members is NULL");
+    if ((member_out_off == nullptr) != (member_text_off == nullptr) || (!member_out_off && members_cap)) return fail(LEON_E_INVALID, "bgzf records: a half-given member table");
+    if (const char* why = bgzf_records_refusal(d_rec_off != nullptr, n_records, n_head, n_body, last)) return fail(LEON_E_INVALID, why);
+    *n_taken = 0; *out_bytes = 0; *n_members = 0;
+    const bool fixed = !d_rec_off && !n_head;                     // (and no records: refused above otherwise)
+    const uint64_t n_text = n_head + n_body;
+    BgzfIndex ix;
+    ix.out = member_out_off; ix.text = member_text_off;
+    uint64_t at = 0, members = 0, taken = 0;
+    if (fixed) {
+        taken = last ? n_text : n_text - n_text % W;
+        const uint64_t need = (taken + W - 1) / W;
+        if (ix.out && need > members_cap) { *n_members = need; return fail(LEON_E_OVERFLOW, "the member table needs " + std::to_string(need) + " entries"); }
+        if (taken) {
+            const int rc = bgzf_fixed(device_id, d_text, taken, sink, user, &ix, who, &at, &members);
+            if (rc) return rc;
+        }
+    } else if (d_rec_off || n_text) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) { (void)hipGetLastError(); return fail(LEON_E_NO_DEVICE, "no such HIP device"); }
+        if (device_id >= DF_MAX_DEVICES) return fail(LEON_E_INVALID, "device ordinal beyond the scratch table");
+        DCHK(hipSetDevice(device_id));
+        BgzfScratch& S = bgzf_table()[device_id];
+        std::lock_guard<std::mutex> lock(S.mu);
+        S.device = device_id;
+        BgzfStream st;
+        DCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+        hipStream_t s = st.s;
+        DCHK(S.state.ensure(8 * 8));
+        uint64_t h_state[5] = {0, 0, 0, 0, 0};
+        if (d_rec_off) {                                          // the offsets are checked before anything is indexed with them
+            uint32_t flags[3] = {0, 0, 0};
+            DCHK(hipMemsetAsync(S.state.p, 0, sizeof flags, s));
+            hipLaunchKernelGGL(k_bgzf_check_recs, dim3((uint32_t)((n_records + 1 + 255) / 256)), dim3(256), 0, s, d_rec_off, n_records, n_body, S.state.as<uint32_t>());
+            DCHK(hipGetLastError());
+            DCHK(hipMemcpyAsync(flags, S.state.p, sizeof flags, hipMemcpyDeviceToHost, s));
+            DCHK(hipStreamSynchronize(s));
+            if (const char* why = bgzf_offsets_refusal((flags[0] ? 1u : 0u) | (flags[1] ? 2u : 0u) | (flags[2] ? 4u : 0u))) return fail(LEON_E_INVALID, why);
+        }
+        const uint64_t n_starts = (n_head ? 1 : 0) + n_records + 1, bound = 3 * (n_text / W) + 2;
+        auto cuts = [&](uint64_t k, uint64_t skip, uint64_t budget_end, uint64_t cap, uint64_t* begin, uint32_t* len) -> int {
+            hipLaunchKernelGGL(k_bgzf_cuts, dim3(1), dim3(BGZF_CUT_T), 0, s, d_rec_off, n_starts, n_head, k, skip, budget_end, n_text, (uint32_t)last, cap, begin, len,
+                               S.state.as<uint64_t>());
+            DCHK(hipGetLastError());
+            DCHK(hipMemcpyAsync(h_state, S.state.p, sizeof h_state, hipMemcpyDeviceToHost, s));
+            DCHK(hipStreamSynchronize(s));
+            return LEON_OK;
+        };
+        if (ix.out && members_cap < bound) {                      // a table that may be too small: found out before a byte is delivered, by one counting walk
+            if (const int rc = cuts(0, 0, ~0ull, ~0ull, nullptr, nullptr)) return rc;
+            if (h_state[0] > members_cap) { *n_members = h_state[0]; return fail(LEON_E_OVERFLOW, "the member table needs " + std::to_string(h_state[0]) + " entries"); }
+        }
+        const uint64_t slice = bgzf_slice_text();
+        uint64_t k = 0, skip = 0;
+        for (;;) {                                                // sequential: a slice ends at a cut, the next one begins there
+            const uint64_t cap = 3 * (std::min(slice, n_text - taken) / W) + 4;
+            DCHK(S.begin.ensure((cap + 1) * 8)); DCHK(S.len.ensure(cap * 4));
+            if (const int rc = cuts(k, skip, taken + slice, cap, S.begin.as<uint64_t>(), S.len.as<uint32_t>())) return rc;
+            const uint64_t n = h_state[0], end = h_state[3];
+            if (n > cap || end < taken + n || end > n_text || h_state[1] >= n_starts || members + n > bound || (ix.out && members + n > members_cap))
+                return fail(LEON_E_OVERFLOW, "the cut table does not add up");
+            if (n) {
+                uint64_t size = 0;
+                const int rc = bgzf_members_out(S, device_id, s, d_text, n, taken, end, at, 0, sink, user, &ix, who, &size);
+                if (rc) return rc;
+                at += size; members += n;
+            }
+            k = h_state[1]; skip = h_state[2]; taken = end;
+            if (!n || !h_state[4]) break;
+        }
+        if (members > bound) return fail(LEON_E_OVERFLOW, "more members than 3 * (n_text / W) + 2");
+        if (last && taken != n_text) return fail(LEON_E_OVERFLOW, "the cut table does not add up");
+    }
+    if (last) {
+        if (sink(user, at, kBgzfEof, sizeof kBgzfEof)) return fail(LEON_E_SINK, "the sink returned non-zero");
+        at += sizeof kBgzfEof;
+    }
+    *n_taken = taken; *out_bytes = at; *n_members = members;
     return LEON_OK;
 }
 

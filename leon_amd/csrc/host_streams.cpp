@@ -561,3 +561,60 @@ int leon_host_letters_apply(uint8_t* bases, uint64_t n_bytes, const uint64_t* ru
     });
     return LEON_OK;
 }
+
+// ---- BGZF members cut at record starts: the host form of k_bgzf_cuts' rule ----
+namespace leon {
+// what leon_text_bgzf_records_device and leon_host_bgzf_record_cuts both refuse, in the same words; nullptr: the arguments are in order
+const char* bgzf_records_refusal(bool have_off, uint64_t n_records, uint64_t n_head, uint64_t n_body, int last) {
+    if (last != 0 && last != 1) return "bgzf records: last is neither 0 nor 1";
+    if (n_head > LEON_BGZF_MEMBER_TEXT) return "bgzf records: n_head is above LEON_BGZF_MEMBER_TEXT";
+    if (n_records && !have_off) return "bgzf records: records given with rec_off NULL";
+    if (!n_records && n_body && (have_off || n_head)) return "bgzf records: n_body != 0 without records in record mode";
+    if ((n_records >> 58) || (n_body >> 62)) return "bgzf records: implausible sizes";
+    return nullptr;
+}
+// flags: 1 the offsets run backwards or stand still somewhere, 2 the first is not 0, 4 the last is not n_body
+const char* bgzf_offsets_refusal(uint32_t flags) {
+    if (flags & 2u) return "bgzf records: the record offsets do not start at 0";
+    if (flags & 1u) return "bgzf records: the record offsets are not strictly ascending";
+    if (flags & 4u) return "bgzf records: the record offsets do not end at n_body";
+    return nullptr;
+}
+}  // namespace leon
+
+int leon_host_bgzf_record_cuts(const uint64_t* rec_off, uint64_t n_records, uint64_t n_head, int last, uint64_t* begin, uint32_t* len,
+                               uint64_t cap, uint64_t* n_members, uint64_t* n_taken) {
+    constexpr uint64_t W = LEON_BGZF_MEMBER_TEXT;
+    if (!n_members || !n_taken) return fail(LEON_E_INVALID, "bgzf records: n_members or n_taken is NULL");
+    *n_members = 0; *n_taken = 0;
+    if ((begin == nullptr) != (len == nullptr) || (!begin && cap)) return fail(LEON_E_INVALID, "bgzf records: a half-given member table");
+    if (n_records && !rec_off) return fail(LEON_E_INVALID, leon::bgzf_records_refusal(false, n_records, n_head, 0, last));
+    const uint64_t n_body = rec_off ? rec_off[n_records] : 0;
+    if (const char* why = leon::bgzf_records_refusal(rec_off != nullptr, n_records, n_head, n_body, last)) return fail(LEON_E_INVALID, why);
+    uint32_t flags = rec_off && rec_off[0] != 0 ? 2u : 0u;
+    for (uint64_t r = 0; r < n_records; r++) if (rec_off[r + 1] <= rec_off[r]) { flags |= 1u; break; }
+    if (const char* why = leon::bgzf_offsets_refusal(flags)) return fail(LEON_E_INVALID, why);
+    // the record starts of the call's text: 0 when there is a head (one record as far as the rule goes), then the body's
+    const uint64_t hs = n_head ? 1 : 0, n_starts = hs + n_records + 1, n_text = n_head + n_body;
+    auto S = [&](uint64_t k) { return k < hs ? 0 : n_head + (rec_off ? rec_off[k - hs] : 0); };
+    uint64_t n = 0, k = 0;
+    auto emit = [&](uint64_t a, uint64_t m) { if (n < cap) { begin[n] = a; len[n] = (uint32_t)m; } n++; };
+    while (k + 1 < n_starts) {
+        const uint64_t p = S(k);
+        if (!last && n_text - p <= W) break;
+        const uint64_t next = S(k + 1);
+        if (next - p > W) {                                       // an oversized record: members of its own
+            for (uint64_t a = p; a < next; a += W) emit(a, std::min(W, next - a));
+            k++;
+            continue;
+        }
+        uint64_t lo = k + 1, hi = std::min(n_starts - 1, k + W);  // the largest start <= p + W (records have at least one byte)
+        while (lo < hi) { const uint64_t mid = lo + (hi - lo + 1) / 2; if (S(mid) <= p + W) lo = mid; else hi = mid - 1; }
+        emit(p, S(lo) - p);
+        k = lo;
+    }
+    *n_members = n; *n_taken = S(k);
+    if (n > 3 * (n_text / W) + 2) return fail(LEON_E_OVERFLOW, "bgzf records: more members than the bound allows");
+    if (begin && n > cap) return fail(LEON_E_OVERFLOW, "bgzf records: the member table needs " + std::to_string(n) + " entries");
+    return LEON_OK;
+}

@@ -152,33 +152,81 @@ Metadata read_metadata(Container& in, const std::string& file) {
 // `-gz`: a round's text leaves as BGZF members of LEON_BGZF_MEMBER_TEXT bytes, compressed where the device has it
 // (leon_text_bgzf_device); what does not fill a member waits in `carry` and goes in front of the next round's text, so the file is
 // the same bytes however the text was cut into rounds and whoever formatted them.  All of it is stage C's (one round at a time).
+// `-gz-records`: the members are cut at record starts (leon_text_bgzf_records_device with the records' offsets), and
+// the carry -- whole records, at most one member's text -- is the next call's head.  `-gz-index`: every member's place in the file and
+// in the text is kept for X.d.gz.gzi.
 struct BgzfWriter {
-    static constexpr uint64_t HEAD = LEON_BGZF_MEMBER_TEXT;  // room in front of a round's text for the carry (always below one member)
+    static constexpr uint64_t HEAD = LEON_BGZF_MEMBER_TEXT;  // room in front of a round's text for the carry (at most one member's text)
     int fd = -1, device = 0;
     const std::string* out_name = nullptr;
     std::vector<uint8_t> carry;
     uint64_t file_at = 0, members = 0, text = 0;
-    bool closed = false;
-    // n_all bytes of device memory (the carry and a text behind it) through the call; returns the bytes it took
-    uint64_t compress(const uint8_t* d_all, uint64_t n_all, bool last) {
+    bool closed = false, records = false, index = false;
+    std::vector<uint64_t> gzi;                               // `-gz-index`: per data member, its offset in the file and in the text
+    std::vector<uint64_t> m_out, m_text;
+    // n_head + n_body bytes of device memory (the carry and a text behind it) through the call; returns the bytes it took.  The body's
+    // records start at d_rec_off[0 .. n_records] (device memory; looked at under `-gz-records` only)
+    uint64_t compress(const uint8_t* d_all, uint64_t n_head, uint64_t n_body, const uint64_t* d_rec_off, uint64_t n_records, bool last) {
         FileSink sink{fd, file_at};
         uint64_t taken = 0, out_bytes = 0, n_members = 0;
-        const int rc = leon_text_bgzf_device(device, d_all, n_all, last ? 1 : 0, FileSink::piece, &sink, &taken, &out_bytes, &n_members);
-        if (rc == LEON_E_SINK) throw Exception("cannot write " + *out_name);
-        check(nullptr, rc, "leon_text_bgzf_device");
+        const uint64_t n_all = n_head + n_body;
+        if (!records && !index) {
+            const int rc = leon_text_bgzf_device(device, d_all, n_all, last ? 1 : 0, FileSink::piece, &sink, &taken, &out_bytes, &n_members);
+            if (rc == LEON_E_SINK) throw Exception("cannot write " + *out_name);
+            check(nullptr, rc, "leon_text_bgzf_device");
+        } else {
+            if (!records) { n_head = 0; n_body = n_all; d_rec_off = nullptr; n_records = 0; }      // fixed cuts, with the members' places
+            const uint64_t cap = !index ? 0 : records ? 3 * (n_all / HEAD) + 2 : n_all / HEAD + 1;
+            if (m_out.size() < cap) { m_out.resize(cap); m_text.resize(cap); }
+            const int rc = leon_text_bgzf_records_device(device, d_all, n_head, n_body, d_rec_off, n_records, last ? 1 : 0, FileSink::piece, &sink, &taken, &out_bytes,
+                                                         index ? m_out.data() : nullptr, index ? m_text.data() : nullptr, cap, &n_members);
+            if (rc == LEON_E_SINK) throw Exception("cannot write " + *out_name);
+            check(nullptr, rc, "leon_text_bgzf_records_device");
+            if (index) for (uint64_t c = 0; c < n_members; c++) { gzi.push_back(file_at + m_out[c]); gzi.push_back(text + m_text[c]); }
+        }
         file_at += out_bytes; members += n_members; text += taken;
         if (last) closed = true;
         return taken;
     }
+    // `-gz-records`, a text the host formatted: pieces of whole records of at most one slice of the call, each with what the piece
+    // before left as its head; leon_host_bgzf_record_cuts says where a piece's rest begins, and the device has to agree
+    void records_from_host(uint8_t* p_text, uint64_t n_text, const std::vector<uint64_t>& rec_off, bool last, uint64_t piece) {
+        const uint64_t n_rec = rec_off.size() - 1;
+        uint64_t head = carry.size(), ra = 0;                 // the piece's text begins at p_text + rec_off[ra] - head
+        std::vector<uint64_t> rel;
+        do {
+            uint64_t rb = (uint64_t)(std::upper_bound(rec_off.begin() + ra, rec_off.end(), rec_off[ra] + (piece > head ? piece - head : 0)) - rec_off.begin()) - 1;
+            rb = std::min(std::max(rb, ra + 1), n_rec);       // at least one record
+            const uint64_t n = rb - ra, body = rec_off[rb] - rec_off[ra], m = head + body;
+            DeviceMem d, d_off;
+            if (!d.try_alloc(device, m + 64) || !d_off.try_alloc(device, (n + 1) * 8)) {
+                if (n <= 1) throw Exception("-gz-records: the device has no memory for the text of one record");
+                piece = std::max<uint64_t>(piece / 2, 1);
+                continue;
+            }
+            rel.resize(n + 1);
+            for (uint64_t i = 0; i <= n; i++) rel[i] = rec_off[ra + i] - rec_off[ra];
+            if (m) check(nullptr, leon_device_upload(device, d.get(), p_text + rec_off[ra] - head, m), "leon_device_upload");
+            check(nullptr, leon_device_upload(device, d_off.get(), rel.data(), (n + 1) * 8), "leon_device_upload");
+            const bool fin = last && rb == n_rec;
+            uint64_t host_members = 0, host_taken = 0;
+            check(nullptr, leon_host_bgzf_record_cuts(rel.data(), n, head, fin ? 1 : 0, nullptr, nullptr, 0, &host_members, &host_taken), "leon_host_bgzf_record_cuts");
+            if (compress(d.as<uint8_t>(), head, body, d_off.as<uint64_t>(), n, fin) != host_taken)
+                throw Exception("leon_text_bgzf_records_device: a piece was not cut where leon_host_bgzf_record_cuts cuts it");
+            head = m - host_taken; ra = rb;
+        } while (ra < n_rec);
+        carry.assign(p_text + n_text - head, p_text + n_text);
+    }
     // a text the host formatted, with HEAD bytes of room in front of it: up it goes behind the carry, in pieces of whole members of at
     // most one slice of the call; a piece the device has no memory for is halved
-    void from_host(uint8_t* p_text, uint64_t n_text, bool last) {
+    void from_host(uint8_t* p_text, uint64_t n_text, const std::vector<uint64_t>& rec_off, bool last) {
         const uint64_t nc = carry.size();
         uint8_t* const all = p_text - nc;
         if (nc) memcpy(all, carry.data(), nc);
         const uint64_t n_all = nc + n_text, todo = last ? n_all : n_all - n_all % HEAD;
         uint64_t piece = 512ull << 20;
         if (const char* e = getenv("LEON_BGZF_SLICE")) { const long long v = atoll(e); if (v > 0) piece = (uint64_t)v; }
+        if (records) return records_from_host(p_text, n_text, rec_off, last, piece);
         piece = std::max<uint64_t>(piece / HEAD, 1) * HEAD;
         for (uint64_t at = 0; at < todo;) {
             const uint64_t m = std::min(piece, todo - at);
@@ -189,17 +237,17 @@ struct BgzfWriter {
                 continue;
             }
             check(nullptr, leon_device_upload(device, d.get(), all + at, m), "leon_device_upload");
-            if (compress(d.as<uint8_t>(), m, last && at + m == todo) != m) throw Exception("leon_text_bgzf_device: a piece of whole members was not taken whole");
+            if (compress(d.as<uint8_t>(), 0, m, nullptr, 0, last && at + m == todo) != m) throw Exception("leon_text_bgzf_device: a piece of whole members was not taken whole");
             at += m;
         }
         carry.assign(all + todo, all + n_all);
     }
     // a text the device formatted, with HEAD bytes of room in front of it: it never crosses to the host uncompressed
-    void from_device(uint8_t* d_text, uint64_t n_text, bool last) {
+    void from_device(uint8_t* d_text, uint64_t n_text, const uint64_t* d_rec_off, uint64_t n_records, bool last) {
         const uint64_t nc = carry.size(), n_all = nc + n_text;
         uint8_t* const d_all = d_text - nc;
         if (nc) check(nullptr, leon_device_upload(device, d_all, carry.data(), nc), "leon_device_upload");
-        const uint64_t taken = compress(d_all, n_all, last);
+        const uint64_t taken = compress(d_all, nc, n_text, d_rec_off, n_records, last);
         carry.resize(n_all - taken);
         if (!carry.empty()) check(nullptr, leon_device_download(device, carry.data(), d_all + taken, carry.size()), "leon_device_download");
     }
@@ -231,7 +279,7 @@ struct Decoder {
     std::vector<uint64_t> anchors;
     std::future<void> dict_job;
     std::string out_path;
-    OutFile ofd;
+    OutFile ofd, gzi_fd;                                     // (`-gz-index`: the index beside the file)
     bool rt_asked = false, rt_device = false, qi_device = false, hdr_text_device = false, hdr_on_device = false;
     std::string rt_reason;                                   // why the host formats although the device was asked for
     std::atomic<uint64_t> rt_rounds_on_device{0}, rt_rounds_no_memory{0}, qi_rounds_on_device{0}, qi_rounds_no_memory{0};
@@ -336,6 +384,12 @@ void Decoder::open_output() {
     if (ofd.fd < 0) throw Exception("cannot write " + o._outputFilename);
     ofd.path = out_path;
     gz.fd = ofd.fd; gz.device = dev; gz.out_name = &o._outputFilename;
+    gz.records = o._gzRecords; gz.index = o._gzIndex;
+    if (o._gzIndex) {                                        // X.fastq.d.gz.gzi, under a temporary name like the file it belongs to
+        gzi_fd.fd = ::open((o._outputFilename + ".gzi.tmp").c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (gzi_fd.fd < 0) throw Exception("cannot write " + o._outputFilename + ".gzi");
+        gzi_fd.path = o._outputFilename + ".gzi.tmp";
+    }
     // (read here, not with the rest of the metadata: a table that is refused takes the output file with it, as a failed run does)
     if (m.fastq_out && m.has_header && in.exists(DS_PLUS_LINES)) {
         const std::vector<uint8_t> blob = in.getBytes(DS_PLUS_LINES);
@@ -760,7 +814,7 @@ void Decoder::write_round(Round& R) {
         for (auto& t : th) t.join();
     }
     if (write_failed) throw Exception("cannot write " + o._outputFilename);
-    if (o._gz) gz.from_host(reinterpret_cast<uint8_t*>(tbase), n_text, R.last);
+    if (o._gz) gz.from_host(reinterpret_cast<uint8_t*>(tbase), n_text, rec_off, R.last);
     lap(tl, t_text);
 }
 
@@ -771,10 +825,11 @@ bool Decoder::write_round_device(Round& R) {
     auto tl = std::chrono::steady_clock::now();
     const uint64_t g_reads = R.g_reads, g_bases = R.g_bases, n_text = R.n_text;
     check_qual_lengths(R);
-    DeviceMem d_text, d_qual, d_hdr, d_hoff;
+    DeviceMem d_text, d_qual, d_hdr, d_hoff, d_rec;
     auto upload = [&](void* d, const void* src, uint64_t n) { check(nullptr, leon_device_upload(dev, d, src, n), "leon_device_upload"); };
     const uint64_t head = o._gz ? BgzfWriter::HEAD : 0;       // `-gz`: room for the carry right in front of the text
     if (!d_text.try_alloc(dev, head + n_text + 64)) return false;
+    if (o._gzRecords && !d_rec.try_alloc(dev, (g_reads + 1) * 8)) return false;       // `-gz-records`: the records' offsets stay on the device
     uint8_t* const d_txt = d_text.as<uint8_t>() + head;
     if (m.fastq_out && !R.d_qual) {
         if (!d_qual.try_alloc(dev, g_bases + 64)) return false;
@@ -795,11 +850,12 @@ bool Decoder::write_round_device(Round& R) {
     lay.struct_size = (uint32_t)sizeof(lay); lay.lead = (uint8_t)m.lead; lay.fastq = m.fastq_out ? 1 : 0; lay.plus_kind = m.fastq_out && m.plus.def == 1 ? 1 : 0;
     lay.wrap = (uint32_t)std::min<uint64_t>(m.wrap, 0xFFFFFFFFull); lay.first_read_index = R.read_index; lay.hdr_bytes = hb;
     uint64_t size = 0;
-    const int rc = leon_records_format_device(dev, &lay, R.d_bases(), R.dna->d_lens.as<uint32_t>() + R.read0, g_reads, g_bases, hp, ho, quals, d_txt, n_text, nullptr, &size);
+    const int rc = leon_records_format_device(dev, &lay, R.d_bases(), R.dna->d_lens.as<uint32_t>() + R.read0, g_reads, g_bases, hp, ho, quals, d_txt, n_text,
+                                              o._gzRecords ? d_rec.as<uint64_t>() : nullptr, &size);
     if (rc == LEON_E_OVERFLOW || (rc == LEON_OK && size != n_text)) throw Exception(file + ": the decoded reads do not add up to their blocks' sizes");
     check(nullptr, rc, "leon_records_format_device");
     R.d_qual.reset();
-    if (o._gz) gz.from_device(d_txt, n_text, R.last);         // one call instead of the downloads
+    if (o._gz) gz.from_device(d_txt, n_text, o._gzRecords ? d_rec.as<uint64_t>() : nullptr, g_reads, R.last);    // one call instead of the downloads
     else download_text(R, d_txt);
     rt_rounds_on_device++;
     lap(tl, t_text);
@@ -858,13 +914,32 @@ void Decoder::finish() {
     }
     if (o._gz && !gz.closed) {                                // (a file without a round: the EOF marker alone)
         if (!gz.carry.empty()) throw Exception("-gz: text was left over behind the last round");
-        (void)gz.compress(nullptr, 0, true);
+        (void)gz.compress(nullptr, 0, 0, nullptr, 0, true);
     }
     if (::close(ofd.fd) != 0) { ofd.fd = -1; throw Exception("cannot write " + o._outputFilename); }
     ofd.fd = -1;
     if (read_index != m.p.n_reads) throw Exception("the block tables do not add up to the header's read count");
+    if (o._gzIndex) {
+        // the .gzi: a little-endian count, then (offset in the file, offset in the text) of every data member but the first
+        std::vector<uint64_t> words(1, gz.members ? gz.members - 1 : 0);
+        if (gz.gzi.size() != 2 * gz.members) throw Exception("-gz-index: the members' places do not add up");
+        if (gz.members) words.insert(words.end(), gz.gzi.begin() + 2, gz.gzi.end());
+        std::vector<uint8_t> bytes(words.size() * 8);
+        for (size_t i = 0; i < words.size(); i++) for (int b = 0; b < 8; b++) bytes[8 * i + b] = (uint8_t)(words[i] >> (8 * b));
+        const bool wrote = write_all(gzi_fd.fd, bytes.data(), bytes.size(), 0);
+        const bool closed = ::close(gzi_fd.fd) == 0;
+        gzi_fd.fd = -1;
+        if (!wrote || !closed) throw Exception("cannot write " + o._outputFilename + ".gzi");
+    }
     if (o._gz && std::rename(out_path.c_str(), o._outputFilename.c_str()) != 0) throw Exception("cannot write " + o._outputFilename);
     ofd.keep = true;
+    if (o._gzIndex) {
+        if (std::rename(gzi_fd.path.c_str(), (o._outputFilename + ".gzi").c_str()) != 0) {
+            std::remove(o._outputFilename.c_str());          // neither file is left
+            throw Exception("cannot write " + o._outputFilename + ".gzi");
+        }
+        gzi_fd.keep = true;
+    }
 }
 
 // "device (kernel), N round(s)[, M round(s) on the host threads for want of device memory]"
@@ -897,7 +972,9 @@ void Decoder::report() {
     if (m.fastq_out)
         std::cout << "quality blocks: " << (qi_device ? rounds_text("k_qual_inflate", qi_rounds_on_device.load(), qi_rounds_no_memory.load()) : std::string("host threads")) << std::endl;
     if (o._gz)
-        std::cout << "output: BGZF on the device (k_deflate_chunks, k_bgzf_members), " << gz.members << " member(s), " << gz.text << " -> " << gz.file_at << " bytes" << std::endl;
+        std::cout << "output: BGZF on the device (k_deflate_chunks, k_bgzf_members), " << gz.members << " member(s), " << gz.text << " -> " << gz.file_at << " bytes"
+                  << (o._gzRecords ? ", record-aligned" : "")
+                  << (o._gzIndex ? ", index " + o._outputFilename + ".gzi (" + std::to_string(gz.members ? gz.members - 1 : 0) + " entries)" : std::string()) << std::endl;
 }
 
 }  // namespace

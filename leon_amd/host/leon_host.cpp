@@ -55,6 +55,8 @@ void Leon::run(int argc, char* argv[]) {
             else if (a == "-ignore-checksum") _ignoreChecksum = true;
             else if (a == "-letters") _letters = true;
             else if (a == "-gz") _gz = true;
+            else if (a == "-gz-records") _gzRecords = true;
+            else if (a == "-gz-index") _gzIndex = true;
             else if (a == "-qual-deflate") { _qualDeflate = need("-qual-deflate"); (void)qual_encoder_choice(_qualDeflate); }
             else if (a == "-input-inflate") { _inputInflate = need("-input-inflate"); (void)parse_choice("-input-inflate", _inputInflate); }
             else if (a == "-header-text") { _headerText = need("-header-text"); (void)parse_choice("-header-text", _headerText); }
@@ -68,6 +70,8 @@ void Leon::run(int argc, char* argv[]) {
         if (_ignoreChecksum && _compress) throw Exception("option -ignore-checksum belongs to -d");
         if (_letters && _decompress) throw Exception("option -letters belongs to -c: -d restores the letters whenever the container holds them");
         if (_gz && _compress) throw Exception("option -gz belongs to -d");
+        if (_gzRecords && !_gz) throw Exception("option -gz-records belongs to -gz");
+        if (_gzIndex && !_gz) throw Exception("option -gz-index belongs to -gz");
         if (!_inputInflate.empty() && _decompress) throw Exception("option -input-inflate belongs to -c");
         if (_seqOnly) _noHeader = _noQual = true;             // "same as -noheader -noqual", /root/reference/README.md:56
         execute();

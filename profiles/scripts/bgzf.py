@@ -7,6 +7,10 @@
                                        `rocprofv3 --kernel-trace --stats` (kernel times come from there; the JSON line carries the calls'
                                        wall times, which include the copy of the output to the host); text bytes / a kernel's time is to be
                                        read against the float4 copy measured on this chip, 6.29 TB/s
+  bgzf.py --kernel [N] --records       the same, and behind it leon_text_bgzf_records_device on the same text with every
+                                       record's offset (found on the device: every fourth newline), one warm-up call on the first records
+                                       and TWO whole calls, with member tables; the JSON line gains the calls' wall times, members and
+                                       bytes.  Under `rocprofv3 --kernel-trace --stats`: k_bgzf_cuts beside k_deflate_chunks
   bgzf.py --cli N --parent LEON        `leon -d`, `leon -d -gz` and the parent commit's `leon -d` on the lossless container of an N-read
                                        150 bp FASTQ in a RAM-backed directory, alternating, three each, -header-text device -record-text
                                        device -qual-inflate device on every side; the output sizes and the `time:` and `output:` lines of
@@ -33,6 +37,7 @@ from leon_amd import capi  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--kernel", type=int, nargs="?", const=10_000_000, default=0)
+ap.add_argument("--records", action="store_true")
 ap.add_argument("--cli", type=int, default=0)
 ap.add_argument("--parent", default="")
 ap.add_argument("--dir", default="/dev/shm/leon_bgzf")
@@ -85,7 +90,33 @@ def kernel():
     z6_s = time.perf_counter() - t0
     c = zlib.compressobj(6, zlib.DEFLATED, -15, 9, zlib.Z_RLE)
     zrle = len(c.compress(sample) + c.flush())
-    print(json.dumps({"reads": N, "text_bytes": n, "leon_text_bgzf_device_ms": ms, **whole, "text_per_out": round(n / whole["out_bytes"], 4),
+    rec = {}
+    if args.records:
+        nl = (d[:n] == 10).nonzero().flatten()
+        assert len(nl) == 4 * N
+        off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), nl[3::4] + 1]).contiguous()
+        del nl
+        torch.cuda.synchronize()
+        cap = capi.bgzf_members_bound(n)
+        m_out, m_text = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)
+
+        def call_records(n_records, last):
+            counted[0] = 0
+            n_body = int(off[n_records])
+            rc = lib.leon_text_bgzf_records_device(0, C.c_void_p(d.data_ptr()), 0, n_body, C.c_void_p(off.data_ptr()), n_records, last, sink, None, C.byref(taken),
+                                                   C.byref(out_bytes), C.c_void_p(m_out.ctypes.data), C.c_void_p(m_text.ctypes.data), cap, C.byref(members))
+            assert rc == 0, lib.leon_last_error(None)
+            assert counted[0] == out_bytes.value and (not last or taken.value == n_body)
+        call_records(min(N, 1000), 1)
+        rms = []
+        for _ in range(2):
+            t0 = time.perf_counter()
+            call_records(N, 1)
+            rms.append(round((time.perf_counter() - t0) * 1e3, 2))
+        assert m_text[0] == 0 and (np.diff(m_text[:members.value].astype(np.int64)) <= capi.BGZF_MEMBER_TEXT).all()
+        rec = {"leon_text_bgzf_records_device_ms": rms, "records_members": members.value, "records_out_bytes": out_bytes.value,
+               "records_out_per_fixed_out": round(out_bytes.value / whole["out_bytes"], 6)}
+    print(json.dumps({"reads": N, "text_bytes": n, "leon_text_bgzf_device_ms": ms, **whole, **rec, "text_per_out": round(n / whole["out_bytes"], 4),
                       "sample_bytes": m, "sample_out_bytes": len(got), "sample_reads_back": gzip.decompress(got) == sample,
                       "sample_zlib6_bytes": z6, "sample_zlib6_one_thread_gb_s": round(m / z6_s / 1e9, 4), "sample_zlib_rle_bytes": zrle,
                       "float4_copy_tb_s": COPY_TBS,
