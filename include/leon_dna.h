@@ -54,12 +54,15 @@ typedef struct leon_dna_cfg {
     const uint64_t* random_values; /* optional 256-entry simplehash16 table; NULL = built-in */
     uint64_t resolve_window;     /* reads per anchor-resolution window; 0 = default (1<<21) */
     uint32_t flags;              /* LEON_F_* */
-    uint32_t reserved;
+    uint32_t dict_piece_anchors; /* with LEON_F_DICT_PIECES: anchors per piece, 0 = 1024, otherwise 1 .. 2^20; must be 0 without the flag */
 } leon_dna_cfg;
 
 #define LEON_F_KEEP_TRACE 1u     /* keep per-read anchors / events of the last batch for leon_dna_trace_* */
 #define LEON_F_DICT_ON_DEVICE 2u /* code the anchor-dictionary stream with the device range coder (one serial chain on one
                                     workgroup, ~50x slower than the default host thread: DESIGN.md 4.4) instead of the host thread */
+#define LEON_F_DICT_PIECES 4u    /* write the anchor dictionary as independently coded PIECES of dict_piece_anchors anchors (a different
+                                    stream: leon_dna_dict_pieces below), coded on the device by leon_dna_finish; the host
+                                    chain is not fed.  Not together with LEON_F_DICT_ON_DEVICE. */
 
 /* Replaces Leon::writeBlock(buffer, size, nReads, blockId): called on the calling thread, in increasing
  * block_id; payload is owned by the library and valid until the sink returns.  Non-zero aborts. */
@@ -204,6 +207,32 @@ int leon_device_download(int device_id, void* dst, const void* d_src, uint64_t b
  * Leon::encodeInsertedAnchor over `kmers` in address order followed by the flush.  Used by the CPU tests. */
 int leon_host_anchor_dict_encode(const uint64_t* kmers, uint64_t n_anchors, uint32_t kmer_size, uint8_t* out,
                                  uint64_t out_cap, uint64_t* size);
+
+/* -- the anchor dictionary in independently coded pieces --
+ * Anchors in address order are cut into pieces of P = piece_anchors anchors (0 = 1024, at most 2^20; the last piece holds the rest),
+ * n_pieces = ceil(n_anchors / P).  Piece p is exactly the bytes leon_host_anchor_dict_encode returns for anchors [p * P, min((p + 1) * P,
+ * n_anchors)): a fresh model, a fresh coder, the 8 flush bytes.  The stream is the pieces back to back; piece_off (n_pieces + 1 entries,
+ * piece_off[0] = 0) says where each begins.
+ * leon_dna_dict_pieces: after leon_dna_finish on a context created with LEON_F_DICT_PIECES -- whose dict_payload is then this stream --
+ * its table; *piece_off is the context's until leon_dna_reset_stream or destroy.  LEON_E_STATE before leon_dna_finish or without the flag.
+ * The context-free calls work on a stream of their own beside calls on any context and are complete on return.
+ * encode: d_kmers (n_anchors * W words) in DEVICE memory, out / piece_off in host memory; *size = the stream's bytes, LEON_E_OVERFLOW when
+ * out_cap is smaller (piece_off is filled, out is not written).  k_dict_encode_pieces, lane = piece.
+ * decode: everything in host memory; out_kmers (n_anchors * W words) is written only when every piece has decoded, else LEON_E_INVALID
+ * "anchor dictionary piece N does not decode" names the SMALLEST piece that fails.  k_dict_decode_pieces, lane = piece.
+ * The leon_host_ twins do the same without a device (the encode twin takes the k-mers in host memory), one piece per task on n_threads
+ * host threads (0 = all this process may use).  They are the verdict for the device calls: the same arguments are refused, before a
+ * device is touched, with the same code and words -- null pointers, kmer_size outside 1..63, piece_anchors above 2^20, "piece table does
+ * not match the anchor count" (n_pieces != ceil(n_anchors / P)), "piece offsets run backwards".  Errors: leon_last_error(NULL). */
+int leon_dna_dict_pieces(leon_dna_ctx* ctx, const uint64_t** piece_off, uint64_t* n_pieces, uint32_t* piece_anchors);
+int leon_anchor_dict_encode_pieces_device(int device_id, const uint64_t* d_kmers, uint64_t n_anchors, uint32_t kmer_size, uint32_t piece_anchors,
+                                          uint8_t* out, uint64_t out_cap, uint64_t* piece_off, uint64_t* size);
+int leon_anchor_dict_decode_pieces_device(int device_id, const uint8_t* payload, const uint64_t* piece_off, uint64_t n_pieces, uint64_t n_anchors,
+                                          uint32_t kmer_size, uint32_t piece_anchors, uint64_t* out_kmers);
+int leon_host_anchor_dict_encode_pieces(const uint64_t* kmers, uint64_t n_anchors, uint32_t kmer_size, uint32_t piece_anchors, uint8_t* out,
+                                        uint64_t out_cap, uint64_t* piece_off, uint64_t* size, uint32_t n_threads);
+int leon_host_anchor_dict_decode_pieces(const uint8_t* payload, const uint64_t* piece_off, uint64_t n_pieces, uint64_t n_anchors,
+                                        uint32_t kmer_size, uint32_t piece_anchors, uint64_t* out_kmers, uint32_t n_threads);
 
 /* -- the inverse path: DnaDecoder::execute over read blocks, blocks in parallel on the device --
  * Needs the bloom of the compressed file in ctx (leon_dna_bloom_upload).  anchors: the dictionary (n_anchors * W words,

@@ -11,6 +11,8 @@ ABI_VERSION = 5          # include/leon_dna.h LEON_DNA_ABI_VERSION this binding 
 HEADER_TEXT_DEVICE_CAP = 4096   # the longest header k_hdr_text builds on the device (kernels.h LEON_HT_HEADER_CAP); longer ones go to the host decoder
 LEON_F_KEEP_TRACE = 1
 LEON_F_DICT_ON_DEVICE = 2
+LEON_F_DICT_PIECES = 4
+DICT_PIECE_ANCHORS_DEFAULT, DICT_PIECE_ANCHORS_MAX = 1024, 1 << 20
 
 
 class LeonDnaError(RuntimeError):
@@ -27,7 +29,7 @@ class _Cfg(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("kmer_size", C.c_uint32), ("reads_per_block", C.c_uint32),
                 ("bloom_n_hash", C.c_uint32), ("bloom_block_nbits", C.c_uint32), ("device_id", C.c_int32),
                 ("bloom_tai", C.c_uint64), ("random_values", C.POINTER(C.c_uint64)), ("resolve_window", C.c_uint64),
-                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+                ("flags", C.c_uint32), ("dict_piece_anchors", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -158,6 +160,11 @@ _EXPORTS = {
     "leon_letters_take_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]),
     "leon_letters_apply_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]),
     "leon_host_letters_apply": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
+    "leon_dna_dict_pieces": (C.c_int, [C.c_void_p, C.POINTER(_u64p), _u64p, _u32p]),
+    "leon_anchor_dict_encode_pieces_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "leon_anchor_dict_decode_pieces_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "leon_host_anchor_dict_encode_pieces": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "leon_host_anchor_dict_decode_pieces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
 }
 EXPORTED_SYMBOLS = tuple(_EXPORTS)
 _lib = None
@@ -217,6 +224,74 @@ def host_anchor_dict_encode(kmers, k):
     if rc:
         raise LeonDnaError(rc, "leon_host_anchor_dict_encode failed")
     return out[:size.value].tobytes()
+
+
+def dict_piece_count(n_anchors, piece_anchors=0):
+    """pieces a dictionary of n_anchors anchors is cut into (piece_anchors = 0: the default of 1024)"""
+    P = piece_anchors or DICT_PIECE_ANCHORS_DEFAULT
+    return (int(n_anchors) + P - 1) // P
+
+
+def _dict_pieces_encode(call, kmers_arg, n_anchors, k, piece_anchors, out_cap, tail):
+    """the two encode calls: (stream bytes, piece_off uint64[n_pieces + 1]); LEON_E_OVERFLOW is answered with a buffer of the size asked for"""
+    lib = load_library()
+    off = np.zeros(dict_piece_count(n_anchors, min(piece_anchors, DICT_PIECE_ANCHORS_MAX)) + 1, dtype=np.uint64)
+    size = C.c_uint64()
+    cap = int(n_anchors) * k // 3 + 64 if out_cap is None else int(out_cap)
+    for _ in range(2):
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        rc = call(kmers_arg, int(n_anchors), k, piece_anchors, C.c_void_p(out.ctypes.data), cap, C.c_void_p(off.ctypes.data),
+                  C.c_void_p(C.addressof(size)), *tail)
+        if rc != -5 or out_cap is not None:
+            break
+        cap = size.value
+    if rc:
+        err = LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+        err.size, err.piece_off = size.value, off
+        raise err
+    return out[:size.value].tobytes(), off
+
+
+def host_anchor_dict_encode_pieces(kmers, k, piece_anchors=0, n_threads=0, out_cap=None):
+    """leon_host_anchor_dict_encode_pieces (no GPU): kmers = flat uint64 array, kmer_words(k) words per anchor"""
+    lib = load_library()
+    kmers = np.ascontiguousarray(kmers, dtype=np.uint64).reshape(-1)
+    n = len(kmers) // kmer_words(k) if 1 <= k <= 63 else len(kmers)
+    return _dict_pieces_encode(lambda *a: lib.leon_host_anchor_dict_encode_pieces(*a), C.c_void_p(kmers.ctypes.data if len(kmers) else 0), n, k,
+                               piece_anchors, out_cap, (n_threads,))
+
+
+def anchor_dict_encode_pieces_device(d_kmers, n_anchors, k, piece_anchors=0, device_id=0, out_cap=None):
+    """leon_anchor_dict_encode_pieces_device: d_kmers = a raw device pointer (integer) to n_anchors * kmer_words(k) words"""
+    lib = load_library()
+    return _dict_pieces_encode(lambda kp, *a: lib.leon_anchor_dict_encode_pieces_device(device_id, kp, *a), C.c_void_p(int(d_kmers)), n_anchors, k,
+                               piece_anchors, out_cap, ())
+
+
+def _dict_pieces_decode(call, payload, piece_off, n_anchors, k, piece_anchors, n_pieces, out):
+    lib = load_library()
+    buf = np.frombuffer(bytes(payload) + b"\0", dtype=np.uint8)
+    off = np.ascontiguousarray(piece_off, dtype=np.uint64)
+    if n_pieces is None:
+        n_pieces = len(off) - 1
+    if out is None:
+        out = np.zeros(max(int(n_anchors) * kmer_words(k), 1), dtype=np.uint64)
+    rc = call(C.c_void_p(buf.ctypes.data), C.c_void_p(off.ctypes.data), int(n_pieces), int(n_anchors), k, piece_anchors, C.c_void_p(out.ctypes.data))
+    if rc:
+        raise LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+    return out[:int(n_anchors) * kmer_words(k)]
+
+
+def host_anchor_dict_decode_pieces(payload, piece_off, n_anchors, k, piece_anchors=0, n_threads=0, n_pieces=None, out=None):
+    """leon_host_anchor_dict_decode_pieces (no GPU): the anchors' k-mer words; `out` (a uint64 array) is written only when every piece decodes"""
+    lib = load_library()
+    return _dict_pieces_decode(lambda *a: lib.leon_host_anchor_dict_decode_pieces(*a, n_threads), payload, piece_off, n_anchors, k, piece_anchors, n_pieces, out)
+
+
+def anchor_dict_decode_pieces_device(payload, piece_off, n_anchors, k, piece_anchors=0, device_id=0, n_pieces=None, out=None):
+    """leon_anchor_dict_decode_pieces_device: host memory in and out, the pieces decoded on the device"""
+    lib = load_library()
+    return _dict_pieces_decode(lambda *a: lib.leon_anchor_dict_decode_pieces_device(device_id, *a), payload, piece_off, n_anchors, k, piece_anchors, n_pieces, out)
 
 
 def _join_blocks(blocks):
@@ -811,14 +886,17 @@ class DnaEncodeContext:
     """One ordered read stream on one GPU (wraps leon_dna_ctx)."""
 
     def __init__(self, kmer_size=31, reads_per_block=50000, bloom_tai=0, bloom_n_hash=7, bloom_block_nbits=12,
-                 device_id=0, resolve_window=0, keep_trace=False, random_values=None, dict_on_device=False):
+                 device_id=0, resolve_window=0, keep_trace=False, random_values=None, dict_on_device=False, dict_pieces=False,
+                 dict_piece_anchors=0):
         self.lib = load_library()
         cfg = _Cfg()
         cfg.struct_size = C.sizeof(_Cfg)
         cfg.kmer_size, cfg.reads_per_block = kmer_size, reads_per_block
         cfg.bloom_n_hash, cfg.bloom_block_nbits, cfg.device_id = bloom_n_hash, bloom_block_nbits, device_id
         cfg.bloom_tai, cfg.resolve_window = int(bloom_tai), int(resolve_window)
-        cfg.flags = (LEON_F_KEEP_TRACE if keep_trace else 0) | (LEON_F_DICT_ON_DEVICE if dict_on_device else 0)
+        cfg.flags = (LEON_F_KEEP_TRACE if keep_trace else 0) | (LEON_F_DICT_ON_DEVICE if dict_on_device else 0) | \
+            (LEON_F_DICT_PIECES if dict_pieces else 0)
+        cfg.dict_piece_anchors = dict_piece_anchors
         self._rv = None
         if random_values is not None:
             self._rv = np.ascontiguousarray(random_values, dtype=np.uint64)
@@ -1078,6 +1156,12 @@ class DnaEncodeContext:
         p, sz, na = _u8p(), C.c_uint64(), C.c_uint64()
         self._chk(self.lib.leon_dna_finish(self.h, C.byref(p), C.byref(sz), C.byref(na)))
         return (C.string_at(p, sz.value) if copy else sz.value), na.value
+
+    def dict_pieces(self):
+        """leon_dna_dict_pieces, after finish() on a context created with dict_pieces=True: (piece_off uint64[n_pieces + 1], piece_anchors)"""
+        p, n, pa = _u64p(), C.c_uint64(), C.c_uint32()
+        self._chk(self.lib.leon_dna_dict_pieces(self.h, C.byref(p), C.byref(n), C.byref(pa)))
+        return np.ctypeslib.as_array(p, shape=(n.value + 1,)).astype(np.uint64, copy=True), pa.value
 
     def decode_blocks(self, anchors, blocks, block_n_bases):
         """DnaDecoder over read blocks: blocks = [(block_id, payload, n_reads)] as the encoder's sink delivered them,

@@ -6,6 +6,7 @@
 #include "staging.h"
 #include "host_blocks.h"
 #include "host_bgzf.h"
+#include "host_dict_pieces.h"
 
 #include "prim.h"
 
@@ -118,7 +119,8 @@ struct leon_dna_ctx {
     DevBuf anchor_kmers;
     AnchorDictWorker* anchor_worker = nullptr;   // host thread coding the dictionary stream, fed per window
     double anchor_wait_ms = 0;
-    std::vector<uint8_t> dict_device_out;        // LEON_F_DICT_ON_DEVICE: the stream coded by k_rc_encode
+    std::vector<uint8_t> dict_device_out;        // LEON_F_DICT_ON_DEVICE: the stream coded by k_rc_encode; LEON_F_DICT_PIECES: the pieces back to back
+    std::vector<uint64_t> dict_piece_off;        // LEON_F_DICT_PIECES: where each piece begins (n_pieces + 1 entries), from leon_dna_finish on
     // stream state
     uint64_t next_read = 0, next_block = 0;
     uint32_t shard_rank = 0, shard_world = 1;    // leon_dna_set_shard
@@ -618,6 +620,10 @@ int leon_dna_ctx_create(const leon_dna_cfg* cfg, leon_dna_ctx** out) {
         if ((tai0 & (tai0 - 1)) == 0) tai0--;
         if (tai0 <= 2 * blk0 || cfg->bloom_tai > (1ull << 46)) return fail(nullptr, LEON_E_INVALID, "bloom_tai out of range (1 .. 2^46 bits)");
     }
+    if ((cfg->flags & LEON_F_DICT_PIECES) && (cfg->flags & LEON_F_DICT_ON_DEVICE))
+        return fail(nullptr, LEON_E_INVALID, "LEON_F_DICT_PIECES and LEON_F_DICT_ON_DEVICE exclude each other");
+    if (cfg->dict_piece_anchors && !(cfg->flags & LEON_F_DICT_PIECES)) return fail(nullptr, LEON_E_INVALID, "dict_piece_anchors needs LEON_F_DICT_PIECES");
+    if (cfg->dict_piece_anchors > kDictPieceAnchorsMax) return fail(nullptr, LEON_E_INVALID, "dict_piece_anchors must be in 1..2^20 (0 = 1024)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(nullptr, LEON_E_NO_DEVICE, "no HIP device: the DNA encode path has no CPU fallback");
@@ -1129,7 +1135,7 @@ struct EncodeBatch {
             std::swap(static_cast<DevBuf&>(nb).cap, c->anchor_kmers.cap);
         }
         launch_assign_addr(s, c->D, V, w0, w1, c->rank.as<uint32_t>(), c->n_anchors, c->anchor_kmers.as<uint64_t>(), k);
-        if (n_new && c->shard_rank == 0 && !(c->cfg.flags & LEON_F_DICT_ON_DEVICE)) {   // the window's new anchors, for the host thread coding the dictionary stream
+        if (n_new && c->shard_rank == 0 && !(c->cfg.flags & (LEON_F_DICT_ON_DEVICE | LEON_F_DICT_PIECES))) {   // the window's new anchors, for the host thread coding the dictionary stream
             HIPCHK(c, hipMemcpyAsync(c->h_anchor[anchor_buf], c->anchor_kmers.as<uint64_t>() + c->n_anchors * KW, n_new * 8 * KW, hipMemcpyDeviceToHost, s));
             pending.buf = anchor_buf; pending.n = n_new;
             anchor_buf ^= 1;
@@ -1645,10 +1651,144 @@ int leon_qual_smooth_batch(leon_dna_ctx* c, const uint8_t* bases, const uint64_t
     return LEON_OK;
 }
 
+// ---- the anchor dictionary in independently coded pieces (dict_kernels.hip) ----
+// The pieces of d_kmers coded on stream s: piece_off (host, n_pieces + 1 entries) and the stream's bytes, back to back, in d_dst.
+// A piece's slot is first P * k / 2 + 64 bytes, twice what a genomic dictionary needs (2 bits a base); a list that does not fit --
+// nothing but adversarial k-mers -- is coded again with 8 bytes per symbol, the most a step can shift out (k_dict_encode_pieces).
+static int dict_pieces_code(leon_dna_ctx* c, hipStream_t s, const uint64_t* d_kmers, uint64_t n_anchors, uint32_t k, uint32_t P, uint64_t* piece_off, TmpBuf& d_dst) {
+    const uint64_t n_pieces = dict_piece_count(n_anchors, P);
+    piece_off[0] = 0;
+    if (!n_pieces) return LEON_OK;
+    const uint64_t piece_syms = (uint64_t)std::min<uint64_t>(P, n_anchors) * k;
+    TmpBuf d_scratch, d_sizes, d_off, d_err, d_tmp;
+    HIPCHK(c, d_sizes.ensure((n_pieces + 1) * 8)); HIPCHK(c, d_off.ensure((n_pieces + 1) * 8)); HIPCHK(c, d_err.ensure(4));
+    HIPCHK(c, hipMemsetAsync((uint64_t*)d_sizes.p + n_pieces, 0, 8, s));
+    uint64_t stride = 0;
+    for (int wide = 0;; wide++) {
+        stride = ((wide ? 8 * piece_syms + 12 : piece_syms / 2 + 64) + 7) & ~7ull;
+        HIPCHK(c, d_scratch.ensure(n_pieces * stride));
+        HIPCHK(c, hipMemsetAsync(d_err.p, 0, 4, s));
+        launch_dict_encode_pieces(s, d_kmers, n_anchors, k, P, n_pieces, d_scratch.as<uint8_t>(), stride, d_sizes.as<uint64_t>(), d_err.as<int>());
+        HIPCHK(c, hipGetLastError());
+        int err = 0;
+        HIPCHK(c, hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        if (!err) break;
+        if (wide) return fail(c, LEON_E_OVERFLOW, "anchor dictionary pieces: a piece outgrew 8 bytes per symbol (internal error)");
+    }
+    size_t tmp_bytes = 0;
+    HIPCHK(c, prim::ExclusiveSum(nullptr, tmp_bytes, d_sizes.as<uint64_t>(), d_off.as<uint64_t>(), n_pieces + 1, s));
+    HIPCHK(c, d_tmp.ensure(tmp_bytes + 16));
+    HIPCHK(c, prim::ExclusiveSum(d_tmp.p, tmp_bytes, d_sizes.as<uint64_t>(), d_off.as<uint64_t>(), n_pieces + 1, s));
+    HIPCHK(c, hipMemcpyAsync(piece_off, d_off.p, (n_pieces + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, d_dst.ensure(piece_off[n_pieces] + 16));
+    launch_dict_gather_pieces(s, d_scratch.as<uint8_t>(), stride, d_off.as<uint64_t>(), n_pieces, d_dst.as<uint8_t>());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s));
+    return LEON_OK;
+}
+
+int leon_dna_dict_pieces(leon_dna_ctx* c, const uint64_t** piece_off, uint64_t* n_pieces, uint32_t* piece_anchors) {
+    if (!c || !piece_off || !n_pieces || !piece_anchors) return LEON_E_INVALID;
+    if (!(c->cfg.flags & LEON_F_DICT_PIECES)) return fail(c, LEON_E_STATE, "leon_dna_dict_pieces: the context was created without LEON_F_DICT_PIECES");
+    if (!c->finished || c->dict_piece_off.empty()) return fail(c, LEON_E_STATE, "leon_dna_dict_pieces must follow leon_dna_finish");
+    *piece_off = c->dict_piece_off.data();
+    *n_pieces = c->dict_piece_off.size() - 1;
+    *piece_anchors = dict_piece_anchors(c->cfg.dict_piece_anchors);
+    return LEON_OK;
+}
+
+int leon_anchor_dict_encode_pieces_device(int device_id, const uint64_t* d_kmers, uint64_t n_anchors, uint32_t k, uint32_t piece_anchors, uint8_t* out,
+                                          uint64_t out_cap, uint64_t* piece_off, uint64_t* size) {
+    if (const char* why = dict_pieces_encode_refusal(d_kmers, n_anchors, k, piece_anchors, out, out_cap, piece_off, size)) return fail(nullptr, LEON_E_INVALID, why);
+    const uint32_t P = dict_piece_anchors(piece_anchors);
+    *size = 0; piece_off[0] = 0;
+    if (!n_anchors) return LEON_OK;                               // no piece: no device is asked
+    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_NO_DEVICE, "leon_anchor_dict_encode_pieces_device: no such HIP device"); }
+    // a stream of its own: the call runs beside calls on the contexts' streams
+    struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
+    HIPCHK(nullptr, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    TmpBuf d_dst;
+    if (int rc = dict_pieces_code(nullptr, st.s, d_kmers, n_anchors, k, P, piece_off, d_dst)) return rc;
+    *size = piece_off[dict_piece_count(n_anchors, P)];
+    if (*size > out_cap) return fail(nullptr, LEON_E_OVERFLOW, "anchor dictionary pieces: out_cap too small");
+    HIPCHK(nullptr, hipMemcpyAsync(out, d_dst.p, *size, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(nullptr, hipStreamSynchronize(st.s));
+    return LEON_OK;
+}
+
+int leon_anchor_dict_decode_pieces_device(int device_id, const uint8_t* payload, const uint64_t* piece_off, uint64_t n_pieces, uint64_t n_anchors, uint32_t k,
+                                          uint32_t piece_anchors, uint64_t* out_kmers) {
+    if (const char* why = dict_pieces_decode_refusal(payload, piece_off, n_pieces, n_anchors, k, piece_anchors, out_kmers)) return fail(nullptr, LEON_E_INVALID, why);
+    if (!n_pieces) return LEON_OK;                                // no piece: no device is asked
+    const uint32_t P = dict_piece_anchors(piece_anchors), W = kmer_words(k);
+    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_NO_DEVICE, "leon_anchor_dict_decode_pieces_device: no such HIP device"); }
+    struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
+    HIPCHK(nullptr, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    hipStream_t s = st.s;
+    // the pieces' bytes alone travel: [piece_off[0], piece_off[n_pieces]), the offsets rebased to them
+    const uint64_t first = piece_off[0], bytes = piece_off[n_pieces] - first;
+    std::vector<uint64_t> rel(n_pieces + 1);
+    for (uint64_t p = 0; p <= n_pieces; p++) rel[p] = piece_off[p] - first;
+    TmpBuf d_pay, d_off, d_out, d_bad;
+    HIPCHK(nullptr, d_pay.ensure(bytes + 16)); HIPCHK(nullptr, d_off.ensure((n_pieces + 1) * 8));
+    HIPCHK(nullptr, d_out.ensure(n_anchors * W * 8)); HIPCHK(nullptr, d_bad.ensure(n_pieces * 4));
+    if (bytes && staged_h2d(device_id, d_pay.p, payload + first, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_HIP, "leon_anchor_dict_decode_pieces_device: the pieces' copy to the device failed"); }
+    HIPCHK(nullptr, hipMemcpyAsync(d_off.p, rel.data(), (n_pieces + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(nullptr, hipMemsetAsync(d_bad.p, 0, n_pieces * 4, s));
+    launch_dict_decode_pieces(s, d_pay.as<uint8_t>(), d_off.as<uint64_t>(), n_pieces, n_anchors, k, P, d_out.as<uint64_t>(), d_bad.as<uint32_t>());
+    HIPCHK(nullptr, hipGetLastError());
+    std::vector<uint32_t> bad(n_pieces);
+    HIPCHK(nullptr, hipMemcpyAsync(bad.data(), d_bad.p, n_pieces * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(nullptr, hipStreamSynchronize(s));
+    for (uint64_t p = 0; p < n_pieces; p++) if (bad[p]) return fail(nullptr, LEON_E_INVALID, dict_piece_refusal(p));
+    HIPCHK(nullptr, hipMemcpyAsync(out_kmers, d_out.p, n_anchors * W * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(nullptr, hipStreamSynchronize(s));
+    return LEON_OK;
+}
+
+int leon_host_anchor_dict_encode_pieces(const uint64_t* kmers, uint64_t n_anchors, uint32_t k, uint32_t piece_anchors, uint8_t* out, uint64_t out_cap,
+                                        uint64_t* piece_off, uint64_t* size, uint32_t n_threads) {
+    std::string why;
+    const int rc = host_dict_encode_pieces(kmers, n_anchors, k, piece_anchors, out, out_cap, piece_off, size, n_threads, why);
+    return rc ? fail(nullptr, rc, why) : LEON_OK;
+}
+int leon_host_anchor_dict_decode_pieces(const uint8_t* payload, const uint64_t* piece_off, uint64_t n_pieces, uint64_t n_anchors, uint32_t k,
+                                        uint32_t piece_anchors, uint64_t* out_kmers, uint32_t n_threads) {
+    std::string why;
+    const int rc = host_dict_decode_pieces(payload, piece_off, n_pieces, n_anchors, k, piece_anchors, out_kmers, n_threads, why);
+    return rc ? fail(nullptr, rc, why) : LEON_OK;
+}
+
 int leon_dna_finish(leon_dna_ctx* c, const uint8_t** payload, uint64_t* size, uint64_t* n_anchors) {
     if (!c || !payload || !size || !n_anchors) return LEON_E_INVALID;
     if (c->poisoned) return fail(c, LEON_E_STATE, "an earlier batch failed part-way: the stream is unusable until leon_dna_reset_stream");
     auto t0 = std::chrono::steady_clock::now();
+    if (c->cfg.flags & LEON_F_DICT_PIECES) {
+        if (!c->finished) {
+            c->dict_device_out.clear();
+            c->dict_piece_off.assign(1, 0);
+            if (c->shard_rank == 0 && c->n_anchors) {              // the dictionary stream is rank 0's to write
+                HIPCHK(c, hipSetDevice(c->device));
+                const uint32_t P = dict_piece_anchors(c->cfg.dict_piece_anchors);
+                c->dict_piece_off.assign(dict_piece_count(c->n_anchors, P) + 1, 0);
+                TmpBuf d_dst;
+                if (int rc = dict_pieces_code(c, c->stream, c->anchor_kmers.as<uint64_t>(), c->n_anchors, c->cfg.kmer_size, P, c->dict_piece_off.data(), d_dst)) {
+                    c->dict_piece_off.clear();
+                    return rc;
+                }
+                c->dict_device_out.resize(c->dict_piece_off.back());
+                if (!c->dict_device_out.empty()) HIPCHK(c, hipMemcpy(c->dict_device_out.data(), d_dst.p, c->dict_device_out.size(), hipMemcpyDeviceToHost));
+            }
+            c->finished = true;
+        }
+        c->anchor_wait_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        *payload = c->dict_device_out.data();
+        *size = c->dict_device_out.size();
+        *n_anchors = c->n_anchors;
+        return LEON_OK;
+    }
     if (c->cfg.flags & LEON_F_DICT_ON_DEVICE) {
         if (!c->finished) {
             c->dict_device_out.clear();
@@ -1733,6 +1873,7 @@ int leon_dna_reset_stream(leon_dna_ctx* c) {
     const auto t_enter = std::chrono::steady_clock::now();
     struct Done { bool on; std::chrono::steady_clock::time_point t0; ~Done() { if (on) fprintf(stderr, "[leon step] %-34s %8.2f ms\n", "reset_stream", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); } } done{trace_step, t_enter};
     c->anchor_worker->reset();
+    c->dict_piece_off.clear();
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, spin_sync(c->stream));
     HIPCHK(c, hipMemsetAsync(c->fbits.p, 0, (1ull << c->fbits_log2) / 8, c->stream));

@@ -40,10 +40,11 @@ class ReciprocalStream {
 public:
     static constexpr uint64_t kChunk = 1ull << 18;
     static constexpr uint32_t kBufs = 12, kThreads = 3;         // one 128/64-bit division per symbol: ~3 threads keep ahead
-    ReciprocalStream() { for (auto& b : buf_) b.resize(kChunk); }
+    ReciprocalStream() = default;
     ~ReciprocalStream() { stop(); }
     void restart() {                                           // a new stream: t starts at 0 again
         stop();
+        for (auto& b : buf_) b.resize(kChunk);                 // (25 MB, only for a stream that asks for reciprocals: a decoder of short pieces never does)
         consumed_ = 0; quit_ = false;
         for (auto& h : holds_) h = 0;
         for (uint32_t j = 0; j < kThreads; j++) th_[j] = std::thread([this, j] { run(j); });

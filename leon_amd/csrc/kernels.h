@@ -253,4 +253,16 @@ void launch_crc32_segments(hipStream_t s, const uint8_t* bytes, const uint64_t* 
 // ---- lower-case runs and bytes outside ACGTN of a device buffer (letters_kernels.hip), DESIGN.md 4.12 ----
 constexpr uint64_t LETTERS_MAX_GROUPS = 2048;                  // the grid's cap: a workgroup walks ceil(tiles / cap) consecutive 4 KiB tiles
 
+// ---- the anchor dictionary in independently coded pieces (dict_kernels.hip), DESIGN.md 4.4 ----
+constexpr uint32_t DICT_PIECES_MAX_GROUPS = 1024;              // the grid's cap: a wave codes 64 pieces (lane = piece), then the 64 a grid further on
+// piece p = anchors [p * P, min((p + 1) * P, n_anchors)) of kmers, coded into scratch[p * stride .. + stride) (stride >= 64), sizes[p] its
+// bytes; *err (zeroed by the caller) is set when a piece came within 4 bytes of its stride: code again with a wider one
+void launch_dict_encode_pieces(hipStream_t s, const uint64_t* kmers, uint64_t n_anchors, uint32_t k, uint32_t P, uint64_t n_pieces, uint8_t* scratch,
+                               uint64_t stride, uint64_t* sizes, int* err);
+// the slots back to back: off[n_pieces + 1] = the exclusive sums of sizes
+void launch_dict_gather_pieces(hipStream_t s, const uint8_t* scratch, uint64_t stride, const uint64_t* off, uint64_t n_pieces, uint8_t* dst);
+// piece p = payload[off[p] .. off[p + 1]) -> its anchors' k-mer words in out; bad[p] (zeroed by the caller) is set for a piece that does not decode
+void launch_dict_decode_pieces(hipStream_t s, const uint8_t* payload, const uint64_t* off, uint64_t n_pieces, uint64_t n_anchors, uint32_t k, uint32_t P,
+                               uint64_t* out, uint32_t* bad);
+
 }  // namespace leon

@@ -165,6 +165,7 @@ struct Compressor {
     std::vector<CtxPtr> ctx;
     std::vector<uint8_t> bloom;
     const uint8_t* dict = nullptr; uint64_t dict_size = 0, n_anchors = 0;
+    std::vector<uint64_t> dict_piece_table;                      // -dict-pieces: what leon/anchors/dict_piece_table gets
     // The jobs that run beside the pass read the members above (the batch buffers, d_qbuf, the writers) in place: they are the last
     // members, so they are joined before anything they read goes.
     std::future<void> qual_job, hdr_sum_job;
@@ -372,7 +373,7 @@ void Compressor::kmers_and_bloom() {
         batch_max_reads = std::max(batch_max_reads, r1 - r0); batch_max_bases = std::max(batch_max_bases, offsets[r1] - offsets[r0]);
     }
     for (int g = 0; g < n_gpus; g++) {
-        ctx.push_back(make_ctx(k, tai, store[g]->device));
+        ctx.push_back(make_ctx(k, tai, store[g]->device, 7, 12, Leon::READ_PER_BLOCK, o._dictPieces ? LEON_F_DICT_PIECES : 0u, o._dictPieceAnchors));
         check(ctx[g].get(), leon_dna_set_shard(ctx[g].get(), (uint32_t)g, (uint32_t)n_gpus), "leon_dna_set_shard");
         // every per-batch buffer sized now, in one go, before the bloom is built and copied: the first (usually only) encode
         // call then allocates nothing large
@@ -409,6 +410,13 @@ void Compressor::encode_dna() {
     for (const std::string& e : gpu_error) if (!e.empty()) throw Exception(e);
     check(ctx[0].get(), leon_dna_finish(ctx[0].get(), &dict, &dict_size, &n_anchors), "leon_dna_finish");
     for (int g = 1; g < n_gpus; g++) { const uint8_t* d; uint64_t ds, na; check(ctx[g].get(), leon_dna_finish(ctx[g].get(), &d, &ds, &na), "leon_dna_finish"); }
+    if (o._dictPieces) {                                         // the table beside the stream: the kind, anchors per piece, every piece's bytes
+        const uint64_t* piece_off = nullptr; uint64_t n_pieces = 0; uint32_t piece_anchors = 0;
+        check(ctx[0].get(), leon_dna_dict_pieces(ctx[0].get(), &piece_off, &n_pieces, &piece_anchors), "leon_dna_dict_pieces");
+        dict_piece_table.assign(2, 0);
+        dict_piece_table[0] = DICT_PIECES_ORDER0; dict_piece_table[1] = piece_anchors;
+        for (uint64_t p = 0; p < n_pieces; p++) dict_piece_table.push_back(piece_off[p + 1] - piece_off[p]);
+    }
     t_encode = seconds_since(t_dna);
 }
 
@@ -533,7 +541,10 @@ void Compressor::write_tables() {
             out->putBytes(DS_LETTER_ODD_BYTES, letter_odd_bytes.data(), letter_odd_bytes.size());
         }
     }
-    out->putBytes(DS_ANCHOR_DICT, dict, dict_size);
+    if (o._dictPieces) {
+        out->putBytes(DS_ANCHOR_DICT_PIECES, dict, dict_size);
+        out->putU64(DS_ANCHOR_DICT_PIECE_TABLE, dict_piece_table.data(), dict_piece_table.size());
+    } else out->putBytes(DS_ANCHOR_DICT, dict, dict_size);
     out->putBytes(DS_BLOOM_BITS, bloom.data(), bloom.size());
     const uint8_t info = (uint8_t)((fastq ? 0 : INFO_FASTA) | (keep_header ? 0 : INFO_NO_HEADER) | (keep_qual ? 0 : INFO_NO_QUAL) | (o._lossless ? INFO_LOSSLESS : 0));
     out->putBytes(DS_INFOBYTE, &info, 1);
@@ -559,6 +570,8 @@ void Compressor::report() {
                              << (qual_on_device ? " (deflated on the device: runs + dynamic Huffman codes)" : " (zlib on the host threads)") << "\n";
     if (checksum) std::cout << "checksums: CRC-32 of " << n_blocks << " blocks (dna" << (keep_header ? ", header" : "") << (keep_qual ? ", quality" : "") << ")\n";
     std::cout << "written to " << o._outputFilename << std::endl;
+    if (o._verbose && o._dictPieces)
+        std::cout << "dictionary: " << dict_piece_table.size() - 2 << " pieces of " << dict_piece_table[1] << " anchors on the device (k_dict_encode_pieces), " << dict_size << " bytes\n";
     if (o._verbose && o._letters) {
         const uint64_t letter_table_bytes = 8 * (1 + letter_runs.size()) + 9 * letter_odd_pos.size();
         if (has_letters()) std::cout << "letters: " << letter_runs.size() / 2 << " lower-case run(s), " << letter_odd_pos.size() << " other byte(s) kept (" << letter_table_bytes << " bytes)\n";

@@ -33,6 +33,9 @@ constexpr const char* DS_LETTER_RUNS = "leon/metadata/letter_runs";            /
 constexpr const char* DS_LETTER_ODD_POS = "leon/metadata/letter_odd_pos";      // u64[X]: the positions of the bytes outside ACGTN (absent: X = 0)
 constexpr const char* DS_LETTER_ODD_BYTES = "leon/metadata/letter_odd_bytes";  // u8[X]: the original bytes
 constexpr const char* DS_ANCHOR_DICT = "leon/anchors/dict";            // u8[]: the anchor-dictionary stream
+// `-c -dict-pieces`: the dictionary as independently coded pieces, INSTEAD of leon/anchors/dict -- a file holds one form or the other
+constexpr const char* DS_ANCHOR_DICT_PIECES = "leon/anchors/dict_pieces";          // u8[]: the pieces back to back
+constexpr const char* DS_ANCHOR_DICT_PIECE_TABLE = "leon/anchors/dict_piece_table"; // u64[2 + n_pieces]: the kind (DICT_PIECES_*), anchors per piece, every piece's bytes
 constexpr const char* DS_BLOOM_BITS = "bloom/bits";                    // u8[nchar]
 constexpr const char* BLOCK_PREFIX = "block_";
 enum Param : uint32_t { P_VERSION_MAJOR, P_VERSION_MINOR, P_VERSION_PATCH, P_KMER_SIZE, P_READS_PER_BLOCK, P_N_READS, P_N_ANCHORS,
@@ -49,6 +52,8 @@ enum QualEnc : uint64_t { QUAL_ENC_NONE = 0,          // no quality stream (or a
                           QUAL_ENC_ZLIB = 1,          // zlib's compress2 at its default level (what upstream writes [RECALLED]): the default
                           QUAL_ENC_DEVICE_RLE = 2 };  // the device's deflate (runs + dynamic Huffman codes): inflates to the same text, other bytes
 enum LettersKind : uint64_t { LETTERS_RUNS_AND_BYTES = 1 };   // the rule of DESIGN.md 4.12
+enum DictPiecesKind : uint64_t { DICT_PIECES_ORDER0 = 1 };   // a fresh 5-symbol order-0 model and coder per piece, 8 flush bytes
+constexpr uint64_t DICT_PIECE_ANCHORS_MAX = 1ull << 20;
 enum ChecksumKind : uint64_t { CHECKSUM_CRC32 = 1 };  // zlib's crc32 over the block's bytes of the stream as the decoder returns them
 // info byte: bit 0 FASTA input (else FASTQ), bit 1 no header stream, bit 2 no quality stream, bit 3 lossless qualities
 enum Info : uint8_t { INFO_FASTA = 1, INFO_NO_HEADER = 2, INFO_NO_QUAL = 4, INFO_LOSSLESS = 8 };

@@ -363,6 +363,22 @@ void Decoder::open_device_and_dictionary() {
     // the first round's header / quality blocks, and is waited for right before the first DNA blocks go to the device
     const uint32_t W = p.k >= 32 ? 2 : 1;
     anchors.resize(std::max<uint64_t>(p.n_anchors * W, 1));
+    {
+        // `-c -dict-pieces` wrote the dictionary as independently coded pieces: decoded on the device, at once (k_dict_decode_pieces)
+        const bool has_pieces = in.exists(DS_ANCHOR_DICT_PIECES), has_table = in.exists(DS_ANCHOR_DICT_PIECE_TABLE);
+        const std::vector<uint64_t> table = has_table ? in.getU64(DS_ANCHOR_DICT_PIECE_TABLE) : std::vector<uint64_t>();
+        const std::vector<uint8_t> pieces = has_pieces ? in.getBytes(DS_ANCHOR_DICT_PIECES) : std::vector<uint8_t>();
+        if (plan::check_dict_pieces(file, in.exists(DS_ANCHOR_DICT), has_pieces, has_table, table, pieces.size(), p.n_anchors)) {
+            const uint64_t n_pieces = table.size() - 2;
+            const std::vector<uint64_t> piece_off = plan::prefix_sums(table.data() + 2, n_pieces);
+            const auto t0 = std::chrono::steady_clock::now();
+            if (leon_anchor_dict_decode_pieces_device(dev, pieces.data(), piece_off.data(), n_pieces, p.n_anchors, (uint32_t)p.k, (uint32_t)table[1], anchors.data()) != LEON_OK)
+                throw Exception(file + ": dictionary pieces: " + leon_last_error(nullptr));
+            if (o._verbose) std::cout << "dictionary: " << n_pieces << " pieces of " << table[1] << " anchors decoded on the device (k_dict_decode_pieces) in " << seconds_since(t0) << " s\n";
+            return;                                              // (no dict_job: nothing to wait for)
+        }
+    }
+    if (o._verbose) std::cout << "dictionary: one stream, decoded on a host thread (leon_host_anchor_dict_decode)\n";
     auto dict = std::make_shared<std::vector<uint8_t>>(in.getBytes(DS_ANCHOR_DICT));
     const uint64_t dsz = dict->size(), n_anchors = p.n_anchors;
     dict->push_back(0);

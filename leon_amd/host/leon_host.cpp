@@ -57,6 +57,12 @@ void Leon::run(int argc, char* argv[]) {
             else if (a == "-gz") _gz = true;
             else if (a == "-gz-records") _gzRecords = true;
             else if (a == "-gz-index") _gzIndex = true;
+            else if (a == "-dict-pieces") _dictPieces = true;
+            else if (a == "-dict-piece-anchors") {
+                const long v = number("-dict-piece-anchors");
+                if (v < 1 || v > (1l << 20)) throw Exception("-dict-piece-anchors must be in 1..1048576");
+                _dictPieceAnchors = (uint32_t)v;
+            }
             else if (a == "-qual-deflate") { _qualDeflate = need("-qual-deflate"); (void)qual_encoder_choice(_qualDeflate); }
             else if (a == "-input-inflate") { _inputInflate = need("-input-inflate"); (void)parse_choice("-input-inflate", _inputInflate); }
             else if (a == "-header-text") { _headerText = need("-header-text"); (void)parse_choice("-header-text", _headerText); }
@@ -73,6 +79,8 @@ void Leon::run(int argc, char* argv[]) {
         if (_gzRecords && !_gz) throw Exception("option -gz-records belongs to -gz");
         if (_gzIndex && !_gz) throw Exception("option -gz-index belongs to -gz");
         if (!_inputInflate.empty() && _decompress) throw Exception("option -input-inflate belongs to -c");
+        if (_dictPieces && _decompress) throw Exception("option -dict-pieces belongs to -c: -d reads the pieces whenever the container holds them");
+        if (_dictPieceAnchors && !_dictPieces) throw Exception("option -dict-piece-anchors belongs to -dict-pieces");
         if (_seqOnly) _noHeader = _noQual = true;             // "same as -noheader -noqual", /root/reference/README.md:56
         execute();
     } catch (const Exception&) {

@@ -48,9 +48,11 @@ inline double seconds_since(std::chrono::steady_clock::time_point t0) {
 struct CtxDeleter { void operator()(leon_dna_ctx* c) const { if (c) leon_dna_ctx_destroy(c); } };
 typedef std::unique_ptr<leon_dna_ctx, CtxDeleter> CtxPtr;
 
-inline CtxPtr make_ctx(uint32_t k, uint64_t tai, int device, uint32_t n_hash = 7, uint32_t block_nbits = 12, uint32_t rpb = Leon::READ_PER_BLOCK) {
+inline CtxPtr make_ctx(uint32_t k, uint64_t tai, int device, uint32_t n_hash = 7, uint32_t block_nbits = 12, uint32_t rpb = Leon::READ_PER_BLOCK,
+                       uint32_t flags = 0, uint32_t dict_piece_anchors = 0) {
     leon_dna_cfg cfg = {};
     cfg.struct_size = sizeof(cfg);
+    cfg.flags = flags; cfg.dict_piece_anchors = dict_piece_anchors;
     cfg.kmer_size = k; cfg.reads_per_block = rpb;
     cfg.bloom_n_hash = n_hash; cfg.bloom_block_nbits = block_nbits; cfg.bloom_tai = tai; cfg.device_id = device;
     leon_dna_ctx* c = nullptr;

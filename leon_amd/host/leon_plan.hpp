@@ -121,6 +121,33 @@ inline void check_checksum_table(const std::string& file, const std::vector<uint
     if (tsum[0] != CHECKSUM_CRC32) throw Exception(file + ": unknown checksum kind " + std::to_string(tsum[0]) + " in " + DS_CHECKSUMS + " (this build knows 1 = CRC-32)");
     if (tsum.size() != 1 + 3 * n_blocks) throw Exception(file + ": the checksum table does not match the read count");
 }
+// `-c -dict-pieces`: the piece table against the parameters and the bytes of leon/anchors/dict_pieces.  has_single / has_pieces / has_table:
+// which of leon/anchors/dict, dict_pieces and dict_piece_table the file holds.  Returns false for a file of the single-stream form (the
+// table is then not looked at), true for a checked pieced one; the piece sizes are table[2 ...].
+inline bool check_dict_pieces(const std::string& file, bool has_single, bool has_pieces, bool has_table, const std::vector<uint64_t>& table,
+                              uint64_t piece_bytes, uint64_t n_anchors) {
+    using namespace layout;
+    auto refuse = [&](const std::string& what) { return Exception(file + ": dictionary pieces: " + what); };
+    if (!has_pieces && !has_table) return false;
+    if (has_pieces != has_table) throw refuse(std::string(has_pieces ? DS_ANCHOR_DICT_PIECE_TABLE : DS_ANCHOR_DICT_PIECES) + " is missing");
+    if (has_single) throw refuse(std::string("the file holds ") + DS_ANCHOR_DICT + " as well");
+    if (table.size() < 2) throw refuse("the piece table is too short");
+    if (table[0] != DICT_PIECES_ORDER0) throw refuse("unknown kind " + std::to_string(table[0]) + " in " + DS_ANCHOR_DICT_PIECE_TABLE + " (this build knows 1)");
+    const uint64_t P = table[1];
+    if (P < 1 || P > DICT_PIECE_ANCHORS_MAX) throw refuse(std::to_string(P) + " anchors per piece (1 .. 1048576)");
+    const uint64_t n_pieces = (n_anchors + P - 1) / P;
+    if (table.size() - 2 != n_pieces)
+        throw refuse("the table holds " + std::to_string(table.size() - 2) + " pieces, " + std::to_string(n_anchors) + " anchors in pieces of " + std::to_string(P) + " make " + std::to_string(n_pieces));
+    uint64_t sum = 0;
+    for (uint64_t i = 0; i < n_pieces; i++) {
+        const uint64_t sz = table[2 + i];
+        if (sz < 8) throw refuse("piece " + std::to_string(i) + " has " + std::to_string(sz) + " bytes (a piece ends with 8 flush bytes)");
+        if (sz > piece_bytes - sum) throw refuse("the piece sizes add up to more than the " + std::to_string(piece_bytes) + " bytes of " + DS_ANCHOR_DICT_PIECES);
+        sum += sz;
+    }
+    if (sum != piece_bytes) throw refuse("the piece sizes add up to " + std::to_string(sum) + ", " + DS_ANCHOR_DICT_PIECES + " holds " + std::to_string(piece_bytes) + " bytes");
+    return true;
+}
 inline Exception letters_error(const char* ds, const std::string& what) { return Exception(std::string("letters: ") + ds + " " + what); }
 // the runs as stored (the kind word first); on return the kind word is taken off
 inline void check_letter_runs(std::vector<uint64_t>& runs, uint64_t total_bases) {
