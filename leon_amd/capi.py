@@ -1150,6 +1150,12 @@ class DnaEncodeContext:
             self._chk(self.lib.leon_qual_smooth_batch(self.h, bytes(bases), _ptr(offsets, _u64p), len(offsets) - 1, _ptr(q, _u8p)))
         return q.tobytes()
 
+    def qual_smooth_batch_device(self, d_bases, d_offsets, n_reads, d_quals):
+        """leon_qual_smooth_batch_device: bases, offsets (uint64[n_reads + 1]) and qualities in device memory (raw pointers,
+        device_alloc / device_upload_bytes); read i's qualities lie at d_quals + offsets[i] - offsets[0] and are rewritten in place"""
+        self._chk(self.lib.leon_qual_smooth_batch_device(self.h, C.c_void_p(int(d_bases or 0)), C.c_void_p(int(d_offsets or 0)),
+                                                         int(n_reads), C.c_void_p(int(d_quals or 0))))
+
     def finish(self, copy=True):
         """(dictionary stream, number of anchors); copy=False returns its size instead of a bytes copy (the C caller
         gets a pointer into the context and writes from there: a 100 M-read file's stream is 110 MB)"""
