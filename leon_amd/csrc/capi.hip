@@ -1,12 +1,13 @@
-// capi.hip -- the C-ABI of include/leon_dna.h: context, device memory, and the stage pipeline
+// capi.hip -- the C-ABI of include/leon_dna.h: the context, its device memory, and the stage pipeline
 //   pack -> anchor resolution (windows, fixpoint rounds) -> anchor sort -> walk -> symbols -> range coder -> D2H.
+// The calls that take a device_id instead of a context live beside their kernels (device_call.h).
 #include "../../include/leon_dna.h"
 #include "kernels.h"
 #include "host_rc.h"
 #include "staging.h"
 #include "host_blocks.h"
-#include "host_bgzf.h"
 #include "host_dict_pieces.h"
+#include "device_call.h"
 
 #include "prim.h"
 
@@ -24,42 +25,9 @@
 
 using namespace leon;
 
-namespace {
-
-thread_local std::string g_create_error;
-}
+namespace { thread_local std::string g_create_error; }
 namespace leon { void set_create_error(const std::string& msg) { g_create_error = msg; } }
 namespace {
-
-const bool g_trace_alloc = getenv("LEON_TRACE_ALLOC") != nullptr;   // measurement aid: device allocations of 1 ms or more on stderr
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        auto t0 = std::chrono::steady_clock::now();
-        if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { (void)hipGetLastError(); leon_device_trim(); e = hipMalloc(&p, want); }   // (the k-mer counter's parked buffers: kmer_kernels.hip)
-        if (e == hipSuccess) cap = want;
-        if (g_trace_alloc) {
-            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            if (ms >= 1.0) fprintf(stderr, "[leon alloc] %.1f MB in %.1f ms\n", want / 1e6, ms);
-        }
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <typename T> T* as() const { return (T*)p; }
-};
-// a device buffer that lives for one call: released on every way out of the scope
-struct TmpBuf : DevBuf {
-    TmpBuf() = default;
-    TmpBuf(const TmpBuf&) = delete;
-    TmpBuf& operator=(const TmpBuf&) = delete;
-    ~TmpBuf() { release(); }
-};
 
 uint64_t splitmix_rv(uint32_t idx) {     // built-in simplehash16 table, see DESIGN.md "recalled constants"
     uint64_t s = 0x4C454F4EULL + (uint64_t)(idx + 1) * 0x9E3779B97F4A7C15ULL;
@@ -168,15 +136,16 @@ struct leon_dna_ctx {
 
 namespace {
 
+// a context call's failure: its words stay with the context (device_call.h has the forms for calls without one)
 int fail(leon_dna_ctx* c, int code, const std::string& msg) {
-    if (c) c->err = msg; else g_create_error = msg;
+    if (!c) return dev_fail(code, msg);
+    c->err = msg;
     return code;
 }
 #define HIPCHK(c, call)                                                                         \
     do {                                                                                        \
         hipError_t e_ = (call);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return fail((c), LEON_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));    \
+        if (e_ != hipSuccess) return fail((c), LEON_E_HIP, hip_failure(#call, e_));             \
     } while (0)
 
 void dict_free(DictDev& D) {
@@ -604,30 +573,30 @@ int leon_dna_abi_version(void) { return LEON_DNA_ABI_VERSION; }
 const char* leon_last_error(const leon_dna_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
 int leon_dna_ctx_create(const leon_dna_cfg* cfg, leon_dna_ctx** out) {
-    if (!cfg || !out) return fail(nullptr, LEON_E_INVALID, "null argument");
+    if (!cfg || !out) return dev_fail(LEON_E_INVALID, "null argument");
     *out = nullptr;
-    if (cfg->struct_size != sizeof(leon_dna_cfg)) return fail(nullptr, LEON_E_INVALID, "leon_dna_cfg.struct_size mismatch");
+    if (cfg->struct_size != sizeof(leon_dna_cfg)) return dev_fail(LEON_E_INVALID, "leon_dna_cfg.struct_size mismatch");
     if (cfg->kmer_size < 3 || cfg->kmer_size > 63)
-        return fail(nullptr, LEON_E_INVALID, "kmer_size must be in 3..63 (one 64-bit word below 32, two words from 32 to 63)");
-    if (cfg->reads_per_block == 0) return fail(nullptr, LEON_E_INVALID, "reads_per_block must be > 0");
-    if (cfg->bloom_n_hash < 1 || cfg->bloom_n_hash > 10) return fail(nullptr, LEON_E_INVALID, "bloom_n_hash must be in 1..10");
+        return dev_fail(LEON_E_INVALID, "kmer_size must be in 3..63 (one 64-bit word below 32, two words from 32 to 63)");
+    if (cfg->reads_per_block == 0) return dev_fail(LEON_E_INVALID, "reads_per_block must be > 0");
+    if (cfg->bloom_n_hash < 1 || cfg->bloom_n_hash > 10) return dev_fail(LEON_E_INVALID, "bloom_n_hash must be in 1..10");
     if (cfg->bloom_block_nbits < 4 || cfg->bloom_block_nbits > 16)
-        return fail(nullptr, LEON_E_INVALID, "bloom_block_nbits must be in 4..16");
+        return dev_fail(LEON_E_INVALID, "bloom_block_nbits must be in 4..16");
     {   // BloomNeighborCoherent's modulus tai' - 2 * blk must stay positive (bloom_tai = 0 makes tai a power of two, tai' = tai - 1
         // < 2 * blk), and an absurd size is refused here rather than by hipMalloc
         const uint64_t blk0 = 1ull << cfg->bloom_block_nbits;
         uint64_t tai0 = cfg->bloom_tai + 2 * blk0;
         if ((tai0 & (tai0 - 1)) == 0) tai0--;
-        if (tai0 <= 2 * blk0 || cfg->bloom_tai > (1ull << 46)) return fail(nullptr, LEON_E_INVALID, "bloom_tai out of range (1 .. 2^46 bits)");
+        if (tai0 <= 2 * blk0 || cfg->bloom_tai > (1ull << 46)) return dev_fail(LEON_E_INVALID, "bloom_tai out of range (1 .. 2^46 bits)");
     }
     if ((cfg->flags & LEON_F_DICT_PIECES) && (cfg->flags & LEON_F_DICT_ON_DEVICE))
-        return fail(nullptr, LEON_E_INVALID, "LEON_F_DICT_PIECES and LEON_F_DICT_ON_DEVICE exclude each other");
-    if (cfg->dict_piece_anchors && !(cfg->flags & LEON_F_DICT_PIECES)) return fail(nullptr, LEON_E_INVALID, "dict_piece_anchors needs LEON_F_DICT_PIECES");
-    if (cfg->dict_piece_anchors > kDictPieceAnchorsMax) return fail(nullptr, LEON_E_INVALID, "dict_piece_anchors must be in 1..2^20 (0 = 1024)");
+        return dev_fail(LEON_E_INVALID, "LEON_F_DICT_PIECES and LEON_F_DICT_ON_DEVICE exclude each other");
+    if (cfg->dict_piece_anchors && !(cfg->flags & LEON_F_DICT_PIECES)) return dev_fail(LEON_E_INVALID, "dict_piece_anchors needs LEON_F_DICT_PIECES");
+    if (cfg->dict_piece_anchors > kDictPieceAnchorsMax) return dev_fail(LEON_E_INVALID, "dict_piece_anchors must be in 1..2^20 (0 = 1024)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(nullptr, LEON_E_NO_DEVICE, "no HIP device: the DNA encode path has no CPU fallback");
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(nullptr, LEON_E_INVALID, "device_id out of range");
+        return dev_fail(LEON_E_NO_DEVICE, "no HIP device: the DNA encode path has no CPU fallback");
+    if (cfg->device_id < 0 || cfg->device_id >= ndev) return dev_fail(LEON_E_INVALID, "device_id out of range");
     leon_dna_ctx* c = new leon_dna_ctx();
     c->cfg = *cfg;
     c->cfg.random_values = nullptr;
@@ -637,7 +606,7 @@ int leon_dna_ctx_create(const leon_dna_cfg* cfg, leon_dna_ctx** out) {
     do {                                                                                                         \
         hipError_t e_ = (call);                                                                                  \
         if (e_ != hipSuccess) {                                                                                  \
-            int r_ = fail(nullptr, LEON_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));               \
+            int r_ = dev_fail(LEON_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));               \
             leon_dna_ctx_destroy(c);                                                                             \
             return r_;                                                                                           \
         }                                                                                                        \
@@ -1651,44 +1620,7 @@ int leon_qual_smooth_batch(leon_dna_ctx* c, const uint8_t* bases, const uint64_t
     return LEON_OK;
 }
 
-// ---- the anchor dictionary in independently coded pieces (dict_kernels.hip) ----
-// The pieces of d_kmers coded on stream s: piece_off (host, n_pieces + 1 entries) and the stream's bytes, back to back, in d_dst.
-// A piece's slot is first P * k / 2 + 64 bytes, twice what a genomic dictionary needs (2 bits a base); a list that does not fit --
-// nothing but adversarial k-mers -- is coded again with 8 bytes per symbol, the most a step can shift out (k_dict_encode_pieces).
-static int dict_pieces_code(leon_dna_ctx* c, hipStream_t s, const uint64_t* d_kmers, uint64_t n_anchors, uint32_t k, uint32_t P, uint64_t* piece_off, TmpBuf& d_dst) {
-    const uint64_t n_pieces = dict_piece_count(n_anchors, P);
-    piece_off[0] = 0;
-    if (!n_pieces) return LEON_OK;
-    const uint64_t piece_syms = (uint64_t)std::min<uint64_t>(P, n_anchors) * k;
-    TmpBuf d_scratch, d_sizes, d_off, d_err, d_tmp;
-    HIPCHK(c, d_sizes.ensure((n_pieces + 1) * 8)); HIPCHK(c, d_off.ensure((n_pieces + 1) * 8)); HIPCHK(c, d_err.ensure(4));
-    HIPCHK(c, hipMemsetAsync((uint64_t*)d_sizes.p + n_pieces, 0, 8, s));
-    uint64_t stride = 0;
-    for (int wide = 0;; wide++) {
-        stride = ((wide ? 8 * piece_syms + 12 : piece_syms / 2 + 64) + 7) & ~7ull;
-        HIPCHK(c, d_scratch.ensure(n_pieces * stride));
-        HIPCHK(c, hipMemsetAsync(d_err.p, 0, 4, s));
-        launch_dict_encode_pieces(s, d_kmers, n_anchors, k, P, n_pieces, d_scratch.as<uint8_t>(), stride, d_sizes.as<uint64_t>(), d_err.as<int>());
-        HIPCHK(c, hipGetLastError());
-        int err = 0;
-        HIPCHK(c, hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        if (!err) break;
-        if (wide) return fail(c, LEON_E_OVERFLOW, "anchor dictionary pieces: a piece outgrew 8 bytes per symbol (internal error)");
-    }
-    size_t tmp_bytes = 0;
-    HIPCHK(c, prim::ExclusiveSum(nullptr, tmp_bytes, d_sizes.as<uint64_t>(), d_off.as<uint64_t>(), n_pieces + 1, s));
-    HIPCHK(c, d_tmp.ensure(tmp_bytes + 16));
-    HIPCHK(c, prim::ExclusiveSum(d_tmp.p, tmp_bytes, d_sizes.as<uint64_t>(), d_off.as<uint64_t>(), n_pieces + 1, s));
-    HIPCHK(c, hipMemcpyAsync(piece_off, d_off.p, (n_pieces + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    HIPCHK(c, d_dst.ensure(piece_off[n_pieces] + 16));
-    launch_dict_gather_pieces(s, d_scratch.as<uint8_t>(), stride, d_off.as<uint64_t>(), n_pieces, d_dst.as<uint8_t>());
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
-    return LEON_OK;
-}
-
+// ---- the anchor dictionary in independently coded pieces (dict_pieces_code and the device calls: dict_kernels.hip) ----
 int leon_dna_dict_pieces(leon_dna_ctx* c, const uint64_t** piece_off, uint64_t* n_pieces, uint32_t* piece_anchors) {
     if (!c || !piece_off || !n_pieces || !piece_anchors) return LEON_E_INVALID;
     if (!(c->cfg.flags & LEON_F_DICT_PIECES)) return fail(c, LEON_E_STATE, "leon_dna_dict_pieces: the context was created without LEON_F_DICT_PIECES");
@@ -1699,66 +1631,17 @@ int leon_dna_dict_pieces(leon_dna_ctx* c, const uint64_t** piece_off, uint64_t* 
     return LEON_OK;
 }
 
-int leon_anchor_dict_encode_pieces_device(int device_id, const uint64_t* d_kmers, uint64_t n_anchors, uint32_t k, uint32_t piece_anchors, uint8_t* out,
-                                          uint64_t out_cap, uint64_t* piece_off, uint64_t* size) {
-    if (const char* why = dict_pieces_encode_refusal(d_kmers, n_anchors, k, piece_anchors, out, out_cap, piece_off, size)) return fail(nullptr, LEON_E_INVALID, why);
-    const uint32_t P = dict_piece_anchors(piece_anchors);
-    *size = 0; piece_off[0] = 0;
-    if (!n_anchors) return LEON_OK;                               // no piece: no device is asked
-    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_NO_DEVICE, "leon_anchor_dict_encode_pieces_device: no such HIP device"); }
-    // a stream of its own: the call runs beside calls on the contexts' streams
-    struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
-    HIPCHK(nullptr, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    TmpBuf d_dst;
-    if (int rc = dict_pieces_code(nullptr, st.s, d_kmers, n_anchors, k, P, piece_off, d_dst)) return rc;
-    *size = piece_off[dict_piece_count(n_anchors, P)];
-    if (*size > out_cap) return fail(nullptr, LEON_E_OVERFLOW, "anchor dictionary pieces: out_cap too small");
-    HIPCHK(nullptr, hipMemcpyAsync(out, d_dst.p, *size, hipMemcpyDeviceToHost, st.s));
-    HIPCHK(nullptr, hipStreamSynchronize(st.s));
-    return LEON_OK;
-}
-
-int leon_anchor_dict_decode_pieces_device(int device_id, const uint8_t* payload, const uint64_t* piece_off, uint64_t n_pieces, uint64_t n_anchors, uint32_t k,
-                                          uint32_t piece_anchors, uint64_t* out_kmers) {
-    if (const char* why = dict_pieces_decode_refusal(payload, piece_off, n_pieces, n_anchors, k, piece_anchors, out_kmers)) return fail(nullptr, LEON_E_INVALID, why);
-    if (!n_pieces) return LEON_OK;                                // no piece: no device is asked
-    const uint32_t P = dict_piece_anchors(piece_anchors), W = kmer_words(k);
-    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_NO_DEVICE, "leon_anchor_dict_decode_pieces_device: no such HIP device"); }
-    struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
-    HIPCHK(nullptr, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    hipStream_t s = st.s;
-    // the pieces' bytes alone travel: [piece_off[0], piece_off[n_pieces]), the offsets rebased to them
-    const uint64_t first = piece_off[0], bytes = piece_off[n_pieces] - first;
-    std::vector<uint64_t> rel(n_pieces + 1);
-    for (uint64_t p = 0; p <= n_pieces; p++) rel[p] = piece_off[p] - first;
-    TmpBuf d_pay, d_off, d_out, d_bad;
-    HIPCHK(nullptr, d_pay.ensure(bytes + 16)); HIPCHK(nullptr, d_off.ensure((n_pieces + 1) * 8));
-    HIPCHK(nullptr, d_out.ensure(n_anchors * W * 8)); HIPCHK(nullptr, d_bad.ensure(n_pieces * 4));
-    if (bytes && staged_h2d(device_id, d_pay.p, payload + first, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_HIP, "leon_anchor_dict_decode_pieces_device: the pieces' copy to the device failed"); }
-    HIPCHK(nullptr, hipMemcpyAsync(d_off.p, rel.data(), (n_pieces + 1) * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(nullptr, hipMemsetAsync(d_bad.p, 0, n_pieces * 4, s));
-    launch_dict_decode_pieces(s, d_pay.as<uint8_t>(), d_off.as<uint64_t>(), n_pieces, n_anchors, k, P, d_out.as<uint64_t>(), d_bad.as<uint32_t>());
-    HIPCHK(nullptr, hipGetLastError());
-    std::vector<uint32_t> bad(n_pieces);
-    HIPCHK(nullptr, hipMemcpyAsync(bad.data(), d_bad.p, n_pieces * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(nullptr, hipStreamSynchronize(s));
-    for (uint64_t p = 0; p < n_pieces; p++) if (bad[p]) return fail(nullptr, LEON_E_INVALID, dict_piece_refusal(p));
-    HIPCHK(nullptr, hipMemcpyAsync(out_kmers, d_out.p, n_anchors * W * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(nullptr, hipStreamSynchronize(s));
-    return LEON_OK;
-}
-
 int leon_host_anchor_dict_encode_pieces(const uint64_t* kmers, uint64_t n_anchors, uint32_t k, uint32_t piece_anchors, uint8_t* out, uint64_t out_cap,
                                         uint64_t* piece_off, uint64_t* size, uint32_t n_threads) {
     std::string why;
     const int rc = host_dict_encode_pieces(kmers, n_anchors, k, piece_anchors, out, out_cap, piece_off, size, n_threads, why);
-    return rc ? fail(nullptr, rc, why) : LEON_OK;
+    return rc ? dev_fail(rc, why) : LEON_OK;
 }
 int leon_host_anchor_dict_decode_pieces(const uint8_t* payload, const uint64_t* piece_off, uint64_t n_pieces, uint64_t n_anchors, uint32_t k,
                                         uint32_t piece_anchors, uint64_t* out_kmers, uint32_t n_threads) {
     std::string why;
     const int rc = host_dict_decode_pieces(payload, piece_off, n_pieces, n_anchors, k, piece_anchors, out_kmers, n_threads, why);
-    return rc ? fail(nullptr, rc, why) : LEON_OK;
+    return rc ? dev_fail(rc, why) : LEON_OK;
 }
 
 int leon_dna_finish(leon_dna_ctx* c, const uint8_t** payload, uint64_t* size, uint64_t* n_anchors) {
@@ -1774,9 +1657,10 @@ int leon_dna_finish(leon_dna_ctx* c, const uint8_t** payload, uint64_t* size, ui
                 const uint32_t P = dict_piece_anchors(c->cfg.dict_piece_anchors);
                 c->dict_piece_off.assign(dict_piece_count(c->n_anchors, P) + 1, 0);
                 TmpBuf d_dst;
-                if (int rc = dict_pieces_code(c, c->stream, c->anchor_kmers.as<uint64_t>(), c->n_anchors, c->cfg.kmer_size, P, c->dict_piece_off.data(), d_dst)) {
+                std::string why;
+                if (int rc = dict_pieces_code(c->stream, c->anchor_kmers.as<uint64_t>(), c->n_anchors, c->cfg.kmer_size, P, c->dict_piece_off.data(), d_dst, why)) {
                     c->dict_piece_off.clear();
-                    return rc;
+                    return fail(c, rc, why);
                 }
                 c->dict_device_out.resize(c->dict_piece_off.back());
                 if (!c->dict_device_out.empty()) HIPCHK(c, hipMemcpy(c->dict_device_out.data(), d_dst.p, c->dict_device_out.size(), hipMemcpyDeviceToHost));
@@ -1900,9 +1784,9 @@ int leon_dna_get_stats(const leon_dna_ctx* c, leon_dna_stats* out) {
 
 // ------------------------------------------------------------------------------------------------ decode
 int leon_host_anchor_dict_decode(const uint8_t* payload, uint64_t size, uint64_t n_anchors, uint32_t k, uint64_t* out) {
-    if ((!payload && size) || (!out && n_anchors)) return fail(nullptr, LEON_E_INVALID, "null argument");
-    if (k < 3 || k > 63) return fail(nullptr, LEON_E_INVALID, "kmer_size must be in 3..63");
-    if (!decode_anchor_dict(payload, size, n_anchors, k, out)) return fail(nullptr, LEON_E_INVALID, "anchor dictionary stream does not decode");
+    if ((!payload && size) || (!out && n_anchors)) return dev_fail(LEON_E_INVALID, "null argument");
+    if (k < 3 || k > 63) return dev_fail(LEON_E_INVALID, "kmer_size must be in 3..63");
+    if (!decode_anchor_dict(payload, size, n_anchors, k, out)) return dev_fail(LEON_E_INVALID, "anchor dictionary stream does not decode");
     return LEON_OK;
 }
 
@@ -2073,282 +1957,6 @@ int leon_dna_decode_blocks_device(leon_dna_ctx* c, const uint64_t* anchors, uint
     return decode_blocks_impl(c, anchors, n_anchors, payloads, payload_off, block_n_reads, block_n_bases, n_blocks, nullptr, out_cap, out_len, d_out_bases, d_out_len);
 }
 
-// ---- record text on the device (fmt_kernels.hip) ----
-int leon_records_format_device(int device_id, const leon_record_layout* lay, const uint8_t* d_bases, const uint32_t* d_len, uint64_t n_reads,
-                               uint64_t n_bases, const uint8_t* d_hdr_text, const uint64_t* d_hdr_off, const uint8_t* d_quals, uint8_t* d_text,
-                               uint64_t text_cap, uint64_t* d_rec_off, uint64_t* text_size) {
-    if (!lay || !text_size) return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: null argument");
-    *text_size = 0;
-    if (lay->struct_size != sizeof(leon_record_layout))
-        return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: unknown struct_size " + std::to_string(lay->struct_size) + " of leon_record_layout");
-    if (lay->plus_kind > 1) return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: plus_kind must be 0 (bare) or 1 (the header again)");
-    if (n_reads > (1ull << 40) || n_bases > (1ull << 46)) return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: implausible sizes");
-    if ((n_reads && !d_len) || (n_bases && !d_bases)) return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: null argument");
-    if (lay->fastq && !d_quals) return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: FASTQ records need the qualities (d_quals)");
-    if (lay->plus_kind == 1 && !d_hdr_text)
-        return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: '+' lines that repeat the header need the headers (d_hdr_text)");
-    if (d_hdr_text && !d_hdr_off) return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: headers without their offsets (d_hdr_off)");
-    if (!n_reads) return LEON_OK;
-    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_NO_DEVICE, "leon_records_format_device: no such HIP device"); }
-    // a stream of its own: the call runs beside decode calls on the contexts' streams
-    struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
-    HIPCHK(nullptr, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    hipStream_t s = st.s;
-    const uint64_t* hdr_off = d_hdr_text ? d_hdr_off : nullptr;
-    FmtLayout L{};
-    L.first_read_index = lay->first_read_index; L.hdr_bytes = lay->hdr_bytes; L.wrap = lay->wrap;
-    L.lead = lay->lead; L.fastq = lay->fastq ? 1 : 0; L.plus_kind = lay->fastq ? lay->plus_kind : 0;
-    TmpBuf d_in, d_off, d_flags, d_tmp;
-    HIPCHK(nullptr, d_in.ensure((n_reads + 1) * sizeof(FmtPair))); HIPCHK(nullptr, d_off.ensure((n_reads + 1) * sizeof(FmtPair)));
-    HIPCHK(nullptr, d_flags.ensure(64));
-    HIPCHK(nullptr, hipMemsetAsync(d_flags.p, 0, 64, s));
-    launch_fmt_sizes(s, L, d_len, hdr_off, n_reads, d_in.as<FmtPair>(), d_flags.as<uint32_t>());
-    HIPCHK(nullptr, hipGetLastError());
-    size_t tmp_bytes = 0;
-    HIPCHK(nullptr, fmt_scan(nullptr, tmp_bytes, d_in.as<FmtPair>(), d_off.as<FmtPair>(), n_reads, s));
-    HIPCHK(nullptr, d_tmp.ensure(std::max<size_t>(tmp_bytes, 16)));
-    HIPCHK(nullptr, fmt_scan(d_tmp.p, tmp_bytes, d_in.as<FmtPair>(), d_off.as<FmtPair>(), n_reads, s));
-    uint32_t flags[2] = {0, 0};
-    uint64_t totals[2] = {0, 0};
-    HIPCHK(nullptr, hipMemcpyAsync(flags, d_flags.p, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(nullptr, hipMemcpyAsync(totals, d_off.as<FmtPair>() + n_reads, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(nullptr, hipStreamSynchronize(s));
-    // what the arrays say against what the call was told, before anything is indexed with it
-    if (flags[0]) return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: the header offsets (d_hdr_off) run backwards");
-    if (flags[1]) return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: the header offsets (d_hdr_off) do not end at the " + std::to_string(lay->hdr_bytes) + " header bytes given");
-    if (totals[1] != n_bases)
-        return fail(nullptr, LEON_E_INVALID, "leon_records_format_device: the lengths (d_len) add up to " + std::to_string(totals[1]) + " bases, not the " + std::to_string(n_bases) + " given");
-    *text_size = totals[0];
-    if (totals[0] > text_cap || !d_text) return fail(nullptr, LEON_E_OVERFLOW, "leon_records_format_device: the text needs " + std::to_string(totals[0]) + " bytes");
-    launch_fmt_records(s, L, d_off.as<FmtPair>(), hdr_off, n_reads, d_bases, d_hdr_text, d_quals, d_text, totals[0]);
-    HIPCHK(nullptr, hipGetLastError());
-    if (d_rec_off) { launch_fmt_rec_off(s, d_off.as<FmtPair>(), n_reads, d_rec_off); HIPCHK(nullptr, hipGetLastError()); }
-    HIPCHK(nullptr, hipStreamSynchronize(s));
-    return LEON_OK;
-}
-
-// ---- quality blocks inflated on the device (inflate_kernels.hip) ----
-int leon_qual_inflate_blocks_device(int device_id, const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads,
-                                    const uint64_t* block_n_bytes, uint64_t n_blocks, const uint32_t* d_len, uint8_t* d_quals, uint64_t quals_cap,
-                                    uint64_t* d_qual_off, uint64_t* n_symbols) {
-    if (n_symbols) *n_symbols = 0;
-    if (n_blocks && (!payloads || !payload_off || !block_n_reads || !block_n_bytes || !d_quals)) return fail(nullptr, LEON_E_INVALID, "null argument");
-    if (!n_blocks) return LEON_OK;
-    if (n_blocks > (1ull << 31)) return fail(nullptr, LEON_E_INVALID, "implausible number of blocks");
-    std::vector<uint64_t> o0(n_blocks + 1, 0), r0(n_blocks + 1, 0);
-    for (uint64_t b = 0; b < n_blocks; b++) {
-        if (payload_off[b + 1] < payload_off[b]) return fail(nullptr, LEON_E_INVALID, "payload offsets are not monotonic");
-        o0[b + 1] = o0[b] + block_n_bytes[b];
-        r0[b + 1] = r0[b] + block_n_reads[b];
-        if (o0[b + 1] < o0[b] || o0[b + 1] > quals_cap) return fail(nullptr, LEON_E_INVALID, "output capacity below the sum of block_n_bytes");
-    }
-    const uint64_t total_reads = r0[n_blocks];
-    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_NO_DEVICE, "leon_qual_inflate_blocks_device: no such HIP device"); }
-    // a stream of its own: the call runs beside decode calls on the contexts' streams
-    struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
-    HIPCHK(nullptr, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    hipStream_t s = st.s;
-    // The blocks in launches of at most kMaxBlocks blocks and kMaxText bytes of temporary text (the lines WITH their newlines, every
-    // block's share 16-byte aligned): what bounds the temporaries; a launch holds at least one block.
-    constexpr uint64_t kMaxBlocks = 1024, kMaxText = 8ull << 30;
-    auto share = [&](uint64_t b) { return (block_n_bytes[b] + block_n_reads[b] + 15) & ~15ull; };
-    std::vector<uint64_t> cut{0};
-    uint64_t max_text = 0, max_pay = 0, max_tiles = 0, max_blocks = 0;
-    for (uint64_t b = 0; b < n_blocks;) {
-        uint64_t e = b, text = 0, tiles = 0;
-        while (e < n_blocks && (e == b || (e - b < kMaxBlocks && text + share(e) <= kMaxText))) {
-            text += share(e); tiles += (block_n_bytes[e] + block_n_reads[e] + 4095) / 4096; e++;
-        }
-        max_text = std::max(max_text, text); max_tiles = std::max(max_tiles, tiles); max_blocks = std::max(max_blocks, e - b);
-        max_pay = std::max(max_pay, payload_off[e] - payload_off[b]);
-        cut.push_back(e); b = e;
-    }
-    if (max_tiles >= (1ull << 31)) return fail(nullptr, LEON_E_INVALID, "implausible block sizes");
-    TmpBuf d_pay, d_text, d_blk, d_status, d_adler, d_tile_nl, d_nl_before, d_sums, d_last, d_tmp, d_cnt, d_off_own;
-    HIPCHK(nullptr, d_pay.ensure(max_pay + 64)); HIPCHK(nullptr, d_text.ensure(max_text + 64));
-    HIPCHK(nullptr, d_blk.ensure((max_blocks + 1) * sizeof(QiBlock)));
-    HIPCHK(nullptr, d_status.ensure(max_blocks * 4)); HIPCHK(nullptr, d_adler.ensure(max_blocks * 4)); HIPCHK(nullptr, d_last.ensure(max_blocks * 4));
-    HIPCHK(nullptr, d_sums.ensure(max_blocks * 16));
-    HIPCHK(nullptr, d_tile_nl.ensure((max_tiles + 1) * 4)); HIPCHK(nullptr, d_nl_before.ensure((max_tiles + 1) * 8));
-    HIPCHK(nullptr, d_cnt.ensure(16));
-    HIPCHK(nullptr, hipMemsetAsync(d_cnt.p, 0, 8, s));
-    HIPCHK(nullptr, hipMemsetAsync(d_cnt.as<uint8_t>() + 8, 0xFF, 8, s));
-    size_t tmp_bytes = 0;
-    HIPCHK(nullptr, qual_tiles_scan(nullptr, tmp_bytes, d_tile_nl.as<uint32_t>(), d_nl_before.as<uint64_t>(), max_tiles, s));
-    HIPCHK(nullptr, d_tmp.ensure(std::max<size_t>(tmp_bytes, 16)));
-    uint64_t* qual_off = d_qual_off;
-    if (!qual_off && d_len) { HIPCHK(nullptr, d_off_own.ensure((total_reads + 1) * 8)); qual_off = d_off_own.as<uint64_t>(); }   // the lengths are checked through the offsets
-    if (qual_off) HIPCHK(nullptr, hipMemsetAsync(qual_off, 0, 8, s));
-    std::vector<QiBlock> blk;
-    std::vector<uint32_t> status;
-    for (size_t g = 0; g + 1 < cut.size(); g++) {
-        const uint64_t b0 = cut[g], b1 = cut[g + 1], nb = b1 - b0, pay_bytes = payload_off[b1] - payload_off[b0];
-        blk.assign(nb + 1, QiBlock{});
-        uint64_t text = 0, tiles = 0;
-        for (uint64_t b = b0; b <= b1; b++) {
-            QiBlock& K = blk[b - b0];
-            K.text0 = text; K.tile0 = tiles;
-            if (b == b1) break;
-            K.pay0 = payload_off[b] - payload_off[b0]; K.pay_size = payload_off[b + 1] - payload_off[b];
-            K.text_size = block_n_bytes[b] + block_n_reads[b];
-            K.q0 = o0[b]; K.read0 = r0[b]; K.n_reads = block_n_reads[b];
-            text += share(b); tiles += (K.text_size + 4095) / 4096;
-        }
-        if (staged_h2d(device_id, d_pay.p, payloads + payload_off[b0], pay_bytes) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_HIP, "leon_qual_inflate_blocks_device: the payloads' copy to the device failed"); }
-        HIPCHK(nullptr, hipMemcpyAsync(d_blk.p, blk.data(), (nb + 1) * sizeof(QiBlock), hipMemcpyHostToDevice, s));
-        HIPCHK(nullptr, hipMemsetAsync(d_sums.p, 0, nb * 16, s));
-        HIPCHK(nullptr, hipMemsetAsync(d_last.p, 0, nb * 4, s));
-        HIPCHK(nullptr, hipMemsetAsync(d_tile_nl.as<uint32_t>() + tiles, 0, 4, s));
-        launch_qual_inflate(s, d_pay.as<uint32_t>(), (pay_bytes + 3) / 4, d_blk.as<QiBlock>(), (uint32_t)nb, d_text.as<uint8_t>(), d_status.as<uint32_t>(),
-                            d_adler.as<uint32_t>(), n_symbols ? d_cnt.as<unsigned long long>() : nullptr);
-        HIPCHK(nullptr, hipGetLastError());
-        launch_qual_tiles(s, d_blk.as<QiBlock>(), (uint32_t)nb, tiles, d_text.as<uint8_t>(), d_tile_nl.as<uint32_t>(), d_sums.as<unsigned long long>(), d_last.as<uint32_t>());
-        HIPCHK(nullptr, hipGetLastError());
-        HIPCHK(nullptr, qual_tiles_scan(d_tmp.p, tmp_bytes, d_tile_nl.as<uint32_t>(), d_nl_before.as<uint64_t>(), tiles, s));
-        launch_qual_check(s, d_blk.as<QiBlock>(), (uint32_t)nb, d_nl_before.as<uint64_t>(), d_sums.as<unsigned long long>(), d_last.as<uint32_t>(),
-                          d_adler.as<uint32_t>(), d_status.as<uint32_t>());
-        HIPCHK(nullptr, hipGetLastError());
-        // the blocks' status words in one small copy; the smallest failing block is the one the host way names
-        status.assign(nb, 0);
-        HIPCHK(nullptr, hipMemcpyAsync(status.data(), d_status.p, nb * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(nullptr, hipStreamSynchronize(s));
-        for (uint64_t b = 0; b < nb; b++)
-            if (status[b] != QI_OK) return fail(nullptr, LEON_E_INVALID, "quality block " + std::to_string(b0 + b) + " does not decode");
-        launch_qual_lines(s, d_blk.as<QiBlock>(), (uint32_t)nb, tiles, d_text.as<uint8_t>(), d_nl_before.as<uint64_t>(), d_quals, o0[n_blocks], qual_off, total_reads);
-        HIPCHK(nullptr, hipGetLastError());
-        HIPCHK(nullptr, hipStreamSynchronize(s));                 // the next launch reuses the temporaries (and the host's blk)
-    }
-    uint64_t words[2] = {0, ~0ull};
-    if (d_len) { launch_qual_lens(s, qual_off, d_len, 0, total_reads, d_cnt.as<unsigned long long>() + 1); HIPCHK(nullptr, hipGetLastError()); }
-    HIPCHK(nullptr, hipMemcpyAsync(words, d_cnt.p, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(nullptr, hipStreamSynchronize(s));
-    if (n_symbols) *n_symbols = words[0];
-    if (words[1] != ~0ull) {
-        const uint64_t b = (uint64_t)(std::upper_bound(r0.begin(), r0.end(), words[1]) - r0.begin()) - 1;
-        return fail(nullptr, LEON_E_INVALID, "read " + std::to_string(words[1]) + " (quality block " + std::to_string(b) + "): the quality line's length is not the one given (d_len)");
-    }
-    return LEON_OK;
-}
-
-// ---- zlib's CRC-32 of segments of a device buffer (crc_kernels.hip) ----
-extern "C++" { namespace leon {                                // (host_streams.cpp)
-const char* crc32_segments_refusal(const uint8_t* bytes, uint64_t n_bytes, const uint64_t* seg_off, uint64_t n_seg, const uint32_t* crc);
-} }
-int leon_crc32_segments_device(int device_id, const uint8_t* d_bytes, uint64_t n_bytes, const uint64_t* seg_off, uint64_t n_seg, uint32_t* crc) {
-    if (const char* why = crc32_segments_refusal(d_bytes, n_bytes, seg_off, n_seg, crc)) return fail(nullptr, LEON_E_INVALID, why);
-    if (!n_seg) return LEON_OK;
-    const uint64_t n_tiles = crc32_tile_count(d_bytes, seg_off[0], seg_off[n_seg]);
-    if (!n_tiles) { memset(crc, 0, n_seg * sizeof(uint32_t)); return LEON_OK; }      // nothing but empty segments: no device is asked
-    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_NO_DEVICE, "leon_crc32_segments_device: no such HIP device"); }
-    // a stream of its own: the call runs beside calls on the contexts' streams
-    struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
-    HIPCHK(nullptr, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    hipStream_t s = st.s;
-    TmpBuf d_off, d_acc;
-    HIPCHK(nullptr, d_off.ensure((n_seg + 1) * sizeof(uint64_t))); HIPCHK(nullptr, d_acc.ensure(n_seg * sizeof(uint32_t)));
-    HIPCHK(nullptr, hipMemcpyAsync(d_off.p, seg_off, (n_seg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    HIPCHK(nullptr, hipMemsetAsync(d_acc.p, 0, n_seg * sizeof(uint32_t), s));
-    launch_crc32_segments(s, d_bytes, d_off.as<uint64_t>(), n_seg, n_tiles, d_acc.as<uint32_t>());
-    HIPCHK(nullptr, hipGetLastError());
-    HIPCHK(nullptr, hipMemcpyAsync(crc, d_acc.p, n_seg * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(nullptr, hipStreamSynchronize(s));
-    return LEON_OK;
-}
-
-// ---- BGZF members inflated on the device (inflate_kernels.hip) ----
-int leon_bgzf_inflate_device(int device_id, const uint8_t* bytes, uint64_t n_bytes, const uint64_t* member_off, uint64_t n_members, uint8_t* d_text,
-                             uint64_t text_cap, uint64_t* n_text, uint32_t max_members_per_launch, uint64_t* n_symbols) {
-    if (n_symbols) *n_symbols = 0;
-    std::vector<BgzfMember> m;
-    {
-        std::string why;
-        if (const int rc = bgzf_prepare(bytes, n_bytes, member_off, n_members, d_text, text_cap, n_text, m, why)) return fail(nullptr, rc, why);
-    }
-    if (!n_members) return LEON_OK;
-    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_NO_DEVICE, "leon_bgzf_inflate_device: no such HIP device"); }
-    // a stream of its own: the call runs beside calls on the contexts' streams
-    struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
-    HIPCHK(nullptr, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    hipStream_t s = st.s;
-    // launches of at most `per` members: what bounds the temporaries (a member has at most 64 KiB of payload and of text)
-    const uint64_t per = max_members_per_launch ? max_members_per_launch : 4096;
-    auto share = [&](uint64_t i) { return ((uint64_t)m[i].isize + 15) & ~15ull; };
-    uint64_t max_pay = 0, max_tmp = 0, max_nb = 0;
-    for (uint64_t b0 = 0; b0 < n_members; b0 += per) {
-        const uint64_t b1 = std::min(n_members, b0 + per);
-        uint64_t tmp = 0;
-        for (uint64_t i = b0; i < b1; i++) tmp += share(i);
-        max_pay = std::max(max_pay, member_off[b1] - member_off[b0]); max_tmp = std::max(max_tmp, tmp); max_nb = std::max(max_nb, b1 - b0);
-    }
-    TmpBuf d_pay, d_tmp, d_blk, d_status, d_seg, d_acc, d_cnt;
-    HIPCHK(nullptr, d_pay.ensure(max_pay + 64)); HIPCHK(nullptr, d_tmp.ensure(max_tmp + 64));
-    HIPCHK(nullptr, d_blk.ensure((max_nb + 1) * sizeof(QiBlock)));
-    HIPCHK(nullptr, d_status.ensure(max_nb * 4)); HIPCHK(nullptr, d_seg.ensure((2 * max_nb + 1) * 8)); HIPCHK(nullptr, d_acc.ensure(2 * max_nb * 4));
-    HIPCHK(nullptr, d_cnt.ensure(8));
-    HIPCHK(nullptr, hipMemsetAsync(d_cnt.p, 0, 8, s));
-    std::vector<QiBlock> blk;
-    std::vector<uint64_t> seg;
-    std::vector<uint32_t> status, acc;
-    for (uint64_t b0 = 0; b0 < n_members; b0 += per) {
-        const uint64_t b1 = std::min(n_members, b0 + per), nb = b1 - b0, pay_bytes = member_off[b1] - member_off[b0];
-        blk.assign(nb + 1, QiBlock{}); seg.assign(2 * nb + 1, 0);
-        uint64_t tmp = 0, tiles = 0;
-        for (uint64_t i = b0; i <= b1; i++) {
-            QiBlock& K = blk[i - b0];
-            K.text0 = tmp; K.tile0 = tiles;
-            seg[2 * (i - b0)] = tmp;                              // the member's text, then the share's padding: two segments
-            if (i == b1) break;
-            if (m[i].ok) { K.pay0 = m[i].pay0 - member_off[b0]; K.pay_size = m[i].pay_size; K.text_size = m[i].isize; }   // (!ok: an empty stream, refused below)
-            K.q0 = m[i].text0;
-            seg[2 * (i - b0) + 1] = tmp + K.text_size;
-            tmp += share(i); tiles += (K.text_size + 4095) / 4096;
-        }
-        if (staged_h2d(device_id, d_pay.p, bytes + member_off[b0], pay_bytes) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_HIP, "leon_bgzf_inflate_device: the payloads' copy to the device failed"); }
-        HIPCHK(nullptr, hipMemcpyAsync(d_blk.p, blk.data(), (nb + 1) * sizeof(QiBlock), hipMemcpyHostToDevice, s));
-        HIPCHK(nullptr, hipMemcpyAsync(d_seg.p, seg.data(), (2 * nb + 1) * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(nullptr, hipMemsetAsync(d_acc.p, 0, 2 * nb * 4, s));
-        launch_bgzf_inflate(s, d_pay.as<uint32_t>(), (pay_bytes + 3) / 4, d_blk.as<QiBlock>(), (uint32_t)nb, d_tmp.as<uint8_t>(), d_status.as<uint32_t>(),
-                            n_symbols ? d_cnt.as<unsigned long long>() : nullptr);
-        HIPCHK(nullptr, hipGetLastError());
-        // the CRC-32 of every member's text where the wave left it, before anything goes to d_text
-        launch_crc32_segments(s, d_tmp.as<uint8_t>(), d_seg.as<uint64_t>(), 2 * nb, crc32_tile_count(d_tmp.as<uint8_t>(), 0, tmp), d_acc.as<uint32_t>());
-        HIPCHK(nullptr, hipGetLastError());
-        status.assign(nb, 0); acc.assign(2 * nb, 0);
-        HIPCHK(nullptr, hipMemcpyAsync(status.data(), d_status.p, nb * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(nullptr, hipMemcpyAsync(acc.data(), d_acc.p, 2 * nb * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(nullptr, hipStreamSynchronize(s));
-        for (uint64_t i = 0; i < nb; i++)
-            if (!m[b0 + i].ok || status[i] != QI_OK || acc[2 * i] != m[b0 + i].crc) return fail(nullptr, LEON_E_INVALID, bgzf_refusal(b0 + i, member_off[b0 + i]));
-        launch_bgzf_gather(s, d_blk.as<QiBlock>(), (uint32_t)nb, tiles, d_tmp.as<uint8_t>(), d_text, *n_text);
-        HIPCHK(nullptr, hipGetLastError());
-        HIPCHK(nullptr, hipStreamSynchronize(s));                 // the next launch reuses the temporaries (and the host's tables)
-    }
-    if (n_symbols) {
-        HIPCHK(nullptr, hipMemcpyAsync(n_symbols, d_cnt.p, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(nullptr, hipStreamSynchronize(s));
-    }
-    return LEON_OK;
-}
-
-int leon_host_pinned_alloc(int device_id, uint64_t bytes, void** ptr) {
-    if (!ptr) return fail(nullptr, LEON_E_INVALID, "leon_host_pinned_alloc: null argument");
-    *ptr = nullptr;
-    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_NO_DEVICE, "leon_host_pinned_alloc: no such HIP device"); }
-    if (hipHostMalloc(ptr, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); *ptr = nullptr; return fail(nullptr, LEON_E_HIP, "leon_host_pinned_alloc: " + std::to_string(bytes) + " bytes of pinned memory refused"); }
-    return LEON_OK;
-}
-void leon_host_pinned_free(void* ptr) { if (ptr) (void)hipHostFree(ptr); }
-
-int leon_device_download_pieces(int device_id, const void* d_src, uint64_t bytes, leon_piece_sink sink, void* user) {
-    if (!sink || (bytes && !d_src)) return fail(nullptr, LEON_E_INVALID, "leon_device_download_pieces: null argument");
-    if (!bytes) return LEON_OK;
-    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, LEON_E_NO_DEVICE, "leon_device_download_pieces: no such HIP device"); }
-    const int rc = staged_d2h_pieces(device_id, d_src, bytes, [&](uint64_t offset, const void* p, uint64_t size) { return sink(user, offset, p, size); });
-    if (rc == 2) return fail(nullptr, LEON_E_SINK, "leon_device_download_pieces: the sink returned non-zero");
-    if (rc) return fail(nullptr, LEON_E_HIP, "leon_device_download_pieces: copy to the host failed");
-    return LEON_OK;
-}
-
 // Header blocks: the symbols on the device (one wave per block, all blocks at once), the text on host threads
 extern "C++" { namespace leon {                                // (host_streams.cpp)
 int header_blocks_from_symbols(const uint8_t* syms, const uint64_t* sym_begin, const uint64_t* sym_count, const uint32_t* block_n_reads, uint64_t n_blocks,
@@ -2433,10 +2041,10 @@ int leon_header_decode_symbols(leon_dna_ctx* c, const uint8_t* payloads, const u
 int leon_header_text_from_symbols(const leon_header_symbols* H, uint64_t first_block, uint64_t n_blocks, const uint32_t* block_n_reads,
                                   const uint8_t* first_header, uint64_t first_header_len, uint8_t* out, uint64_t out_cap, uint64_t* out_off,
                                   uint64_t* out_size, uint32_t n_threads) {
-    if (!H || !out_size || (n_blocks && (!block_n_reads || !out_off)) || (!first_header && first_header_len)) return fail(nullptr, LEON_E_INVALID, "null argument");
+    if (!H || !out_size || (n_blocks && (!block_n_reads || !out_off)) || (!first_header && first_header_len)) return dev_fail(LEON_E_INVALID, "null argument");
     *out_size = 0;
-    if (first_block > H->count.size() || n_blocks > H->count.size() - first_block) return fail(nullptr, LEON_E_INVALID, "blocks beyond the symbol set");
-    if (H->overflowed) return fail(nullptr, LEON_E_STATE, "the set's symbols did not fit the device buffer: decode the payloads with leon_host_header_decode_blocks");
+    if (first_block > H->count.size() || n_blocks > H->count.size() - first_block) return dev_fail(LEON_E_INVALID, "blocks beyond the symbol set");
+    if (H->overflowed) return dev_fail(LEON_E_STATE, "the set's symbols did not fit the device buffer: decode the payloads with leon_host_header_decode_blocks");
     if (!n_blocks) return LEON_OK;
     return leon::header_blocks_from_symbols(H->syms.get(), H->begin.data() + first_block, H->count.data() + first_block, block_n_reads, n_blocks, first_header,
                                             first_header_len, out, out_cap, out_off, out_size, n_threads);
@@ -2530,33 +2138,33 @@ int leon_header_decode_text(leon_dna_ctx* c, const uint8_t* payloads, const uint
 // blocks [b0, b0 + nb) of the set into out / out_off, the offsets counted from `at` (the run's first byte in the caller's text)
 static int header_text_copy(const leon_header_text* T, uint64_t b0, uint64_t nb, uint8_t* out, uint64_t* out_off, uint64_t at) {
     const uint64_t t0 = T->text_begin[b0], size = T->text_begin[b0 + nb] - t0, r0 = T->read0[b0], nr = T->read0[b0 + nb] - r0;
-    if (hipSetDevice(T->device) != hipSuccess) return fail(nullptr, LEON_E_HIP, "hipSetDevice");
-    if (staged_d2h(T->device, out, T->text.as<uint8_t>() + t0, size) != hipSuccess) return fail(nullptr, LEON_E_HIP, "header text: copy to the host failed");
-    if (staged_d2h(T->device, out_off, T->off.as<uint64_t>() + r0, (nr + 1) * 8) != hipSuccess) return fail(nullptr, LEON_E_HIP, "header offsets: copy to the host failed");
+    if (hipSetDevice(T->device) != hipSuccess) return dev_fail(LEON_E_HIP, "hipSetDevice");
+    if (staged_d2h(T->device, out, T->text.as<uint8_t>() + t0, size) != hipSuccess) return dev_fail(LEON_E_HIP, "header text: copy to the host failed");
+    if (staged_d2h(T->device, out_off, T->off.as<uint64_t>() + r0, (nr + 1) * 8) != hipSuccess) return dev_fail(LEON_E_HIP, "header offsets: copy to the host failed");
     if (at != t0) for (uint64_t i = 0; i <= nr; i++) out_off[i] = out_off[i] - t0 + at;
     return LEON_OK;
 }
 static int header_text_run(const leon_header_text* T, uint64_t first_block, uint64_t n_blocks) {
-    if (first_block > T->status.size() || n_blocks > T->status.size() - first_block) return fail(nullptr, LEON_E_INVALID, "blocks beyond the text set");
+    if (first_block > T->status.size() || n_blocks > T->status.size() - first_block) return dev_fail(LEON_E_INVALID, "blocks beyond the text set");
     for (uint64_t b = first_block; b < first_block + n_blocks; b++)
-        if (T->status[b]) return fail(nullptr, LEON_E_STATE, "header block " + std::to_string(b) + " was not built on the device (reason " + std::to_string(T->status[b]) +
+        if (T->status[b]) return dev_fail(LEON_E_STATE, "header block " + std::to_string(b) + " was not built on the device (reason " + std::to_string(T->status[b]) +
                                       "): decode the payloads with leon_host_header_decode_blocks");
     return LEON_OK;
 }
 
 int leon_header_text_fetch(const leon_header_text* T, uint64_t first_block, uint64_t n_blocks, uint8_t* out, uint64_t out_cap, uint64_t* out_off, uint64_t* out_size) {
-    if (!T || !out_size || (n_blocks && !out_off)) return fail(nullptr, LEON_E_INVALID, "null argument");
+    if (!T || !out_size || (n_blocks && !out_off)) return dev_fail(LEON_E_INVALID, "null argument");
     *out_size = 0;
     if (int rc = header_text_run(T, first_block, n_blocks)) return rc;
     if (!n_blocks) return LEON_OK;
     const uint64_t size = T->text_begin[first_block + n_blocks] - T->text_begin[first_block];
     *out_size = size;
-    if (size > out_cap || !out) return fail(nullptr, LEON_E_OVERFLOW, "header output needs " + std::to_string(size) + " bytes");
+    if (size > out_cap || !out) return dev_fail(LEON_E_OVERFLOW, "header output needs " + std::to_string(size) + " bytes");
     return header_text_copy(T, first_block, n_blocks, out, out_off, 0);
 }
 
 int leon_header_text_device_ptr(const leon_header_text* T, uint64_t first_block, uint64_t n_blocks, const uint8_t** d_text, const uint64_t** d_off, uint64_t* size) {
-    if (!T || !d_text || !d_off || !size) return fail(nullptr, LEON_E_INVALID, "null argument");
+    if (!T || !d_text || !d_off || !size) return dev_fail(LEON_E_INVALID, "null argument");
     *d_text = nullptr; *d_off = nullptr; *size = 0;
     if (int rc = header_text_run(T, first_block, n_blocks)) return rc;
     if (!T->text.p) return LEON_OK;                              // a set of no blocks

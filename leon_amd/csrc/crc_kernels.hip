@@ -13,8 +13,14 @@
 //   k_crc32_final   a thread per segment: the initial value's term and the final XOR.
 // XOR atomics on integers: the words do not depend on the order of arrival; nothing waits for anything.
 #include "kernels.h"
+#include "device_call.h"
+
+#include <cstring>
 
 namespace leon {
+
+// host_streams.cpp: what both forms refuse, in the same words; nullptr = the segments are in order
+const char* crc32_segments_refusal(const uint8_t* bytes, uint64_t n_bytes, const uint64_t* seg_off, uint64_t n_seg, const uint32_t* crc);
 
 namespace {
 
@@ -180,3 +186,24 @@ void launch_crc32_segments(hipStream_t s, const uint8_t* bytes, const uint64_t* 
 }
 
 }  // namespace leon
+
+using namespace leon;
+
+extern "C" int leon_crc32_segments_device(int device_id, const uint8_t* d_bytes, uint64_t n_bytes, const uint64_t* seg_off, uint64_t n_seg, uint32_t* crc) {
+    if (const char* why = crc32_segments_refusal(d_bytes, n_bytes, seg_off, n_seg, crc)) return dev_fail(LEON_E_INVALID, why);
+    if (!n_seg) return LEON_OK;
+    const uint64_t n_tiles = crc32_tile_count(d_bytes, seg_off[0], seg_off[n_seg]);
+    if (!n_tiles) { memset(crc, 0, n_seg * sizeof(uint32_t)); return LEON_OK; }      // nothing but empty segments: no device is asked
+    CallStream st;
+    if (const int rc = dev_open("leon_crc32_segments_device", device_id, st)) return rc;
+    hipStream_t s = st.s;
+    TmpBuf d_off, d_acc;
+    DEVCHK(d_off.ensure((n_seg + 1) * sizeof(uint64_t))); DEVCHK(d_acc.ensure(n_seg * sizeof(uint32_t)));
+    DEVCHK(hipMemcpyAsync(d_off.p, seg_off, (n_seg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    DEVCHK(hipMemsetAsync(d_acc.p, 0, n_seg * sizeof(uint32_t), s));
+    launch_crc32_segments(s, d_bytes, d_off.as<uint64_t>(), n_seg, n_tiles, d_acc.as<uint32_t>());
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipMemcpyAsync(crc, d_acc.p, n_seg * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    DEVCHK(hipStreamSynchronize(s));
+    return LEON_OK;
+}

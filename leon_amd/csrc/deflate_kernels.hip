@@ -10,10 +10,10 @@
 //   closed on a byte boundary by an empty stored block (Z_SYNC_FLUSH's marker), so the chunks of a read block are concatenated
 //   bytes; the read block's stream = 78 01, its chunks, a final empty stored block, Adler-32 (combined on the host from the
 //   chunks' own).
-#include "../../include/leon_dna.h"
 #include "kernels.h"
 #include "prim.h"
 #include "staging.h"
+#include "device_call.h"
 
 #include <zlib.h>
 
@@ -26,7 +26,6 @@
 #include <vector>
 
 namespace leon {
-void set_create_error(const std::string& msg);
 // host_streams.cpp: what leon_text_bgzf_records_device and leon_host_bgzf_record_cuts both refuse, in the same words; nullptr = in order
 const char* bgzf_records_refusal(bool have_off, uint64_t n_records, uint64_t n_head, uint64_t n_body, int last);
 const char* bgzf_offsets_refusal(uint32_t flags);
@@ -578,18 +577,8 @@ __global__ void __launch_bounds__(BGZF_CUT_T) k_bgzf_cuts(const uint64_t* __rest
 // Device buffers kept from call to call (one set per process, taken under a lock): a call per batch of a file would otherwise
 // allocate and free ~1.5 GB each time, and memory this process has freed comes back from hipMalloc at the driver's wiping
 // rate (~43 GB/s), for this call and for whoever allocates next.  Large calls go through in slices, so the set stays small.
-struct Grow {
-    void* p = nullptr; size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        const size_t want = bytes + bytes / 4 + 256;
-        const hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    template <typename T> T* as() { return (T*)p; }
-};
+// (a quarter of slack, not DevBuf's eighth: it decides how often a file's batches reallocate)
+struct Grow : DevBuf { Grow() { slack = 4; } };
 // One set PER DEVICE (it was one for the process, dropped and rebuilt whenever the device changed: callers on several GPUs serialised
 // behind one mutex and thrashed 1.5 GB each way -- ADVICE r3).  A device's set is used by one call at a time.
 struct DeflateScratch {
@@ -597,15 +586,13 @@ struct DeflateScratch {
     int device = -1;
     Grow off, text, cb, cl, out, sizes, adler, cdst, fin;
     std::vector<uint8_t> h;
-    void drop() { for (Grow* g : {&off, &text, &cb, &cl, &out, &sizes, &adler, &cdst, &fin}) { if (g->p) (void)hipFree(g->p); g->p = nullptr; g->cap = 0; } }
+    void drop() { for (Grow* g : {&off, &text, &cb, &cl, &out, &sizes, &adler, &cdst, &fin}) g->release(); }
 };
 constexpr int DF_MAX_DEVICES = 64;
 DeflateScratch* scratch_table() { static DeflateScratch* t = new DeflateScratch[DF_MAX_DEVICES]; return t; }     // (never destroyed: the HIP runtime may be gone by then)
 DeflateScratch& scratch(int device_id) { return scratch_table()[device_id]; }
 
 constexpr uint64_t DF_SLICE_TEXT = 512ull << 20;                // text bytes per slice of a large call
-
-#define DCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_create_error(std::string(#call) + ": " + hipGetErrorString(e_)); return LEON_E_HIP; } } while (0)
 
 // blocks [b0, b1) of the call: reads [r0, r1), whose qualities start at d_quals + (offsets[r0] - offsets[0])
 int deflate_slice(DeflateScratch& S, int device_id, const uint8_t* d_quals, const uint64_t* offsets, uint64_t r0, uint64_t r1, uint32_t reads_per_block,
@@ -637,21 +624,21 @@ int deflate_slice(DeflateScratch& S, int device_id, const uint8_t* d_quals, cons
     const uint64_t n_chunks = chunk_begin.size();
     ms_tables = ms_since(t_start);
     const auto t_k = std::chrono::steady_clock::now();
-    DCHK(S.off.ensure((n_reads + 1) * 8)); DCHK(S.text.ensure(n_text + 64));
-    DCHK(staged_h2d(device_id, S.off.p, off, (n_reads + 1) * 8));
+    DEVCHK(S.off.ensure((n_reads + 1) * 8)); DEVCHK(S.text.ensure(n_text + 64));
+    DEVCHK(staged_h2d(device_id, S.off.p, off, (n_reads + 1) * 8));
     hipLaunchKernelGGL(k_qual_text, dim3((uint32_t)std::min<uint64_t>((n_reads + 3) / 4, 1u << 16)), dim3(256), 0, s, dq, S.off.as<uint64_t>(), n_reads, q0,
                        S.text.as<uint8_t>());
     std::vector<uint32_t> sizes(n_chunks), adl(n_chunks);
     if (n_chunks) {
-        DCHK(S.cb.ensure(n_chunks * 8)); DCHK(S.cl.ensure(n_chunks * 4)); DCHK(S.out.ensure(n_chunks * (uint64_t)DF_OUT_STRIDE));
-        DCHK(S.sizes.ensure(n_chunks * 4)); DCHK(S.adler.ensure(n_chunks * 4)); DCHK(S.cdst.ensure(n_chunks * 8));
-        DCHK(hipMemcpyAsync(S.cb.p, chunk_begin.data(), n_chunks * 8, hipMemcpyHostToDevice, s));
-        DCHK(hipMemcpyAsync(S.cl.p, chunk_len.data(), n_chunks * 4, hipMemcpyHostToDevice, s));
+        DEVCHK(S.cb.ensure(n_chunks * 8)); DEVCHK(S.cl.ensure(n_chunks * 4)); DEVCHK(S.out.ensure(n_chunks * (uint64_t)DF_OUT_STRIDE));
+        DEVCHK(S.sizes.ensure(n_chunks * 4)); DEVCHK(S.adler.ensure(n_chunks * 4)); DEVCHK(S.cdst.ensure(n_chunks * 8));
+        DEVCHK(hipMemcpyAsync(S.cb.p, chunk_begin.data(), n_chunks * 8, hipMemcpyHostToDevice, s));
+        DEVCHK(hipMemcpyAsync(S.cl.p, chunk_len.data(), n_chunks * 4, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_deflate_chunks, dim3((uint32_t)std::min<uint64_t>(n_chunks, 1u << 20)), dim3(DF_T), 0, s, S.text.as<uint8_t>(), S.cb.as<uint64_t>(),
                            S.cl.as<uint32_t>(), n_chunks, S.out.as<uint8_t>(), S.sizes.as<uint32_t>(), S.adler.as<uint32_t>());
-        DCHK(hipGetLastError());
-        DCHK(hipMemcpy(sizes.data(), S.sizes.p, n_chunks * 4, hipMemcpyDeviceToHost));
-        DCHK(hipMemcpy(adl.data(), S.adler.p, n_chunks * 4, hipMemcpyDeviceToHost));
+        DEVCHK(hipGetLastError());
+        DEVCHK(hipMemcpy(sizes.data(), S.sizes.p, n_chunks * 4, hipMemcpyDeviceToHost));
+        DEVCHK(hipMemcpy(adl.data(), S.adler.p, n_chunks * 4, hipMemcpyDeviceToHost));
     }
     // layout of the final streams: per block 2 bytes of zlib header, its chunks, 5 bytes of final stored block, 4 of Adler-32
     std::vector<uint64_t> blk_dst(n_blocks + 1, 0), chunk_dst(n_chunks);
@@ -664,15 +651,15 @@ int deflate_slice(DeflateScratch& S, int device_id, const uint8_t* d_quals, cons
     if (S.h.size() < total) S.h.resize(total + total / 4);
     uint8_t* h = S.h.data();
     if (n_chunks) {
-        DCHK(S.fin.ensure(total + 16));
-        DCHK(hipMemcpyAsync(S.cdst.p, chunk_dst.data(), n_chunks * 8, hipMemcpyHostToDevice, s));
+        DEVCHK(S.fin.ensure(total + 16));
+        DEVCHK(hipMemcpyAsync(S.cdst.p, chunk_dst.data(), n_chunks * 8, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_deflate_gather, dim3((uint32_t)std::min<uint64_t>(n_chunks, 1u << 20)), dim3(256), 0, s, S.out.as<uint8_t>(), S.sizes.as<uint32_t>(),
                            S.cdst.as<uint64_t>(), n_chunks, S.fin.as<uint8_t>());
-        DCHK(hipGetLastError());
-        DCHK(hipStreamSynchronize(s));
+        DEVCHK(hipGetLastError());
+        DEVCHK(hipStreamSynchronize(s));
         ms_kernels = ms_since(t_k);
         const auto t_d = std::chrono::steady_clock::now();
-        DCHK(staged_d2h(device_id, h, S.fin.p, total));
+        DEVCHK(staged_d2h(device_id, h, S.fin.p, total));
         ms_d2h = ms_since(t_d);
     }
     const auto t_sink = std::chrono::steady_clock::now();
@@ -685,7 +672,7 @@ int deflate_slice(DeflateScratch& S, int device_id, const uint8_t* d_quals, cons
         e[0] = 1; e[1] = 0; e[2] = 0; e[3] = 0xFF; e[4] = 0xFF;                  // BFINAL 1, stored, empty
         e[5] = (uint8_t)(ad >> 24); e[6] = (uint8_t)(ad >> 16); e[7] = (uint8_t)(ad >> 8); e[8] = (uint8_t)ad;
         const uint32_t nr = (uint32_t)std::min<uint64_t>(reads_per_block, n_reads - b * reads_per_block);
-        if (sink(user, first_block_id + b, p, blk_dst[b + 1] - blk_dst[b], nr)) { set_create_error("qual_deflate: block sink returned non-zero"); return LEON_E_SINK; }
+        if (sink(user, first_block_id + b, p, blk_dst[b + 1] - blk_dst[b], nr)) return dev_fail(LEON_E_SINK, "qual_deflate: block sink returned non-zero");
     }
     if (trace) fprintf(stderr, "[leon deflate] %llu blocks, %.1f MB of text -> %.1f MB: tables %.1f ms, offsets + kernels %.1f, D2H %.1f, sink %.1f\n",
                        (unsigned long long)n_blocks, n_text / 1e6, total / 1e6, ms_tables, ms_kernels, ms_d2h, ms_since(t_sink));
@@ -698,11 +685,10 @@ struct BgzfScratch {
     int device = -1;
     Grow begin, len, out, sizes, adler, crc, msize, moff, tmp, framed, idx, state;
     std::vector<uint64_t> h_idx;
-    void drop() { for (Grow* g : {&begin, &len, &out, &sizes, &adler, &crc, &msize, &moff, &tmp, &framed, &idx, &state}) { if (g->p) (void)hipFree(g->p); g->p = nullptr; g->cap = 0; } }
+    void drop() { for (Grow* g : {&begin, &len, &out, &sizes, &adler, &crc, &msize, &moff, &tmp, &framed, &idx, &state}) g->release(); }
 };
 // the member tables of a call (host memory), filled slice by slice; out == NULL: none asked for
 struct BgzfIndex { uint64_t* out = nullptr; uint64_t* text = nullptr; uint64_t at = 0; };
-struct BgzfStream { hipStream_t s = nullptr; ~BgzfStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } };
 BgzfScratch* bgzf_table() { static BgzfScratch* t = new BgzfScratch[DF_MAX_DEVICES]; return t; }
 constexpr uint64_t BGZF_SLICE_TEXT = 512ull << 20;
 
@@ -718,43 +704,43 @@ uint64_t bgzf_slice_text() {
 // ix (may be NULL): the call's member tables, which receive base + the members' offsets and text_base + begin[c].
 int bgzf_members_out(BgzfScratch& S, int device_id, hipStream_t s, const uint8_t* d_text, uint64_t n, uint64_t lo, uint64_t hi, uint64_t base, uint64_t text_base,
                      leon_piece_sink sink, void* user, BgzfIndex* ix, const std::string& who, uint64_t* out_size) {
-    DCHK(S.sizes.ensure(n * 4)); DCHK(S.adler.ensure(n * 4)); DCHK(S.crc.ensure(n * 4));
-    DCHK(S.msize.ensure((n + 1) * 8)); DCHK(S.moff.ensure((n + 1) * 8));
-    DCHK(S.out.ensure(n * (uint64_t)DF_OUT_STRIDE)); DCHK(S.framed.ensure(n * (uint64_t)BGZF_MEMBER_MAX));
+    DEVCHK(S.sizes.ensure(n * 4)); DEVCHK(S.adler.ensure(n * 4)); DEVCHK(S.crc.ensure(n * 4));
+    DEVCHK(S.msize.ensure((n + 1) * 8)); DEVCHK(S.moff.ensure((n + 1) * 8));
+    DEVCHK(S.out.ensure(n * (uint64_t)DF_OUT_STRIDE)); DEVCHK(S.framed.ensure(n * (uint64_t)BGZF_MEMBER_MAX));
     size_t tmp_bytes = 0;
-    DCHK(prim::ExclusiveSum(nullptr, tmp_bytes, S.msize.as<uint64_t>(), S.moff.as<uint64_t>(), n + 1, s));
-    DCHK(S.tmp.ensure(tmp_bytes));
+    DEVCHK(prim::ExclusiveSum(nullptr, tmp_bytes, S.msize.as<uint64_t>(), S.moff.as<uint64_t>(), n + 1, s));
+    DEVCHK(S.tmp.ensure(tmp_bytes));
     const uint32_t tgrid = (uint32_t)((n + 1 + 255) / 256);
     hipLaunchKernelGGL(k_deflate_chunks, dim3((uint32_t)std::min<uint64_t>(n, 1u << 20)), dim3(DF_T), 0, s, d_text, S.begin.as<uint64_t>(), S.len.as<uint32_t>(), n,
                        S.out.as<uint8_t>(), S.sizes.as<uint32_t>(), S.adler.as<uint32_t>());
-    DCHK(hipGetLastError());
-    DCHK(hipMemsetAsync(S.crc.p, 0, n * 4, s));
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipMemsetAsync(S.crc.p, 0, n * 4, s));
     launch_crc32_segments(s, d_text, S.begin.as<uint64_t>(), n, crc32_tile_count(d_text, lo, hi), S.crc.as<uint32_t>());
-    DCHK(hipGetLastError());
+    DEVCHK(hipGetLastError());
     hipLaunchKernelGGL(k_bgzf_sizes, dim3(tgrid), dim3(256), 0, s, S.sizes.as<uint32_t>(), n, S.msize.as<uint64_t>());
-    DCHK(prim::ExclusiveSum(S.tmp.p, tmp_bytes, S.msize.as<uint64_t>(), S.moff.as<uint64_t>(), n + 1, s));
+    DEVCHK(prim::ExclusiveSum(S.tmp.p, tmp_bytes, S.msize.as<uint64_t>(), S.moff.as<uint64_t>(), n + 1, s));
     hipLaunchKernelGGL(k_bgzf_members, dim3((uint32_t)std::min<uint64_t>(n, BGZF_MAX_GROUPS)), dim3(256), 0, s, S.out.as<uint8_t>(), S.sizes.as<uint32_t>(), S.len.as<uint32_t>(),
                        S.crc.as<uint32_t>(), S.moff.as<uint64_t>(), n, S.framed.as<uint8_t>());
-    DCHK(hipGetLastError());
+    DEVCHK(hipGetLastError());
     uint64_t total = 0;
     if (ix && ix->out) {                                          // the members' places come with the total, in the one small copy
-        DCHK(S.idx.ensure((2 * n + 1) * 8));
+        DEVCHK(S.idx.ensure((2 * n + 1) * 8));
         S.h_idx.resize(2 * n + 1);
         hipLaunchKernelGGL(k_bgzf_index, dim3(tgrid), dim3(256), 0, s, S.moff.as<uint64_t>(), S.begin.as<uint64_t>(), n, base, text_base, S.idx.as<uint64_t>());
-        DCHK(hipGetLastError());
-        DCHK(hipMemcpyAsync(S.h_idx.data(), S.idx.p, (2 * n + 1) * 8, hipMemcpyDeviceToHost, s));
-        DCHK(hipStreamSynchronize(s));
+        DEVCHK(hipGetLastError());
+        DEVCHK(hipMemcpyAsync(S.h_idx.data(), S.idx.p, (2 * n + 1) * 8, hipMemcpyDeviceToHost, s));
+        DEVCHK(hipStreamSynchronize(s));
         total = S.h_idx[2 * n];
         for (uint64_t c = 0; c < n; c++) { ix->out[ix->at + c] = S.h_idx[2 * c]; ix->text[ix->at + c] = S.h_idx[2 * c + 1]; }
         ix->at += n;
     } else {
-        DCHK(hipMemcpyAsync(&total, S.moff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
-        DCHK(hipStreamSynchronize(s));
+        DEVCHK(hipMemcpyAsync(&total, S.moff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
+        DEVCHK(hipStreamSynchronize(s));
     }
-    if (total > n * (uint64_t)BGZF_MEMBER_MAX || total < n * (uint64_t)BGZF_FRAME) { set_create_error(who + ": the members' sizes do not add up"); return LEON_E_OVERFLOW; }
+    if (total > n * (uint64_t)BGZF_MEMBER_MAX || total < n * (uint64_t)BGZF_FRAME) return dev_fail(LEON_E_OVERFLOW, who + ": the members' sizes do not add up");
     const int rc = staged_d2h_pieces(device_id, S.framed.p, total, [&](uint64_t offset, const void* p, uint64_t size) { return sink(user, base + offset, p, size); });
-    if (rc == 2) { set_create_error(who + ": the sink returned non-zero"); return LEON_E_SINK; }
-    if (rc) { set_create_error(who + ": copy to the host failed"); return LEON_E_HIP; }
+    if (rc == 2) return dev_fail(LEON_E_SINK, who + ": the sink returned non-zero");
+    if (rc) return dev_fail(LEON_E_HIP, who + ": copy to the host failed");
     *out_size = total;
     return LEON_OK;
 }
@@ -763,7 +749,7 @@ int bgzf_members_out(BgzfScratch& S, int device_id, hipStream_t s, const uint8_t
 int bgzf_slice(BgzfScratch& S, int device_id, hipStream_t s, const uint8_t* d_text, uint64_t n_text, uint64_t base, uint64_t text_base, leon_piece_sink sink, void* user,
                BgzfIndex* ix, const std::string& who, uint64_t* out_size) {
     const uint64_t n = (n_text + DF_CHUNK - 1) / DF_CHUNK;
-    DCHK(S.begin.ensure((n + 1) * 8)); DCHK(S.len.ensure(n * 4));
+    DEVCHK(S.begin.ensure((n + 1) * 8)); DEVCHK(S.len.ensure(n * 4));
     hipLaunchKernelGGL(k_bgzf_table, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, s, n_text, n, S.begin.as<uint64_t>(), S.len.as<uint32_t>());
     return bgzf_members_out(S, device_id, s, d_text, n, 0, n_text, base, text_base, sink, user, ix, who, out_size);
 }
@@ -771,15 +757,14 @@ int bgzf_slice(BgzfScratch& S, int device_id, hipStream_t s, const uint8_t* d_te
 // the fixed cuts of leon_text_bgzf_device and of leon_text_bgzf_records_device without records: `taken` bytes of d_text in slices
 int bgzf_fixed(int device_id, const uint8_t* d_text, uint64_t taken, leon_piece_sink sink, void* user, BgzfIndex* ix, const std::string& who, uint64_t* at, uint64_t* members) {
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) { (void)hipGetLastError(); set_create_error(who + ": no such HIP device"); return LEON_E_NO_DEVICE; }
-    if (device_id >= DF_MAX_DEVICES) { set_create_error(who + ": device ordinal beyond the scratch table"); return LEON_E_INVALID; }
-    DCHK(hipSetDevice(device_id));
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) { (void)hipGetLastError(); return dev_fail(LEON_E_NO_DEVICE, who + ": no such HIP device"); }
+    if (device_id >= DF_MAX_DEVICES) return dev_fail(LEON_E_INVALID, who + ": device ordinal beyond the scratch table");
+    DEVCHK(hipSetDevice(device_id));
     BgzfScratch& S = bgzf_table()[device_id];
     std::lock_guard<std::mutex> lock(S.mu);
     S.device = device_id;
-    // a stream of its own: the call runs beside calls on the contexts' streams
-    BgzfStream st;
-    DCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    CallStream st;
+    if (const int rc = dev_stream(st)) return rc;
     const uint64_t slice = bgzf_slice_text();
     for (uint64_t a = 0; a < taken; a += slice) {                 // sequential: a slice's base is the sum of the sizes before it
         const uint64_t m = std::min(slice, taken - a);
@@ -798,14 +783,14 @@ using namespace leon;
 
 extern "C" int leon_qual_deflate_blocks_device(int device_id, const uint8_t* d_quals, const uint64_t* offsets, uint64_t n_reads,
                                                uint32_t reads_per_block, leon_block_sink sink, void* user, uint64_t first_block_id) {
-    if ((n_reads && (!d_quals || !offsets)) || !sink || !reads_per_block) { set_create_error("qual_deflate: null argument"); return LEON_E_INVALID; }
+    if ((n_reads && (!d_quals || !offsets)) || !sink || !reads_per_block) return dev_fail(LEON_E_INVALID, "qual_deflate: null argument");
     if (!n_reads) return LEON_OK;
     for (uint64_t i = 0; i < n_reads; i++)
-        if (offsets[i + 1] < offsets[i]) { set_create_error("qual_deflate: offsets are not monotonic"); return LEON_E_INVALID; }
+        if (offsets[i + 1] < offsets[i]) return dev_fail(LEON_E_INVALID, "qual_deflate: offsets are not monotonic");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) { set_create_error("qual_deflate: no such HIP device"); return LEON_E_NO_DEVICE; }
-    if (device_id >= DF_MAX_DEVICES) { set_create_error("qual_deflate: device ordinal beyond the scratch table"); return LEON_E_INVALID; }
-    DCHK(hipSetDevice(device_id));
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) return dev_fail(LEON_E_NO_DEVICE, "qual_deflate: no such HIP device");
+    if (device_id >= DF_MAX_DEVICES) return dev_fail(LEON_E_INVALID, "qual_deflate: device ordinal beyond the scratch table");
+    DEVCHK(hipSetDevice(device_id));
     DeflateScratch& S = scratch(device_id);
     std::lock_guard<std::mutex> lock(S.mu);
     S.device = device_id;
@@ -825,7 +810,7 @@ extern "C" int leon_qual_deflate_blocks_device(int device_id, const uint8_t* d_q
 /* any text in device memory as BGZF: the whole members of it, or with `last` all of it and the EOF marker */
 extern "C" int leon_text_bgzf_device(int device_id, const uint8_t* d_text, uint64_t n_text, int last, leon_piece_sink sink, void* user,
                                      uint64_t* n_taken, uint64_t* out_bytes, uint64_t* n_members) {
-    auto refuse = [](const char* why) { set_create_error(std::string("leon_text_bgzf_device: ") + why); return (int)LEON_E_INVALID; };
+    auto refuse = [](const char* why) { return dev_fail(LEON_E_INVALID, std::string("leon_text_bgzf_device: ") + why); };
     if (!d_text && n_text) return refuse("d_text is NULL with n_text != 0");
     if (!sink) return refuse("sink is NULL");
     if (!n_taken) return refuse("n_taken is NULL");
@@ -840,7 +825,7 @@ extern "C" int leon_text_bgzf_device(int device_id, const uint8_t* d_text, uint6
         if (rc) return rc;
     }
     if (last) {
-        if (sink(user, at, kBgzfEof, sizeof kBgzfEof)) { set_create_error("leon_text_bgzf_device: the sink returned non-zero"); return LEON_E_SINK; }
+        if (sink(user, at, kBgzfEof, sizeof kBgzfEof)) return dev_fail(LEON_E_SINK, "leon_text_bgzf_device: the sink returned non-zero");
         at += sizeof kBgzfEof;
     }
     *out_bytes = at;
@@ -853,7 +838,7 @@ extern "C" int leon_text_bgzf_records_device(int device_id, const uint8_t* d_tex
                                              leon_piece_sink sink, void* user, uint64_t* n_taken, uint64_t* out_bytes, uint64_t* member_out_off,
                                              uint64_t* member_text_off, uint64_t members_cap, uint64_t* n_members) {
     const std::string who = "leon_text_bgzf_records_device";
-    auto fail = [&](int code, const std::string& why) { set_create_error(who + ": " + why); return code; };
+    auto fail = [&](int code, const std::string& why) { return dev_fail(code, who + ": " + why); };
     constexpr uint64_t W = DF_CHUNK;
     if (!d_text && (n_head || n_body)) return fail(LEON_E_INVALID, "d_text is NULL with text given");
     if (!sink) return fail(LEON_E_INVALID, "sink is NULL");
@@ -880,31 +865,31 @@ extern "C" int leon_text_bgzf_records_device(int device_id, const uint8_t* d_tex
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) { (void)hipGetLastError(); return fail(LEON_E_NO_DEVICE, "no such HIP device"); }
         if (device_id >= DF_MAX_DEVICES) return fail(LEON_E_INVALID, "device ordinal beyond the scratch table");
-        DCHK(hipSetDevice(device_id));
+        DEVCHK(hipSetDevice(device_id));
         BgzfScratch& S = bgzf_table()[device_id];
         std::lock_guard<std::mutex> lock(S.mu);
         S.device = device_id;
-        BgzfStream st;
-        DCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+        CallStream st;
+        if (const int rc = dev_stream(st)) return rc;
         hipStream_t s = st.s;
-        DCHK(S.state.ensure(8 * 8));
+        DEVCHK(S.state.ensure(8 * 8));
         uint64_t h_state[5] = {0, 0, 0, 0, 0};
         if (d_rec_off) {                                          // the offsets are checked before anything is indexed with them
             uint32_t flags[3] = {0, 0, 0};
-            DCHK(hipMemsetAsync(S.state.p, 0, sizeof flags, s));
+            DEVCHK(hipMemsetAsync(S.state.p, 0, sizeof flags, s));
             hipLaunchKernelGGL(k_bgzf_check_recs, dim3((uint32_t)((n_records + 1 + 255) / 256)), dim3(256), 0, s, d_rec_off, n_records, n_body, S.state.as<uint32_t>());
-            DCHK(hipGetLastError());
-            DCHK(hipMemcpyAsync(flags, S.state.p, sizeof flags, hipMemcpyDeviceToHost, s));
-            DCHK(hipStreamSynchronize(s));
+            DEVCHK(hipGetLastError());
+            DEVCHK(hipMemcpyAsync(flags, S.state.p, sizeof flags, hipMemcpyDeviceToHost, s));
+            DEVCHK(hipStreamSynchronize(s));
             if (const char* why = bgzf_offsets_refusal((flags[0] ? 1u : 0u) | (flags[1] ? 2u : 0u) | (flags[2] ? 4u : 0u))) return fail(LEON_E_INVALID, why);
         }
         const uint64_t n_starts = (n_head ? 1 : 0) + n_records + 1, bound = 3 * (n_text / W) + 2;
         auto cuts = [&](uint64_t k, uint64_t skip, uint64_t budget_end, uint64_t cap, uint64_t* begin, uint32_t* len) -> int {
             hipLaunchKernelGGL(k_bgzf_cuts, dim3(1), dim3(BGZF_CUT_T), 0, s, d_rec_off, n_starts, n_head, k, skip, budget_end, n_text, (uint32_t)last, cap, begin, len,
                                S.state.as<uint64_t>());
-            DCHK(hipGetLastError());
-            DCHK(hipMemcpyAsync(h_state, S.state.p, sizeof h_state, hipMemcpyDeviceToHost, s));
-            DCHK(hipStreamSynchronize(s));
+            DEVCHK(hipGetLastError());
+            DEVCHK(hipMemcpyAsync(h_state, S.state.p, sizeof h_state, hipMemcpyDeviceToHost, s));
+            DEVCHK(hipStreamSynchronize(s));
             return LEON_OK;
         };
         if (ix.out && members_cap < bound) {                      // a table that may be too small: found out before a byte is delivered, by one counting walk
@@ -915,7 +900,7 @@ extern "C" int leon_text_bgzf_records_device(int device_id, const uint8_t* d_tex
         uint64_t k = 0, skip = 0;
         for (;;) {                                                // sequential: a slice ends at a cut, the next one begins there
             const uint64_t cap = 3 * (std::min(slice, n_text - taken) / W) + 4;
-            DCHK(S.begin.ensure((cap + 1) * 8)); DCHK(S.len.ensure(cap * 4));
+            DEVCHK(S.begin.ensure((cap + 1) * 8)); DEVCHK(S.len.ensure(cap * 4));
             if (const int rc = cuts(k, skip, taken + slice, cap, S.begin.as<uint64_t>(), S.len.as<uint32_t>())) return rc;
             const uint64_t n = h_state[0], end = h_state[3];
             if (n > cap || end < taken + n || end > n_text || h_state[1] >= n_starts || members + n > bound || (ix.out && members + n > members_cap))

@@ -8,6 +8,13 @@
 // Totals stay below 5 + 63 * 2^20 < 2^26 (P <= 2^20), far below RC_MAX_TOTAL: no exact-division path.
 #include "kernels.h"
 #include "rc_model.h"
+#include "prim.h"
+#include "staging.h"
+#include "host_dict_pieces.h"
+#include "device_call.h"
+
+#include <algorithm>
+#include <vector>
 
 namespace leon {
 namespace {
@@ -179,8 +186,8 @@ inline uint32_t dp_groups(uint64_t n_pieces) {
     return (uint32_t)(waves < DICT_PIECES_MAX_GROUPS ? waves : DICT_PIECES_MAX_GROUPS);
 }
 
-}  // namespace
-
+// piece p = anchors [p * P, min((p + 1) * P, n_anchors)) of kmers, coded into scratch[p * stride .. + stride) (stride >= 64), sizes[p] its
+// bytes; *err (zeroed by the caller) is set when a piece came within 4 bytes of its stride: code again with a wider one
 void launch_dict_encode_pieces(hipStream_t s, const uint64_t* kmers, uint64_t n_anchors, uint32_t k, uint32_t P, uint64_t n_pieces, uint8_t* scratch,
                                uint64_t stride, uint64_t* sizes, int* err) {
     if (!n_pieces || stride < 64) return;
@@ -188,12 +195,14 @@ void launch_dict_encode_pieces(hipStream_t s, const uint64_t* kmers, uint64_t n_
     else hipLaunchKernelGGL(k_dict_encode_pieces<1>, dim3(dp_groups(n_pieces)), dim3(64), 0, s, kmers, n_anchors, k, P, n_pieces, scratch, stride, sizes, err);
 }
 
+// the slots back to back: off[n_pieces + 1] = the exclusive sums of sizes
 void launch_dict_gather_pieces(hipStream_t s, const uint8_t* scratch, uint64_t stride, const uint64_t* off, uint64_t n_pieces, uint8_t* dst) {
     if (!n_pieces) return;
     const uint32_t gy = n_pieces > 65535 ? 65535u : (uint32_t)n_pieces;
     hipLaunchKernelGGL(k_dict_gather_pieces, dim3(4, gy), dim3(256), 0, s, scratch, stride, off, n_pieces, dst);
 }
 
+// piece p = payload[off[p] .. off[p + 1]) -> its anchors' k-mer words in out; bad[p] (zeroed by the caller) is set for a piece that does not decode
 void launch_dict_decode_pieces(hipStream_t s, const uint8_t* payload, const uint64_t* off, uint64_t n_pieces, uint64_t n_anchors, uint32_t k, uint32_t P,
                                uint64_t* out, uint32_t* bad) {
     if (!n_pieces) return;
@@ -201,4 +210,95 @@ void launch_dict_decode_pieces(hipStream_t s, const uint8_t* payload, const uint
     else hipLaunchKernelGGL(k_dict_decode_pieces<1>, dim3(dp_groups(n_pieces)), dim3(64), 0, s, payload, off, n_pieces, n_anchors, k, P, out, bad);
 }
 
+}  // namespace
+
+// The pieces of d_kmers coded on stream s: piece_off (host, n_pieces + 1 entries) and the stream's bytes, back to back, in d_dst.
+// A piece's slot is first P * k / 2 + 64 bytes, twice what a genomic dictionary needs (2 bits a base); a list that does not fit --
+// nothing but adversarial k-mers -- is coded again with 8 bytes per symbol, the most a step can shift out (k_dict_encode_pieces).
+// LEON_OK, or the code with `why`: leon_dna_finish (capi.hip) keeps it with its context, the stateless call below with the thread.
+int dict_pieces_code(hipStream_t s, const uint64_t* d_kmers, uint64_t n_anchors, uint32_t k, uint32_t P, uint64_t* piece_off, TmpBuf& d_dst, std::string& why) {
+#define PIECES_CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { why = hip_failure(#call, e_); return LEON_E_HIP; } } while (0)
+    const uint64_t n_pieces = dict_piece_count(n_anchors, P);
+    piece_off[0] = 0;
+    if (!n_pieces) return LEON_OK;
+    const uint64_t piece_syms = (uint64_t)std::min<uint64_t>(P, n_anchors) * k;
+    TmpBuf d_scratch, d_sizes, d_off, d_err, d_tmp;
+    PIECES_CHK(d_sizes.ensure((n_pieces + 1) * 8)); PIECES_CHK(d_off.ensure((n_pieces + 1) * 8)); PIECES_CHK(d_err.ensure(4));
+    PIECES_CHK(hipMemsetAsync((uint64_t*)d_sizes.p + n_pieces, 0, 8, s));
+    uint64_t stride = 0;
+    for (int wide = 0;; wide++) {
+        stride = ((wide ? 8 * piece_syms + 12 : piece_syms / 2 + 64) + 7) & ~7ull;
+        PIECES_CHK(d_scratch.ensure(n_pieces * stride));
+        PIECES_CHK(hipMemsetAsync(d_err.p, 0, 4, s));
+        launch_dict_encode_pieces(s, d_kmers, n_anchors, k, P, n_pieces, d_scratch.as<uint8_t>(), stride, d_sizes.as<uint64_t>(), d_err.as<int>());
+        PIECES_CHK(hipGetLastError());
+        int err = 0;
+        PIECES_CHK(hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, s));
+        PIECES_CHK(hipStreamSynchronize(s));
+        if (!err) break;
+        if (wide) { why = "anchor dictionary pieces: a piece outgrew 8 bytes per symbol (internal error)"; return LEON_E_OVERFLOW; }
+    }
+    size_t tmp_bytes = 0;
+    PIECES_CHK(prim::ExclusiveSum(nullptr, tmp_bytes, d_sizes.as<uint64_t>(), d_off.as<uint64_t>(), n_pieces + 1, s));
+    PIECES_CHK(d_tmp.ensure(tmp_bytes + 16));
+    PIECES_CHK(prim::ExclusiveSum(d_tmp.p, tmp_bytes, d_sizes.as<uint64_t>(), d_off.as<uint64_t>(), n_pieces + 1, s));
+    PIECES_CHK(hipMemcpyAsync(piece_off, d_off.p, (n_pieces + 1) * 8, hipMemcpyDeviceToHost, s));
+    PIECES_CHK(hipStreamSynchronize(s));
+    PIECES_CHK(d_dst.ensure(piece_off[n_pieces] + 16));
+    launch_dict_gather_pieces(s, d_scratch.as<uint8_t>(), stride, d_off.as<uint64_t>(), n_pieces, d_dst.as<uint8_t>());
+    PIECES_CHK(hipGetLastError());
+    PIECES_CHK(hipStreamSynchronize(s));
+    return LEON_OK;
+#undef PIECES_CHK
+}
+
 }  // namespace leon
+
+using namespace leon;
+
+extern "C" int leon_anchor_dict_encode_pieces_device(int device_id, const uint64_t* d_kmers, uint64_t n_anchors, uint32_t k, uint32_t piece_anchors, uint8_t* out,
+                                          uint64_t out_cap, uint64_t* piece_off, uint64_t* size) {
+    if (const char* why = dict_pieces_encode_refusal(d_kmers, n_anchors, k, piece_anchors, out, out_cap, piece_off, size)) return dev_fail(LEON_E_INVALID, why);
+    const uint32_t P = dict_piece_anchors(piece_anchors);
+    *size = 0; piece_off[0] = 0;
+    if (!n_anchors) return LEON_OK;                               // no piece: no device is asked
+    CallStream st;
+    if (const int rc = dev_open("leon_anchor_dict_encode_pieces_device", device_id, st)) return rc;
+    TmpBuf d_dst;
+    std::string why;
+    if (const int rc = dict_pieces_code(st.s, d_kmers, n_anchors, k, P, piece_off, d_dst, why)) return dev_fail(rc, why);
+    *size = piece_off[dict_piece_count(n_anchors, P)];
+    if (*size > out_cap) return dev_fail(LEON_E_OVERFLOW, "anchor dictionary pieces: out_cap too small");
+    DEVCHK(hipMemcpyAsync(out, d_dst.p, *size, hipMemcpyDeviceToHost, st.s));
+    DEVCHK(hipStreamSynchronize(st.s));
+    return LEON_OK;
+}
+
+extern "C" int leon_anchor_dict_decode_pieces_device(int device_id, const uint8_t* payload, const uint64_t* piece_off, uint64_t n_pieces, uint64_t n_anchors, uint32_t k,
+                                          uint32_t piece_anchors, uint64_t* out_kmers) {
+    if (const char* why = dict_pieces_decode_refusal(payload, piece_off, n_pieces, n_anchors, k, piece_anchors, out_kmers)) return dev_fail(LEON_E_INVALID, why);
+    if (!n_pieces) return LEON_OK;                                // no piece: no device is asked
+    const uint32_t P = dict_piece_anchors(piece_anchors), W = kmer_words(k);
+    CallStream st;
+    if (const int rc = dev_open("leon_anchor_dict_decode_pieces_device", device_id, st)) return rc;
+    hipStream_t s = st.s;
+    // the pieces' bytes alone travel: [piece_off[0], piece_off[n_pieces]), the offsets rebased to them
+    const uint64_t first = piece_off[0], bytes = piece_off[n_pieces] - first;
+    std::vector<uint64_t> rel(n_pieces + 1);
+    for (uint64_t p = 0; p <= n_pieces; p++) rel[p] = piece_off[p] - first;
+    TmpBuf d_pay, d_off, d_out, d_bad;
+    DEVCHK(d_pay.ensure(bytes + 16)); DEVCHK(d_off.ensure((n_pieces + 1) * 8));
+    DEVCHK(d_out.ensure(n_anchors * W * 8)); DEVCHK(d_bad.ensure(n_pieces * 4));
+    if (bytes && staged_h2d(device_id, d_pay.p, payload + first, bytes) != hipSuccess) { (void)hipGetLastError(); return dev_fail(LEON_E_HIP, "leon_anchor_dict_decode_pieces_device: the pieces' copy to the device failed"); }
+    DEVCHK(hipMemcpyAsync(d_off.p, rel.data(), (n_pieces + 1) * 8, hipMemcpyHostToDevice, s));
+    DEVCHK(hipMemsetAsync(d_bad.p, 0, n_pieces * 4, s));
+    launch_dict_decode_pieces(s, d_pay.as<uint8_t>(), d_off.as<uint64_t>(), n_pieces, n_anchors, k, P, d_out.as<uint64_t>(), d_bad.as<uint32_t>());
+    DEVCHK(hipGetLastError());
+    std::vector<uint32_t> bad(n_pieces);
+    DEVCHK(hipMemcpyAsync(bad.data(), d_bad.p, n_pieces * 4, hipMemcpyDeviceToHost, s));
+    DEVCHK(hipStreamSynchronize(s));
+    for (uint64_t p = 0; p < n_pieces; p++) if (bad[p]) return dev_fail(LEON_E_INVALID, dict_piece_refusal(p));
+    DEVCHK(hipMemcpyAsync(out_kmers, d_out.p, n_anchors * W * 8, hipMemcpyDeviceToHost, s));
+    DEVCHK(hipStreamSynchronize(s));
+    return LEON_OK;
+}

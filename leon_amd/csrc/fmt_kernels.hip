@@ -9,8 +9,20 @@
 // writes the text OUTPUT-driven: a lane per 16 aligned output bytes, the way k_pack writes its slots.
 #include "kernels.h"
 #include "prim.h"
+#include "device_call.h"
+
+#include <algorithm>
 
 namespace leon {
+
+struct FmtLayout { uint64_t first_read_index, hdr_bytes; uint32_t wrap; uint8_t lead, fastq, plus_kind; };
+struct FmtPair {                                               // what the scan carries: a record's text offset and its first base
+    uint64_t rec, base;
+    FmtPair() = default;
+    __host__ __device__ FmtPair(int v) : rec((uint64_t)v), base((uint64_t)v) {}
+    __host__ __device__ FmtPair(uint64_t r, uint64_t b) : rec(r), base(b) {}
+    __host__ __device__ FmtPair operator+(const FmtPair& o) const { return FmtPair(rec + o.rec, base + o.base); }
+};
 
 namespace {
 
@@ -217,13 +229,14 @@ __global__ __launch_bounds__(256) void k_fmt_records(FmtLayout L, const FmtPair*
     }
 }
 
-}  // namespace
-
+// in[n_reads + 1] = every record's (text bytes, bases) and a last (0, 0); flags[0]: the header offsets run backwards, flags[1]: they do
+// not end at L.hdr_bytes (both zeroed by the caller); hdr_off == nullptr: the read index stands in for the header
 void launch_fmt_sizes(hipStream_t s, const FmtLayout& L, const uint32_t* len, const uint64_t* hdr_off, uint64_t n_reads, FmtPair* in, uint32_t* flags) {
     const uint64_t blocks = (n_reads + 1 + 255) / 256;
     hipLaunchKernelGGL(k_fmt_sizes, dim3((uint32_t)blocks), dim3(256), 0, s, L, len, hdr_off, n_reads, in, flags);
 }
 
+// exclusive, n_reads + 1 entries: out[n_reads] = the totals
 hipError_t fmt_scan(void* tmp, size_t& bytes, const FmtPair* in, FmtPair* out, uint64_t n_reads, hipStream_t s) {
     return prim::ExclusiveSum(tmp, bytes, in, out, n_reads + 1, s);
 }
@@ -233,6 +246,7 @@ void launch_fmt_rec_off(hipStream_t s, const FmtPair* off, uint64_t n_reads, uin
     hipLaunchKernelGGL(k_fmt_rec_off, dim3((uint32_t)blocks), dim3(256), 0, s, off, n_reads, rec_off);
 }
 
+// the text itself; the caller has verified off[n_reads] == (text_size, the bases given) and both flags of launch_fmt_sizes
 void launch_fmt_records(hipStream_t s, const FmtLayout& L, const FmtPair* off, const uint64_t* hdr_off, uint64_t n_reads, const uint8_t* bases,
                         const uint8_t* hdr, const uint8_t* quals, uint8_t* text, uint64_t text_size) {
     if (!text_size) return;
@@ -241,4 +255,58 @@ void launch_fmt_records(hipStream_t s, const FmtLayout& L, const FmtPair* off, c
     hipLaunchKernelGGL(k_fmt_records, dim3((uint32_t)blocks), dim3(FMT_THREADS), 0, s, L, off, hdr_off, n_reads, bases, hdr, quals, text, text_size);
 }
 
+}  // namespace
 }  // namespace leon
+
+using namespace leon;
+
+extern "C" int leon_records_format_device(int device_id, const leon_record_layout* lay, const uint8_t* d_bases, const uint32_t* d_len, uint64_t n_reads,
+                                          uint64_t n_bases, const uint8_t* d_hdr_text, const uint64_t* d_hdr_off, const uint8_t* d_quals, uint8_t* d_text,
+                                          uint64_t text_cap, uint64_t* d_rec_off, uint64_t* text_size) {
+    if (!lay || !text_size) return dev_fail(LEON_E_INVALID, "leon_records_format_device: null argument");
+    *text_size = 0;
+    if (lay->struct_size != sizeof(leon_record_layout))
+        return dev_fail(LEON_E_INVALID, "leon_records_format_device: unknown struct_size " + std::to_string(lay->struct_size) + " of leon_record_layout");
+    if (lay->plus_kind > 1) return dev_fail(LEON_E_INVALID, "leon_records_format_device: plus_kind must be 0 (bare) or 1 (the header again)");
+    if (n_reads > (1ull << 40) || n_bases > (1ull << 46)) return dev_fail(LEON_E_INVALID, "leon_records_format_device: implausible sizes");
+    if ((n_reads && !d_len) || (n_bases && !d_bases)) return dev_fail(LEON_E_INVALID, "leon_records_format_device: null argument");
+    if (lay->fastq && !d_quals) return dev_fail(LEON_E_INVALID, "leon_records_format_device: FASTQ records need the qualities (d_quals)");
+    if (lay->plus_kind == 1 && !d_hdr_text)
+        return dev_fail(LEON_E_INVALID, "leon_records_format_device: '+' lines that repeat the header need the headers (d_hdr_text)");
+    if (d_hdr_text && !d_hdr_off) return dev_fail(LEON_E_INVALID, "leon_records_format_device: headers without their offsets (d_hdr_off)");
+    if (!n_reads) return LEON_OK;
+    CallStream st;
+    if (const int rc = dev_open("leon_records_format_device", device_id, st)) return rc;
+    hipStream_t s = st.s;
+    const uint64_t* hdr_off = d_hdr_text ? d_hdr_off : nullptr;
+    FmtLayout L{};
+    L.first_read_index = lay->first_read_index; L.hdr_bytes = lay->hdr_bytes; L.wrap = lay->wrap;
+    L.lead = lay->lead; L.fastq = lay->fastq ? 1 : 0; L.plus_kind = lay->fastq ? lay->plus_kind : 0;
+    TmpBuf d_in, d_off, d_flags, d_tmp;
+    DEVCHK(d_in.ensure((n_reads + 1) * sizeof(FmtPair))); DEVCHK(d_off.ensure((n_reads + 1) * sizeof(FmtPair)));
+    DEVCHK(d_flags.ensure(64));
+    DEVCHK(hipMemsetAsync(d_flags.p, 0, 64, s));
+    launch_fmt_sizes(s, L, d_len, hdr_off, n_reads, d_in.as<FmtPair>(), d_flags.as<uint32_t>());
+    DEVCHK(hipGetLastError());
+    size_t tmp_bytes = 0;
+    DEVCHK(fmt_scan(nullptr, tmp_bytes, d_in.as<FmtPair>(), d_off.as<FmtPair>(), n_reads, s));
+    DEVCHK(d_tmp.ensure(std::max<size_t>(tmp_bytes, 16)));
+    DEVCHK(fmt_scan(d_tmp.p, tmp_bytes, d_in.as<FmtPair>(), d_off.as<FmtPair>(), n_reads, s));
+    uint32_t flags[2] = {0, 0};
+    uint64_t totals[2] = {0, 0};
+    DEVCHK(hipMemcpyAsync(flags, d_flags.p, 8, hipMemcpyDeviceToHost, s));
+    DEVCHK(hipMemcpyAsync(totals, d_off.as<FmtPair>() + n_reads, 16, hipMemcpyDeviceToHost, s));
+    DEVCHK(hipStreamSynchronize(s));
+    // what the arrays say against what the call was told, before anything is indexed with it
+    if (flags[0]) return dev_fail(LEON_E_INVALID, "leon_records_format_device: the header offsets (d_hdr_off) run backwards");
+    if (flags[1]) return dev_fail(LEON_E_INVALID, "leon_records_format_device: the header offsets (d_hdr_off) do not end at the " + std::to_string(lay->hdr_bytes) + " header bytes given");
+    if (totals[1] != n_bases)
+        return dev_fail(LEON_E_INVALID, "leon_records_format_device: the lengths (d_len) add up to " + std::to_string(totals[1]) + " bases, not the " + std::to_string(n_bases) + " given");
+    *text_size = totals[0];
+    if (totals[0] > text_cap || !d_text) return dev_fail(LEON_E_OVERFLOW, "leon_records_format_device: the text needs " + std::to_string(totals[0]) + " bytes");
+    launch_fmt_records(s, L, d_off.as<FmtPair>(), hdr_off, n_reads, d_bases, d_hdr_text, d_quals, d_text, totals[0]);
+    DEVCHK(hipGetLastError());
+    if (d_rec_off) { launch_fmt_rec_off(s, d_off.as<FmtPair>(), n_reads, d_rec_off); DEVCHK(hipGetLastError()); }
+    DEVCHK(hipStreamSynchronize(s));
+    return LEON_OK;
+}

@@ -1,4 +1,4 @@
-// host_bgzf.h -- what the two forms of the BGZF inflate share (host_streams.cpp; capi.hip for leon_bgzf_inflate_device), DESIGN.md 4.14
+// host_bgzf.h -- what the two forms of the BGZF inflate share (host_streams.cpp; inflate_kernels.hip for leon_bgzf_inflate_device), DESIGN.md 4.14
 #pragma once
 #include <stdint.h>
 

@@ -1,7 +1,7 @@
 // host_dict_pieces.h -- the anchor dictionary as independently coded PIECES, on host threads.  Compiles without HIP.
 // Anchors in address order are cut into pieces of P anchors (the last one holds the rest); piece p is exactly what AnchorDictCoder
 // writes for its slice: a fresh 5-symbol model, a fresh coder, the 8 flush bytes.  The stream is the pieces back to back; piece_off
-// (n_pieces + 1 entries) says where each begins.  These functions are the VERDICT for the device calls of capi.hip: the same
+// (n_pieces + 1 entries) says where each begins.  These functions are the VERDICT for the device calls of dict_kernels.hip: the same
 // arguments are refused with the same code and the same words (dict_pieces_*_refusal, shared by both).
 #pragma once
 #include "host_rc.h"

@@ -18,8 +18,22 @@
 // with the members' CRC-32 taken over the temporary by crc_kernels.hip.  The verdict is leon_host_bgzf_inflate's.
 #include "kernels.h"
 #include "prim.h"
+#include "device_call.h"
+#include "staging.h"
+#include "host_bgzf.h"
+
+#include <algorithm>
+#include <vector>
 
 namespace leon {
+
+// a block of one launch: its payload in the launch's payload buffer, its share of the temporary text (16-byte aligned, text_size =
+// its quality bytes + its reads: the lines with their newlines), its first 4 KiB tile of the text, its place in d_quals and d_qual_off.
+// A BGZF member is a QiBlock too: pay0 / pay_size = its raw deflate stream in the launch's payload buffer, text0 = its 16-byte aligned
+// share of the temporary, text_size = its ISIZE, tile0 = its first 4 KiB tile, q0 = its first byte in the contiguous text (read0, n_reads: 0).
+struct QiBlock { uint64_t pay0, pay_size, text0, text_size, tile0, q0, read0, n_reads; };
+enum : uint32_t { QI_OK = 0, QI_HEADER = 1, QI_TYPE = 2, QI_STORED = 3, QI_TABLE = 4, QI_CODE = 5, QI_DIST = 6, QI_LONG = 7, QI_EARLY = 8,
+                  QI_SHORT = 9, QI_LINES = 10, QI_ADLER = 11, QI_SLACK = 12 /* (BGZF) bytes between the stream's end and the trailer */ };
 
 namespace {
 
@@ -520,31 +534,36 @@ __global__ __launch_bounds__(256) void k_qual_lens(const uint64_t* __restrict__ 
     if (r < n && qual_off[read0 + r + 1] - qual_off[read0 + r] != len[read0 + r]) atomicMin(bad_read, (unsigned long long)(read0 + r));
 }
 
-}  // namespace
-
+// one wave per block; status[b] = QI_OK or why the stream was refused, adler_expect[b] = the stream's own checksum; n_syms: nullptr,
+// or a counter of the literal/length symbols decoded (measurement)
 void launch_qual_inflate(hipStream_t s, const uint32_t* pay, uint64_t pay_words, const QiBlock* blk, uint32_t n_blocks, uint8_t* text, uint32_t* status,
                          uint32_t* adler_expect, unsigned long long* n_syms) {
     if (!n_blocks) return;
     hipLaunchKernelGGL(k_qual_inflate, dim3(n_blocks), dim3(64), 0, s, pay, pay_words, blk, n_blocks, text, status, adler_expect, n_syms);
 }
 
+// one wave per member, the decoder of launch_qual_inflate on a raw stream that ends with its payload; status[b] = QI_OK or why
 void launch_bgzf_inflate(hipStream_t s, const uint32_t* pay, uint64_t pay_words, const QiBlock* blk, uint32_t n_blocks, uint8_t* tmp, uint32_t* status,
                          unsigned long long* n_syms) {
     if (!n_blocks) return;
     hipLaunchKernelGGL(k_bgzf_inflate, dim3(n_blocks), dim3(64), 0, s, pay, pay_words, blk, n_blocks, tmp, status, n_syms);
 }
 
+// the shares of the temporary to text[q0 ..), contiguous, whatever text's alignment; nothing at or behind text_end is written
 void launch_bgzf_gather(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, uint64_t n_tiles, const uint8_t* tmp, uint8_t* text, uint64_t text_end) {
     if (!n_tiles) return;
     hipLaunchKernelGGL(k_bgzf_gather, dim3((uint32_t)n_tiles), dim3(QT_THREADS), 0, s, blk, n_blocks, n_tiles, tmp, text, text_end);
 }
 
+// per 4 KiB tile of the text: its newlines (tile_nl: n_tiles + 1, the last 0); per block (zeroed by the caller): the two Adler-32 sums,
+// whether the last byte is a newline
 void launch_qual_tiles(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, uint64_t n_tiles, const uint8_t* text, uint32_t* tile_nl,
                        unsigned long long* sums, uint32_t* last_nl) {
     if (!n_tiles) return;
     hipLaunchKernelGGL(k_qual_tiles, dim3((uint32_t)n_tiles), dim3(QT_THREADS), 0, s, blk, n_blocks, n_tiles, text, tile_nl, sums, last_nl);
 }
 
+// exclusive, n_tiles + 1 entries
 hipError_t qual_tiles_scan(void* tmp, size_t& bytes, const uint32_t* tile_nl, uint64_t* nl_before, uint64_t n_tiles, hipStream_t s) {
     return prim::ExclusiveSum(tmp, bytes, tile_nl, nl_before, n_tiles + 1, s);
 }
@@ -555,6 +574,7 @@ void launch_qual_check(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, con
     hipLaunchKernelGGL(k_qual_check, dim3((n_blocks + 255) / 256), dim3(256), 0, s, blk, n_blocks, nl_before, sums, last_nl, adler_expect, status);
 }
 
+// the text without its newlines and the reads' offsets; only after every status of the launch is QI_OK
 void launch_qual_lines(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, uint64_t n_tiles, const uint8_t* text, const uint64_t* nl_before,
                        uint8_t* quals, uint64_t quals_end, uint64_t* qual_off, uint64_t total_reads) {
     if (!n_tiles) return;
@@ -566,4 +586,179 @@ void launch_qual_lens(hipStream_t s, const uint64_t* qual_off, const uint32_t* l
     hipLaunchKernelGGL(k_qual_lens, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, qual_off, len, read0, n, bad_read);
 }
 
+}  // namespace
 }  // namespace leon
+
+using namespace leon;
+
+extern "C" int leon_qual_inflate_blocks_device(int device_id, const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads,
+                                    const uint64_t* block_n_bytes, uint64_t n_blocks, const uint32_t* d_len, uint8_t* d_quals, uint64_t quals_cap,
+                                    uint64_t* d_qual_off, uint64_t* n_symbols) {
+    if (n_symbols) *n_symbols = 0;
+    if (n_blocks && (!payloads || !payload_off || !block_n_reads || !block_n_bytes || !d_quals)) return dev_fail(LEON_E_INVALID, "null argument");
+    if (!n_blocks) return LEON_OK;
+    if (n_blocks > (1ull << 31)) return dev_fail(LEON_E_INVALID, "implausible number of blocks");
+    std::vector<uint64_t> o0(n_blocks + 1, 0), r0(n_blocks + 1, 0);
+    for (uint64_t b = 0; b < n_blocks; b++) {
+        if (payload_off[b + 1] < payload_off[b]) return dev_fail(LEON_E_INVALID, "payload offsets are not monotonic");
+        o0[b + 1] = o0[b] + block_n_bytes[b];
+        r0[b + 1] = r0[b] + block_n_reads[b];
+        if (o0[b + 1] < o0[b] || o0[b + 1] > quals_cap) return dev_fail(LEON_E_INVALID, "output capacity below the sum of block_n_bytes");
+    }
+    const uint64_t total_reads = r0[n_blocks];
+    CallStream st;
+    if (const int rc = dev_open("leon_qual_inflate_blocks_device", device_id, st)) return rc;
+    hipStream_t s = st.s;
+    // The blocks in launches of at most kMaxBlocks blocks and kMaxText bytes of temporary text (the lines WITH their newlines, every
+    // block's share 16-byte aligned): what bounds the temporaries; a launch holds at least one block.
+    constexpr uint64_t kMaxBlocks = 1024, kMaxText = 8ull << 30;
+    auto share = [&](uint64_t b) { return (block_n_bytes[b] + block_n_reads[b] + 15) & ~15ull; };
+    std::vector<uint64_t> cut{0};
+    uint64_t max_text = 0, max_pay = 0, max_tiles = 0, max_blocks = 0;
+    for (uint64_t b = 0; b < n_blocks;) {
+        uint64_t e = b, text = 0, tiles = 0;
+        while (e < n_blocks && (e == b || (e - b < kMaxBlocks && text + share(e) <= kMaxText))) {
+            text += share(e); tiles += (block_n_bytes[e] + block_n_reads[e] + 4095) / 4096; e++;
+        }
+        max_text = std::max(max_text, text); max_tiles = std::max(max_tiles, tiles); max_blocks = std::max(max_blocks, e - b);
+        max_pay = std::max(max_pay, payload_off[e] - payload_off[b]);
+        cut.push_back(e); b = e;
+    }
+    if (max_tiles >= (1ull << 31)) return dev_fail(LEON_E_INVALID, "implausible block sizes");
+    TmpBuf d_pay, d_text, d_blk, d_status, d_adler, d_tile_nl, d_nl_before, d_sums, d_last, d_tmp, d_cnt, d_off_own;
+    DEVCHK(d_pay.ensure(max_pay + 64)); DEVCHK(d_text.ensure(max_text + 64));
+    DEVCHK(d_blk.ensure((max_blocks + 1) * sizeof(QiBlock)));
+    DEVCHK(d_status.ensure(max_blocks * 4)); DEVCHK(d_adler.ensure(max_blocks * 4)); DEVCHK(d_last.ensure(max_blocks * 4));
+    DEVCHK(d_sums.ensure(max_blocks * 16));
+    DEVCHK(d_tile_nl.ensure((max_tiles + 1) * 4)); DEVCHK(d_nl_before.ensure((max_tiles + 1) * 8));
+    DEVCHK(d_cnt.ensure(16));
+    DEVCHK(hipMemsetAsync(d_cnt.p, 0, 8, s));
+    DEVCHK(hipMemsetAsync(d_cnt.as<uint8_t>() + 8, 0xFF, 8, s));
+    size_t tmp_bytes = 0;
+    DEVCHK(qual_tiles_scan(nullptr, tmp_bytes, d_tile_nl.as<uint32_t>(), d_nl_before.as<uint64_t>(), max_tiles, s));
+    DEVCHK(d_tmp.ensure(std::max<size_t>(tmp_bytes, 16)));
+    uint64_t* qual_off = d_qual_off;
+    if (!qual_off && d_len) { DEVCHK(d_off_own.ensure((total_reads + 1) * 8)); qual_off = d_off_own.as<uint64_t>(); }   // the lengths are checked through the offsets
+    if (qual_off) DEVCHK(hipMemsetAsync(qual_off, 0, 8, s));
+    std::vector<QiBlock> blk;
+    std::vector<uint32_t> status;
+    for (size_t g = 0; g + 1 < cut.size(); g++) {
+        const uint64_t b0 = cut[g], b1 = cut[g + 1], nb = b1 - b0, pay_bytes = payload_off[b1] - payload_off[b0];
+        blk.assign(nb + 1, QiBlock{});
+        uint64_t text = 0, tiles = 0;
+        for (uint64_t b = b0; b <= b1; b++) {
+            QiBlock& K = blk[b - b0];
+            K.text0 = text; K.tile0 = tiles;
+            if (b == b1) break;
+            K.pay0 = payload_off[b] - payload_off[b0]; K.pay_size = payload_off[b + 1] - payload_off[b];
+            K.text_size = block_n_bytes[b] + block_n_reads[b];
+            K.q0 = o0[b]; K.read0 = r0[b]; K.n_reads = block_n_reads[b];
+            text += share(b); tiles += (K.text_size + 4095) / 4096;
+        }
+        if (staged_h2d(device_id, d_pay.p, payloads + payload_off[b0], pay_bytes) != hipSuccess) { (void)hipGetLastError(); return dev_fail(LEON_E_HIP, "leon_qual_inflate_blocks_device: the payloads' copy to the device failed"); }
+        DEVCHK(hipMemcpyAsync(d_blk.p, blk.data(), (nb + 1) * sizeof(QiBlock), hipMemcpyHostToDevice, s));
+        DEVCHK(hipMemsetAsync(d_sums.p, 0, nb * 16, s));
+        DEVCHK(hipMemsetAsync(d_last.p, 0, nb * 4, s));
+        DEVCHK(hipMemsetAsync(d_tile_nl.as<uint32_t>() + tiles, 0, 4, s));
+        launch_qual_inflate(s, d_pay.as<uint32_t>(), (pay_bytes + 3) / 4, d_blk.as<QiBlock>(), (uint32_t)nb, d_text.as<uint8_t>(), d_status.as<uint32_t>(),
+                            d_adler.as<uint32_t>(), n_symbols ? d_cnt.as<unsigned long long>() : nullptr);
+        DEVCHK(hipGetLastError());
+        launch_qual_tiles(s, d_blk.as<QiBlock>(), (uint32_t)nb, tiles, d_text.as<uint8_t>(), d_tile_nl.as<uint32_t>(), d_sums.as<unsigned long long>(), d_last.as<uint32_t>());
+        DEVCHK(hipGetLastError());
+        DEVCHK(qual_tiles_scan(d_tmp.p, tmp_bytes, d_tile_nl.as<uint32_t>(), d_nl_before.as<uint64_t>(), tiles, s));
+        launch_qual_check(s, d_blk.as<QiBlock>(), (uint32_t)nb, d_nl_before.as<uint64_t>(), d_sums.as<unsigned long long>(), d_last.as<uint32_t>(),
+                          d_adler.as<uint32_t>(), d_status.as<uint32_t>());
+        DEVCHK(hipGetLastError());
+        // the blocks' status words in one small copy; the smallest failing block is the one the host way names
+        status.assign(nb, 0);
+        DEVCHK(hipMemcpyAsync(status.data(), d_status.p, nb * 4, hipMemcpyDeviceToHost, s));
+        DEVCHK(hipStreamSynchronize(s));
+        for (uint64_t b = 0; b < nb; b++)
+            if (status[b] != QI_OK) return dev_fail(LEON_E_INVALID, "quality block " + std::to_string(b0 + b) + " does not decode");
+        launch_qual_lines(s, d_blk.as<QiBlock>(), (uint32_t)nb, tiles, d_text.as<uint8_t>(), d_nl_before.as<uint64_t>(), d_quals, o0[n_blocks], qual_off, total_reads);
+        DEVCHK(hipGetLastError());
+        DEVCHK(hipStreamSynchronize(s));                 // the next launch reuses the temporaries (and the host's blk)
+    }
+    uint64_t words[2] = {0, ~0ull};
+    if (d_len) { launch_qual_lens(s, qual_off, d_len, 0, total_reads, d_cnt.as<unsigned long long>() + 1); DEVCHK(hipGetLastError()); }
+    DEVCHK(hipMemcpyAsync(words, d_cnt.p, 16, hipMemcpyDeviceToHost, s));
+    DEVCHK(hipStreamSynchronize(s));
+    if (n_symbols) *n_symbols = words[0];
+    if (words[1] != ~0ull) {
+        const uint64_t b = (uint64_t)(std::upper_bound(r0.begin(), r0.end(), words[1]) - r0.begin()) - 1;
+        return dev_fail(LEON_E_INVALID, "read " + std::to_string(words[1]) + " (quality block " + std::to_string(b) + "): the quality line's length is not the one given (d_len)");
+    }
+    return LEON_OK;
+}
+
+extern "C" int leon_bgzf_inflate_device(int device_id, const uint8_t* bytes, uint64_t n_bytes, const uint64_t* member_off, uint64_t n_members, uint8_t* d_text,
+                             uint64_t text_cap, uint64_t* n_text, uint32_t max_members_per_launch, uint64_t* n_symbols) {
+    if (n_symbols) *n_symbols = 0;
+    std::vector<BgzfMember> m;
+    {
+        std::string why;
+        if (const int rc = bgzf_prepare(bytes, n_bytes, member_off, n_members, d_text, text_cap, n_text, m, why)) return dev_fail(rc, why);
+    }
+    if (!n_members) return LEON_OK;
+    CallStream st;
+    if (const int rc = dev_open("leon_bgzf_inflate_device", device_id, st)) return rc;
+    hipStream_t s = st.s;
+    // launches of at most `per` members: what bounds the temporaries (a member has at most 64 KiB of payload and of text)
+    const uint64_t per = max_members_per_launch ? max_members_per_launch : 4096;
+    auto share = [&](uint64_t i) { return ((uint64_t)m[i].isize + 15) & ~15ull; };
+    uint64_t max_pay = 0, max_tmp = 0, max_nb = 0;
+    for (uint64_t b0 = 0; b0 < n_members; b0 += per) {
+        const uint64_t b1 = std::min(n_members, b0 + per);
+        uint64_t tmp = 0;
+        for (uint64_t i = b0; i < b1; i++) tmp += share(i);
+        max_pay = std::max(max_pay, member_off[b1] - member_off[b0]); max_tmp = std::max(max_tmp, tmp); max_nb = std::max(max_nb, b1 - b0);
+    }
+    TmpBuf d_pay, d_tmp, d_blk, d_status, d_seg, d_acc, d_cnt;
+    DEVCHK(d_pay.ensure(max_pay + 64)); DEVCHK(d_tmp.ensure(max_tmp + 64));
+    DEVCHK(d_blk.ensure((max_nb + 1) * sizeof(QiBlock)));
+    DEVCHK(d_status.ensure(max_nb * 4)); DEVCHK(d_seg.ensure((2 * max_nb + 1) * 8)); DEVCHK(d_acc.ensure(2 * max_nb * 4));
+    DEVCHK(d_cnt.ensure(8));
+    DEVCHK(hipMemsetAsync(d_cnt.p, 0, 8, s));
+    std::vector<QiBlock> blk;
+    std::vector<uint64_t> seg;
+    std::vector<uint32_t> status, acc;
+    for (uint64_t b0 = 0; b0 < n_members; b0 += per) {
+        const uint64_t b1 = std::min(n_members, b0 + per), nb = b1 - b0, pay_bytes = member_off[b1] - member_off[b0];
+        blk.assign(nb + 1, QiBlock{}); seg.assign(2 * nb + 1, 0);
+        uint64_t tmp = 0, tiles = 0;
+        for (uint64_t i = b0; i <= b1; i++) {
+            QiBlock& K = blk[i - b0];
+            K.text0 = tmp; K.tile0 = tiles;
+            seg[2 * (i - b0)] = tmp;                              // the member's text, then the share's padding: two segments
+            if (i == b1) break;
+            if (m[i].ok) { K.pay0 = m[i].pay0 - member_off[b0]; K.pay_size = m[i].pay_size; K.text_size = m[i].isize; }   // (!ok: an empty stream, refused below)
+            K.q0 = m[i].text0;
+            seg[2 * (i - b0) + 1] = tmp + K.text_size;
+            tmp += share(i); tiles += (K.text_size + 4095) / 4096;
+        }
+        if (staged_h2d(device_id, d_pay.p, bytes + member_off[b0], pay_bytes) != hipSuccess) { (void)hipGetLastError(); return dev_fail(LEON_E_HIP, "leon_bgzf_inflate_device: the payloads' copy to the device failed"); }
+        DEVCHK(hipMemcpyAsync(d_blk.p, blk.data(), (nb + 1) * sizeof(QiBlock), hipMemcpyHostToDevice, s));
+        DEVCHK(hipMemcpyAsync(d_seg.p, seg.data(), (2 * nb + 1) * 8, hipMemcpyHostToDevice, s));
+        DEVCHK(hipMemsetAsync(d_acc.p, 0, 2 * nb * 4, s));
+        launch_bgzf_inflate(s, d_pay.as<uint32_t>(), (pay_bytes + 3) / 4, d_blk.as<QiBlock>(), (uint32_t)nb, d_tmp.as<uint8_t>(), d_status.as<uint32_t>(),
+                            n_symbols ? d_cnt.as<unsigned long long>() : nullptr);
+        DEVCHK(hipGetLastError());
+        // the CRC-32 of every member's text where the wave left it, before anything goes to d_text
+        launch_crc32_segments(s, d_tmp.as<uint8_t>(), d_seg.as<uint64_t>(), 2 * nb, crc32_tile_count(d_tmp.as<uint8_t>(), 0, tmp), d_acc.as<uint32_t>());
+        DEVCHK(hipGetLastError());
+        status.assign(nb, 0); acc.assign(2 * nb, 0);
+        DEVCHK(hipMemcpyAsync(status.data(), d_status.p, nb * 4, hipMemcpyDeviceToHost, s));
+        DEVCHK(hipMemcpyAsync(acc.data(), d_acc.p, 2 * nb * 4, hipMemcpyDeviceToHost, s));
+        DEVCHK(hipStreamSynchronize(s));
+        for (uint64_t i = 0; i < nb; i++)
+            if (!m[b0 + i].ok || status[i] != QI_OK || acc[2 * i] != m[b0 + i].crc) return dev_fail(LEON_E_INVALID, bgzf_refusal(b0 + i, member_off[b0 + i]));
+        launch_bgzf_gather(s, d_blk.as<QiBlock>(), (uint32_t)nb, tiles, d_tmp.as<uint8_t>(), d_text, *n_text);
+        DEVCHK(hipGetLastError());
+        DEVCHK(hipStreamSynchronize(s));                 // the next launch reuses the temporaries (and the host's tables)
+    }
+    if (n_symbols) {
+        DEVCHK(hipMemcpyAsync(n_symbols, d_cnt.p, 8, hipMemcpyDeviceToHost, s));
+        DEVCHK(hipStreamSynchronize(s));
+    }
+    return LEON_OK;
+}

@@ -1,7 +1,9 @@
-// kernels.h -- host-callable launchers of the gfx950 kernels (definitions in *.hip).
+// kernels.h -- host-callable launchers of the gfx950 kernels (definitions in *.hip) that are called from ANOTHER file; a launcher whose
+// callers all sit beside its kernel is local to that file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string>
 #include "leon_device.h"
 
 namespace leon {
@@ -195,54 +197,6 @@ void launch_decode_blocks(hipStream_t s, BloomDev B, PathCache C, const uint16_t
                           uint32_t* pool, unsigned long long* pool_cursor, uint64_t pool_words, int* err,
                           unsigned long long* stats /* nullptr, or 16 counters: rounds by kind, time by part (LEON_TRACE_DECODE) */);
 
-// ---- record text (fmt_kernels.hip): FASTA / FASTQ records formatted on the device, DESIGN.md 4.9 ----
-struct FmtLayout { uint64_t first_read_index, hdr_bytes; uint32_t wrap; uint8_t lead, fastq, plus_kind; };
-struct FmtPair {                                               // what the scan carries: a record's text offset and its first base
-    uint64_t rec, base;
-    FmtPair() = default;
-    __host__ __device__ FmtPair(int v) : rec((uint64_t)v), base((uint64_t)v) {}
-    __host__ __device__ FmtPair(uint64_t r, uint64_t b) : rec(r), base(b) {}
-    __host__ __device__ FmtPair operator+(const FmtPair& o) const { return FmtPair(rec + o.rec, base + o.base); }
-};
-// in[n_reads + 1] = every record's (text bytes, bases) and a last (0, 0); flags[0]: the header offsets run backwards, flags[1]: they do
-// not end at L.hdr_bytes (both zeroed by the caller); hdr_off == nullptr: the read index stands in for the header
-void launch_fmt_sizes(hipStream_t s, const FmtLayout& L, const uint32_t* len, const uint64_t* hdr_off, uint64_t n_reads, FmtPair* in, uint32_t* flags);
-hipError_t fmt_scan(void* tmp, size_t& bytes, const FmtPair* in, FmtPair* out, uint64_t n_reads, hipStream_t s);   // exclusive, n_reads + 1 entries: out[n_reads] = the totals
-void launch_fmt_rec_off(hipStream_t s, const FmtPair* off, uint64_t n_reads, uint64_t* rec_off);
-// the text itself; the caller has verified off[n_reads] == (text_size, the bases given) and both flags of launch_fmt_sizes
-void launch_fmt_records(hipStream_t s, const FmtLayout& L, const FmtPair* off, const uint64_t* hdr_off, uint64_t n_reads, const uint8_t* bases,
-                        const uint8_t* hdr, const uint8_t* quals, uint8_t* text, uint64_t text_size);
-
-// ---- quality blocks inflated on the device (inflate_kernels.hip), DESIGN.md 4.10 ----
-// a block of one launch: its payload in the launch's payload buffer, its share of the temporary text (16-byte aligned, text_size =
-// its quality bytes + its reads: the lines with their newlines), its first 4 KiB tile of the text, its place in d_quals and d_qual_off
-struct QiBlock { uint64_t pay0, pay_size, text0, text_size, tile0, q0, read0, n_reads; };
-enum : uint32_t { QI_OK = 0, QI_HEADER = 1, QI_TYPE = 2, QI_STORED = 3, QI_TABLE = 4, QI_CODE = 5, QI_DIST = 6, QI_LONG = 7, QI_EARLY = 8,
-                  QI_SHORT = 9, QI_LINES = 10, QI_ADLER = 11, QI_SLACK = 12 /* (BGZF) bytes between the stream's end and the trailer */ };
-// one wave per block; status[b] = QI_OK or why the stream was refused, adler_expect[b] = the stream's own checksum; n_syms: nullptr,
-// or a counter of the literal/length symbols decoded (measurement)
-void launch_qual_inflate(hipStream_t s, const uint32_t* pay, uint64_t pay_words, const QiBlock* blk /* n_blocks + 1 */, uint32_t n_blocks, uint8_t* text,
-                         uint32_t* status, uint32_t* adler_expect, unsigned long long* n_syms);
-// per 4 KiB tile of the text: its newlines; per block (zeroed by the caller): the two Adler-32 sums, whether the last byte is a newline
-void launch_qual_tiles(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, uint64_t n_tiles, const uint8_t* text, uint32_t* tile_nl /* n_tiles + 1, the last 0 */,
-                       unsigned long long* sums, uint32_t* last_nl);
-hipError_t qual_tiles_scan(void* tmp, size_t& bytes, const uint32_t* tile_nl, uint64_t* nl_before, uint64_t n_tiles, hipStream_t s);   // exclusive, n_tiles + 1 entries
-void launch_qual_check(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, const uint64_t* nl_before, const unsigned long long* sums,
-                       const uint32_t* last_nl, const uint32_t* adler_expect, uint32_t* status);
-// the text without its newlines and the reads' offsets; only after every status of the launch is QI_OK
-void launch_qual_lines(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, uint64_t n_tiles, const uint8_t* text, const uint64_t* nl_before,
-                       uint8_t* quals, uint64_t quals_end, uint64_t* qual_off, uint64_t total_reads);
-void launch_qual_lens(hipStream_t s, const uint64_t* qual_off, const uint32_t* len, uint64_t read0, uint64_t n, unsigned long long* bad_read /* ~0 before */);
-
-// ---- BGZF members inflated on the device (inflate_kernels.hip), DESIGN.md 4.14 ----
-// A member is a QiBlock: pay0 / pay_size = its raw deflate stream in the launch's payload buffer, text0 = its 16-byte aligned share of
-// the temporary, text_size = its ISIZE, tile0 = its first 4 KiB tile, q0 = its first byte in the contiguous text (read0, n_reads: 0).
-// one wave per member, the decoder of launch_qual_inflate on a raw stream that ends with its payload; status[b] = QI_OK or why
-void launch_bgzf_inflate(hipStream_t s, const uint32_t* pay, uint64_t pay_words, const QiBlock* blk /* n_blocks + 1 */, uint32_t n_blocks, uint8_t* tmp,
-                         uint32_t* status, unsigned long long* n_syms);
-// the shares of the temporary to text[q0 ..), contiguous, whatever text's alignment; nothing at or behind text_end is written
-void launch_bgzf_gather(hipStream_t s, const QiBlock* blk, uint32_t n_blocks, uint64_t n_tiles, const uint8_t* tmp, uint8_t* text, uint64_t text_end);
-
 // ---- zlib's CRC-32 of segments of a device buffer (crc_kernels.hip), DESIGN.md 4.11 ----
 constexpr uint64_t CRC32_MAX_GROUPS = 4096;                    // the grid's cap: a workgroup walks ceil(tiles / cap) consecutive tiles
 // the 4 KiB tiles (cut at 16-byte aligned addresses) that hold bytes[first .. last)
@@ -255,14 +209,9 @@ constexpr uint64_t LETTERS_MAX_GROUPS = 2048;                  // the grid's cap
 
 // ---- the anchor dictionary in independently coded pieces (dict_kernels.hip), DESIGN.md 4.4 ----
 constexpr uint32_t DICT_PIECES_MAX_GROUPS = 1024;              // the grid's cap: a wave codes 64 pieces (lane = piece), then the 64 a grid further on
-// piece p = anchors [p * P, min((p + 1) * P, n_anchors)) of kmers, coded into scratch[p * stride .. + stride) (stride >= 64), sizes[p] its
-// bytes; *err (zeroed by the caller) is set when a piece came within 4 bytes of its stride: code again with a wider one
-void launch_dict_encode_pieces(hipStream_t s, const uint64_t* kmers, uint64_t n_anchors, uint32_t k, uint32_t P, uint64_t n_pieces, uint8_t* scratch,
-                               uint64_t stride, uint64_t* sizes, int* err);
-// the slots back to back: off[n_pieces + 1] = the exclusive sums of sizes
-void launch_dict_gather_pieces(hipStream_t s, const uint8_t* scratch, uint64_t stride, const uint64_t* off, uint64_t n_pieces, uint8_t* dst);
-// piece p = payload[off[p] .. off[p + 1]) -> its anchors' k-mer words in out; bad[p] (zeroed by the caller) is set for a piece that does not decode
-void launch_dict_decode_pieces(hipStream_t s, const uint8_t* payload, const uint64_t* off, uint64_t n_pieces, uint64_t n_anchors, uint32_t k, uint32_t P,
-                               uint64_t* out, uint32_t* bad);
+// the pieces of d_kmers coded on stream s into d_dst, piece_off (host, n_pieces + 1 entries) where each begins: leon_dna_finish (capi.hip)
+// and leon_anchor_dict_encode_pieces_device share it.  LEON_OK, or the code with `why`
+struct TmpBuf;
+int dict_pieces_code(hipStream_t s, const uint64_t* d_kmers, uint64_t n_anchors, uint32_t k, uint32_t P, uint64_t* piece_off, TmpBuf& d_dst, std::string& why);
 
 }  // namespace leon

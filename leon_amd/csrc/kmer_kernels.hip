@@ -2,8 +2,8 @@
 // kmer/impl/SortingCountAlgorithm [RECALLED], whose solid k-mers Leon::createBloom inserts).  Sort-based: the canonical
 // k-mers of the reads are emitted in hash partitions that fit the device, each partition is radix-sorted (rocPRIM, prim.h), runs
 // of at least min_abundance equal k-mers are kept.  k-mers containing an N are skipped, as DSK does.
-#include "../../include/leon_dna.h"
 #include "kernels.h"
+#include "device_call.h"
 
 #include "prim.h"
 #include "staging.h"
@@ -17,7 +17,6 @@
 #include <vector>
 
 namespace leon {
-void set_create_error(const std::string& msg);   // capi.hip: message behind leon_last_error(NULL)
 
 namespace {
 
@@ -212,7 +211,6 @@ struct Buf {
     size_t bytes_ = 0;
     int park_device = -1;                                       // >= 0: park instead of free
     hipError_t alloc(size_t bytes) {
-        static const bool trace = getenv("LEON_TRACE_ALLOC") != nullptr;       // (as in capi.hip: allocations of 1 ms or more on stderr)
         bytes_ = bytes ? bytes : 16;
         if (park_device >= 0) {                                 // a parked buffer of this device that is large enough (and not absurdly larger)?
             std::lock_guard<std::mutex> g(g_park_mu);
@@ -227,7 +225,7 @@ struct Buf {
         const auto t0 = std::chrono::steady_clock::now();
         hipError_t e = hipMalloc(&p, bytes_);
         if (e != hipSuccess) { (void)hipGetLastError(); leon_device_trim(); e = hipMalloc(&p, bytes_); }
-        if (trace) {
+        if (g_trace_alloc) {                                   // (LEON_TRACE_ALLOC, as DevBuf: 1 ms or more on stderr)
             const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             if (ms >= 1.0) fprintf(stderr, "[leon alloc] kmer: %.1f MB in %.1f ms\n", bytes_ / 1e6, ms);
         }
@@ -236,10 +234,9 @@ struct Buf {
     ~Buf() {
         if (!p) return;
         if (park_device >= 0) { std::lock_guard<std::mutex> g(g_park_mu); g_parked.push_back({p, bytes_, park_device}); return; }
-        static const bool trace = getenv("LEON_TRACE_ALLOC") != nullptr;
         const auto t0 = std::chrono::steady_clock::now();
         (void)hipFree(p);
-        if (trace) {
+        if (g_trace_alloc) {
             const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             if (ms >= 1.0) fprintf(stderr, "[leon alloc] kmer: free in %.1f ms\n", ms);
         }
@@ -247,8 +244,6 @@ struct Buf {
     template <typename T> T* as() { return (T*)p; }
 };
 uint32_t grid(uint64_t n, uint32_t per = 256, uint32_t cap = 8192) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + per - 1) / per, cap)); }
-
-#define KCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_create_error(std::string(#call) + ": " + hipGetErrorString(e_)); return LEON_E_HIP; } } while (0)
 
 }  // namespace
 }  // namespace leon
@@ -272,41 +267,60 @@ int leon_device_count(int* n_devices) {
     if (!n_devices) return LEON_E_INVALID;
     *n_devices = 0;
     int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) { set_create_error("no usable HIP device"); return LEON_E_NO_DEVICE; }
+    if (hipGetDeviceCount(&n) != hipSuccess) return dev_fail(LEON_E_NO_DEVICE, "no usable HIP device");
     *n_devices = n;
     return LEON_OK;
 }
 int leon_device_alloc(int device_id, uint64_t bytes, void** d_ptr) {
     if (!d_ptr) return LEON_E_INVALID;
     *d_ptr = nullptr;
-    KCHK(hipSetDevice(device_id));
-    KCHK(hipMalloc(d_ptr, bytes ? bytes : 16));
+    DEVCHK(hipSetDevice(device_id));
+    DEVCHK(hipMalloc(d_ptr, bytes ? bytes : 16));
     return LEON_OK;
 }
 int leon_device_upload(int device_id, void* d_dst, const void* src, uint64_t bytes) {
     if (bytes && (!d_dst || !src)) return LEON_E_INVALID;
-    KCHK(hipSetDevice(device_id));
-    if (bytes) KCHK(staged_h2d(device_id, d_dst, src, bytes));
+    DEVCHK(hipSetDevice(device_id));
+    if (bytes) DEVCHK(staged_h2d(device_id, d_dst, src, bytes));
     return LEON_OK;
 }
 int leon_device_copy(int device_id, void* d_dst, const void* d_src, uint64_t bytes) {
     if (bytes && (!d_dst || !d_src)) return LEON_E_INVALID;
-    KCHK(hipSetDevice(device_id));
+    DEVCHK(hipSetDevice(device_id));
     if (bytes) {
-        KCHK(hipMemcpy(d_dst, d_src, bytes, hipMemcpyDeviceToDevice));
+        DEVCHK(hipMemcpy(d_dst, d_src, bytes, hipMemcpyDeviceToDevice));
         // (a device-to-device hipMemcpy may return before the copy has run: a caller that hands d_dst to work on ANOTHER stream next --
         // the exchange callbacks of leon_dna_set_exchange / leon_dna_set_gather do -- must find it complete)
-        KCHK(hipStreamSynchronize(nullptr));
+        DEVCHK(hipStreamSynchronize(nullptr));
     }
     return LEON_OK;
 }
 
 int leon_device_download(int device_id, void* dst, const void* d_src, uint64_t bytes) {
     if (bytes && (!dst || !d_src)) return LEON_E_INVALID;
-    KCHK(hipSetDevice(device_id));
-    if (bytes) KCHK(staged_d2h(device_id, dst, d_src, bytes));          // (at PCIe's rate for large copies: staging.h)
+    DEVCHK(hipSetDevice(device_id));
+    if (bytes) DEVCHK(staged_d2h(device_id, dst, d_src, bytes));          // (at PCIe's rate for large copies: staging.h)
     return LEON_OK;
 }
+
+int leon_device_download_pieces(int device_id, const void* d_src, uint64_t bytes, leon_piece_sink sink, void* user) {
+    if (!sink || (bytes && !d_src)) return dev_fail(LEON_E_INVALID, "leon_device_download_pieces: null argument");
+    if (!bytes) return LEON_OK;
+    if (const int rc = dev_select("leon_device_download_pieces", device_id)) return rc;
+    const int rc = staged_d2h_pieces(device_id, d_src, bytes, [&](uint64_t offset, const void* p, uint64_t size) { return sink(user, offset, p, size); });
+    if (rc == 2) return dev_fail(LEON_E_SINK, "leon_device_download_pieces: the sink returned non-zero");
+    if (rc) return dev_fail(LEON_E_HIP, "leon_device_download_pieces: copy to the host failed");
+    return LEON_OK;
+}
+
+int leon_host_pinned_alloc(int device_id, uint64_t bytes, void** ptr) {
+    if (!ptr) return dev_fail(LEON_E_INVALID, "leon_host_pinned_alloc: null argument");
+    *ptr = nullptr;
+    if (const int rc = dev_select("leon_host_pinned_alloc", device_id)) return rc;
+    if (hipHostMalloc(ptr, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); *ptr = nullptr; return dev_fail(LEON_E_HIP, "leon_host_pinned_alloc: " + std::to_string(bytes) + " bytes of pinned memory refused"); }
+    return LEON_OK;
+}
+void leon_host_pinned_free(void* ptr) { if (ptr) (void)hipHostFree(ptr); }
 
 // The abundance threshold Leon uses when `-abundance` is absent ("default: automatic", /root/reference/README.md:54; upstream
 // asks DSK for `-abundance-min auto` [RECALLED]): the first local minimum of the abundance spectrum -- the valley between the
@@ -327,7 +341,7 @@ int leon_kmer_solid_device(int device_id, const uint8_t* d_bases, const uint64_t
                            uint32_t min_abundance, uint64_t max_keys_per_pass, uint64_t** d_solid, uint64_t* n_solid,
                            uint64_t* histogram) {
     if (!d_solid || !n_solid || (n_reads && (!d_bases || !d_offsets))) return LEON_E_INVALID;
-    if (k < 3 || k > 63) { set_create_error("kmer_solid: need 3 <= k <= 63"); return LEON_E_INVALID; }
+    if (k < 3 || k > 63) return dev_fail(LEON_E_INVALID, "kmer_solid: need 3 <= k <= 63");
     // min_abundance 0 = automatic (Leon's default, /root/reference/README.md:54): k-mers seen twice or more are kept with their
     // abundance while the partitions go by, the threshold comes from the whole spectrum (leon_kmer_auto_cutoff), then they are filtered
     const bool automatic = min_abundance == 0;
@@ -336,41 +350,41 @@ int leon_kmer_solid_device(int device_id, const uint8_t* d_bases, const uint64_t
     if (histogram) memset(histogram, 0, 256 * sizeof(uint64_t));
     if (!n_reads) return LEON_OK;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) { set_create_error("kmer_solid: no such HIP device"); return LEON_E_NO_DEVICE; }
-    KCHK(hipSetDevice(device_id));
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) return dev_fail(LEON_E_NO_DEVICE, "kmer_solid: no such HIP device");
+    DEVCHK(hipSetDevice(device_id));
     hipStream_t s = nullptr;
     const uint32_t W = kmer_words(k);
     // ---- pack the reads once ----
     Buf slot_off, packed, nmask, rlen, ncount, tmp, pos;
     Buf bad;
-    KCHK(slot_off.alloc((n_reads + 1) * 8));
-    KCHK(bad.alloc(4));
-    KCHK(hipMemsetAsync(bad.p, 0, 4, s));
+    DEVCHK(slot_off.alloc((n_reads + 1) * 8));
+    DEVCHK(bad.alloc(4));
+    DEVCHK(hipMemsetAsync(bad.p, 0, 4, s));
     launch_read_slots(s, d_offsets, n_reads, slot_off.as<uint64_t>(), bad.as<uint32_t>());
     size_t tb = 0;
-    KCHK(prim::ExclusiveSum(nullptr, tb, slot_off.as<uint64_t>(), slot_off.as<uint64_t>(), n_reads + 1, s));
-    KCHK(tmp.alloc(tb));
-    KCHK(prim::ExclusiveSum(tmp.p, tb, slot_off.as<uint64_t>(), slot_off.as<uint64_t>(), n_reads + 1, s));
+    DEVCHK(prim::ExclusiveSum(nullptr, tb, slot_off.as<uint64_t>(), slot_off.as<uint64_t>(), n_reads + 1, s));
+    DEVCHK(tmp.alloc(tb));
+    DEVCHK(prim::ExclusiveSum(tmp.p, tb, slot_off.as<uint64_t>(), slot_off.as<uint64_t>(), n_reads + 1, s));
     uint64_t n_slots = 0;
-    KCHK(hipMemcpy(&n_slots, slot_off.as<uint64_t>() + n_reads, 8, hipMemcpyDeviceToHost));
+    DEVCHK(hipMemcpy(&n_slots, slot_off.as<uint64_t>() + n_reads, 8, hipMemcpyDeviceToHost));
     uint32_t bad_offsets = 0;
-    KCHK(hipMemcpy(&bad_offsets, bad.p, 4, hipMemcpyDeviceToHost));
-    if (bad_offsets) { set_create_error("kmer_solid: offsets are not monotonic (or a read is longer than 2^31 bases)"); return LEON_E_INVALID; }
-    KCHK(packed.alloc((n_slots * 2 + 16) * 4)); KCHK(nmask.alloc((n_slots + 4) * 4)); KCHK(rlen.alloc(n_reads * 4)); KCHK(ncount.alloc(n_reads * 4));
-    KCHK(hipMemsetAsync(packed.as<uint32_t>() + n_slots * 2, 0, 64, s));
+    DEVCHK(hipMemcpy(&bad_offsets, bad.p, 4, hipMemcpyDeviceToHost));
+    if (bad_offsets) return dev_fail(LEON_E_INVALID, "kmer_solid: offsets are not monotonic (or a read is longer than 2^31 bases)");
+    DEVCHK(packed.alloc((n_slots * 2 + 16) * 4)); DEVCHK(nmask.alloc((n_slots + 4) * 4)); DEVCHK(rlen.alloc(n_reads * 4)); DEVCHK(ncount.alloc(n_reads * 4));
+    DEVCHK(hipMemsetAsync(packed.as<uint32_t>() + n_slots * 2, 0, 64, s));
     launch_pack(s, d_bases, d_offsets, slot_off.as<uint64_t>(), n_reads, packed.as<uint32_t>(), nmask.as<uint32_t>(), rlen.as<uint32_t>(), ncount.as<uint32_t>());
     ReadsDev R{};
     R.packed = packed.as<uint32_t>(); R.nmask = nmask.as<uint32_t>(); R.slot_off = slot_off.as<uint64_t>(); R.base_off = d_offsets;
     R.len = rlen.as<uint32_t>(); R.n_count = ncount.as<uint32_t>(); R.n = n_reads; R.k = k;
     // ---- how many k-mer positions, hence how many partitions ----
-    KCHK(pos.alloc((n_reads + 1) * 8));
+    DEVCHK(pos.alloc((n_reads + 1) * 8));
     hipLaunchKernelGGL(k_positions, dim3(grid(n_reads)), dim3(256), 0, s, d_offsets, n_reads, k, pos.as<uint64_t>());
     Buf tmp2; size_t tb2 = 0;
-    KCHK(prim::Sum(nullptr, tb2, pos.as<uint64_t>(), pos.as<uint64_t>() + n_reads, n_reads, s));
-    KCHK(tmp2.alloc(tb2));
-    KCHK(prim::Sum(tmp2.p, tb2, pos.as<uint64_t>(), pos.as<uint64_t>() + n_reads, n_reads, s));
+    DEVCHK(prim::Sum(nullptr, tb2, pos.as<uint64_t>(), pos.as<uint64_t>() + n_reads, n_reads, s));
+    DEVCHK(tmp2.alloc(tb2));
+    DEVCHK(prim::Sum(tmp2.p, tb2, pos.as<uint64_t>(), pos.as<uint64_t>() + n_reads, n_reads, s));
     uint64_t total = 0;
-    KCHK(hipMemcpy(&total, pos.as<uint64_t>() + n_reads, 8, hipMemcpyDeviceToHost));
+    DEVCHK(hipMemcpy(&total, pos.as<uint64_t>() + n_reads, 8, hipMemcpyDeviceToHost));
     if (!total) return LEON_OK;
     if (!max_keys_per_pass) {
         // 2^30 k-mers per pass (17-34 GB of sort buffers), less when a third of the free HBM does not hold them.  NOT "as
@@ -378,7 +392,7 @@ int leon_kmer_solid_device(int device_id, const uint8_t* d_bases, const uint64_t
         // returned 200 GB made the first allocation of the encode path wait 3.8 s (profiles/README.md, round 2), and
         // passes of 2^30 keys sort no slower than one of 2^32.
         size_t free_b = 0, total_b = 0;
-        KCHK(hipMemGetInfo(&free_b, &total_b));
+        DEVCHK(hipMemGetInfo(&free_b, &total_b));
         max_keys_per_pass = std::max<uint64_t>(1ull << 24, std::min<uint64_t>(1ull << 30, free_b / 3 / (8 * W * 2 + 1)));
     }
     uint32_t n_parts = (uint32_t)((total + max_keys_per_pass - 1) / max_keys_per_pass);
@@ -389,26 +403,26 @@ int leon_kmer_solid_device(int device_id, const uint8_t* d_bases, const uint64_t
     // ---- per-partition buffers ----
     Buf keys, alt, alt2, alt3, flags, nsel, hist, sort_tmp, sel_tmp, runlen, runsel;
     keys.park_device = alt.park_device = alt2.park_device = alt3.park_device = device_id;       // (the large ones: see Parked)
-    KCHK(keys.alloc(cap * 8 * W)); KCHK(alt.alloc(cap * 8 * W)); KCHK(flags.alloc(cap));
-    if (automatic) { KCHK(runlen.alloc(cap)); KCHK(runsel.alloc(cap)); }
-    if (W == 2) { KCHK(alt2.alloc(cap * 8)); KCHK(alt3.alloc(cap * 8)); }
-    KCHK(nsel.alloc(8)); KCHK(hist.alloc(256 * 8));
-    KCHK(hipMemset(hist.p, 0, 256 * 8));
+    DEVCHK(keys.alloc(cap * 8 * W)); DEVCHK(alt.alloc(cap * 8 * W)); DEVCHK(flags.alloc(cap));
+    if (automatic) { DEVCHK(runlen.alloc(cap)); DEVCHK(runsel.alloc(cap)); }
+    if (W == 2) { DEVCHK(alt2.alloc(cap * 8)); DEVCHK(alt3.alloc(cap * 8)); }
+    DEVCHK(nsel.alloc(8)); DEVCHK(hist.alloc(256 * 8));
+    DEVCHK(hipMemset(hist.p, 0, 256 * 8));
     size_t st = 0, st2 = 0, sl = 0;
-    if (W == 1) { KCHK(prim::SortKeys(nullptr, st, keys.as<uint64_t>(), alt.as<uint64_t>(), cap, 0, 2 * k, s)); }
+    if (W == 1) { DEVCHK(prim::SortKeys(nullptr, st, keys.as<uint64_t>(), alt.as<uint64_t>(), cap, 0, 2 * k, s)); }
     else {
-        KCHK(prim::SortPairs(nullptr, st, keys.as<uint64_t>(), alt.as<uint64_t>(), alt2.as<uint64_t>(), alt3.as<uint64_t>(), cap, 0, 64, s));
+        DEVCHK(prim::SortPairs(nullptr, st, keys.as<uint64_t>(), alt.as<uint64_t>(), alt2.as<uint64_t>(), alt3.as<uint64_t>(), cap, 0, 64, s));
         st2 = st;
     }
-    KCHK(sort_tmp.alloc(std::max(st, st2)));
+    DEVCHK(sort_tmp.alloc(std::max(st, st2)));
     // the solid k-mers accumulate here (grown geometrically)
     uint64_t out_cap = std::max<uint64_t>(total / 16, 1u << 20), out_n = 0;
     uint64_t* out = nullptr;
     uint8_t* out_cnt = nullptr;                               // automatic: abundance (clipped at 255) of every kept k-mer
-    KCHK(hipMalloc((void**)&out, out_cap * 8 * W));
+    DEVCHK(hipMalloc((void**)&out, out_cap * 8 * W));
     auto fail_free = [&](int code) { if (out) (void)hipFree(out); if (out_cnt) (void)hipFree(out_cnt); return code; };
     const bool want_hist = histogram != nullptr || automatic;
-#define KCHK2(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_create_error(std::string(#call) + ": " + hipGetErrorString(e_)); return fail_free(LEON_E_HIP); } } while (0)
+#define KCHK2(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail_free(dev_fail(LEON_E_HIP, hip_failure(#call, e_))); } while (0)   // DEVCHK that frees `out` on its way
     if (automatic) KCHK2(hipMalloc((void**)&out_cnt, out_cap));
     Buf cursor, tile_cnt, tile_tmp;
     KCHK2(cursor.alloc(16));
@@ -425,7 +439,7 @@ int leon_kmer_solid_device(int device_id, const uint8_t* d_bases, const uint64_t
         else hipLaunchKernelGGL((k_part_kmers<u128>), dim3(part_grid), dim3(256), 0, s, R, n_parts, part, keys.as<uint64_t>(), cap, cursor.as<unsigned long long>(), cursor.as<unsigned long long>() + 1);
         uint64_t cur[2] = {0, 0};
         KCHK2(hipMemcpy(cur, cursor.p, 16, hipMemcpyDeviceToHost));
-        if (cur[0] > cap) { set_create_error("kmer_solid: a hash partition exceeds its buffer (very skewed k-mer spectrum); lower max_keys_per_pass"); return fail_free(LEON_E_OVERFLOW); }
+        if (cur[0] > cap) return fail_free(dev_fail(LEON_E_OVERFLOW, "kmer_solid: a hash partition exceeds its buffer (very skewed k-mer spectrum); lower max_keys_per_pass"));
         const uint64_t n_all = cur[0], n = cur[0] - cur[1];      // with and without the padding, which sorts to the end
         if (trace) fprintf(stderr, "[leon kmer] partition %u of %u: %llu k-mers (+ %llu of padding), buffer %llu\n", part, n_parts, (unsigned long long)n, (unsigned long long)cur[1], (unsigned long long)cap);
         if (!n) continue;
@@ -510,19 +524,19 @@ int leon_kmer_solid(int device_id, const uint8_t* bases, const uint64_t* offsets
     if (!n_solid || (n_reads && (!bases || !offsets))) return LEON_E_INVALID;
     *n_solid = 0;
     if (!n_reads) { if (histogram) memset(histogram, 0, 256 * sizeof(uint64_t)); return LEON_OK; }     // (as the device form leaves it)
-    if (hipSetDevice(device_id) != hipSuccess) { set_create_error("kmer_solid: no such HIP device"); return LEON_E_NO_DEVICE; }
+    if (const int rc = dev_select("kmer_solid", device_id)) return rc;
     const uint64_t nb = offsets[n_reads] - offsets[0];
     std::vector<uint64_t> rel(n_reads + 1);
     for (uint64_t i = 0; i <= n_reads; i++) rel[i] = offsets[i] - offsets[0];
     Buf db, doff;
-    KCHK(db.alloc(nb + 64)); KCHK(doff.alloc((n_reads + 1) * 8));
-    KCHK(hipMemcpy(db.p, bases + offsets[0], nb, hipMemcpyHostToDevice));
-    KCHK(hipMemcpy(doff.p, rel.data(), (n_reads + 1) * 8, hipMemcpyHostToDevice));
+    DEVCHK(db.alloc(nb + 64)); DEVCHK(doff.alloc((n_reads + 1) * 8));
+    DEVCHK(hipMemcpy(db.p, bases + offsets[0], nb, hipMemcpyHostToDevice));
+    DEVCHK(hipMemcpy(doff.p, rel.data(), (n_reads + 1) * 8, hipMemcpyHostToDevice));
     uint64_t* d = nullptr;
     int rc = leon_kmer_solid_device(device_id, db.as<uint8_t>(), doff.as<uint64_t>(), n_reads, k, min_abundance, max_keys_per_pass, &d, n_solid, histogram);
     if (rc) return rc;
     const uint32_t W = kmer_words(k);
-    if (out && *n_solid <= out_cap && *n_solid) KCHK(hipMemcpy(out, d, *n_solid * 8 * W, hipMemcpyDeviceToHost));
+    if (out && *n_solid <= out_cap && *n_solid) DEVCHK(hipMemcpy(out, d, *n_solid * 8 * W, hipMemcpyDeviceToHost));
     leon_device_free(d);
     return (out && *n_solid > out_cap) ? LEON_E_OVERFLOW : LEON_OK;
 }

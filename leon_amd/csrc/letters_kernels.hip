@@ -22,14 +22,13 @@
 // Bounds: a 16-byte load or store is made only by a lane whose 16 bytes lie whole inside [0, n); every other byte is touched alone
 // after its position was tested.  The tables are indexed below the counts the launch was given.
 #include "kernels.h"
-#include "../../include/leon_dna.h"
+#include "device_call.h"
 
 #include <algorithm>
 #include <string>
 
 namespace leon {
 
-void set_create_error(const std::string& msg);                   // capi.hip: the message behind leon_last_error(NULL)
 // host_streams.cpp: what both forms of apply refuse, in the same words; nullptr = the tables are in order
 const char* letters_tables_refusal(const uint8_t* bases, uint64_t n_bytes, const uint64_t* runs, uint64_t n_runs, const uint64_t* odd_pos,
                                    const uint8_t* odd_byte, uint64_t n_odd);
@@ -267,19 +266,6 @@ __global__ __launch_bounds__(256) void k_letters_odd(uint8_t* __restrict__ bytes
     }
 }
 
-#define LCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_create_error(std::string(#call) + ": " + hipGetErrorString(e_)); return LEON_E_HIP; } } while (0)
-
-int lt_fail(int code, const std::string& msg) { set_create_error(msg); return code; }
-
-struct Dev {
-    void* p = nullptr;
-    ~Dev() { if (p) (void)hipFree(p); }
-    hipError_t alloc(uint64_t bytes) { return hipMalloc(&p, bytes ? bytes : 8); }
-    template <typename T> T* as() const { return static_cast<T*>(p); }
-};
-// a stream of the call's own: the call runs beside calls on the contexts' streams
-struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } };
-
 // the tiles of n bytes at d: `extra` = 1 covers position n too (the end of a run that reaches the last byte lies there)
 struct Tiles { uint64_t n_tiles, per; uint32_t groups; };
 Tiles lt_tiles(const uint8_t* d, uint64_t n, uint32_t extra) {
@@ -292,16 +278,16 @@ Tiles lt_tiles(const uint8_t* d, uint64_t n, uint32_t extra) {
 }
 
 // k_letters_count and k_letters_scan over the buffer: the totals to the host, the per-workgroup words left on the device for take
-struct Counted { Dev cnt, before, base, total; Tiles T; uint64_t totals[2] = {0, 0}; };
+struct Counted { TmpBuf cnt, before, base, total; Tiles T; uint64_t totals[2] = {0, 0}; };
 int lt_count(hipStream_t s, const uint8_t* d_bases, uint64_t n_bytes, Counted& C) {
     C.T = lt_tiles(d_bases, n_bytes, 1);
-    LCHK(C.cnt.alloc(C.T.groups * 16ull)); LCHK(C.before.alloc(C.T.groups * 4ull)); LCHK(C.base.alloc(C.T.groups * 16ull)); LCHK(C.total.alloc(16));
+    DEVCHK(C.cnt.ensure(C.T.groups * 16ull)); DEVCHK(C.before.ensure(C.T.groups * 4ull)); DEVCHK(C.base.ensure(C.T.groups * 16ull)); DEVCHK(C.total.ensure(16));
     hipLaunchKernelGGL(k_letters_count, dim3(C.T.groups), dim3(LT_THREADS), 0, s, d_bases, n_bytes, C.T.n_tiles, C.T.per, C.cnt.as<ull>(), C.before.as<uint32_t>());
-    LCHK(hipGetLastError());
+    DEVCHK(hipGetLastError());
     hipLaunchKernelGGL(k_letters_scan, dim3(1), dim3(256), 0, s, C.cnt.as<ull>(), C.T.groups, C.base.as<ull>(), C.total.as<ull>());
-    LCHK(hipGetLastError());
-    LCHK(hipMemcpyAsync(C.totals, C.total.p, 16, hipMemcpyDeviceToHost, s));
-    LCHK(hipStreamSynchronize(s));
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipMemcpyAsync(C.totals, C.total.p, 16, hipMemcpyDeviceToHost, s));
+    DEVCHK(hipStreamSynchronize(s));
     return LEON_OK;
 }
 
@@ -313,13 +299,12 @@ using namespace leon;
 extern "C" {
 
 int leon_letters_count_device(int device_id, const uint8_t* d_bases, uint64_t n_bytes, uint64_t* n_runs, uint64_t* n_odd) {
-    if (!n_runs || !n_odd || (n_bytes && !d_bases)) return lt_fail(LEON_E_INVALID, "letters: null argument");
-    if (n_bytes >> 62) return lt_fail(LEON_E_INVALID, "letters: implausible sizes");
+    if (!n_runs || !n_odd || (n_bytes && !d_bases)) return dev_fail(LEON_E_INVALID, "letters: null argument");
+    if (n_bytes >> 62) return dev_fail(LEON_E_INVALID, "letters: implausible sizes");
     *n_runs = *n_odd = 0;
     if (!n_bytes) return LEON_OK;
-    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return lt_fail(LEON_E_NO_DEVICE, "leon_letters_count_device: no such HIP device"); }
-    Stream st;
-    LCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    CallStream st;
+    if (const int rc = dev_open("leon_letters_count_device", device_id, st)) return rc;
     Counted C;
     if (const int rc = lt_count(st.s, d_bases, n_bytes, C)) return rc;
     *n_runs = C.totals[0]; *n_odd = C.totals[1];
@@ -328,57 +313,56 @@ int leon_letters_count_device(int device_id, const uint8_t* d_bases, uint64_t n_
 
 int leon_letters_take_device(int device_id, uint8_t* d_bases, uint64_t n_bytes, uint64_t* runs, uint64_t n_runs, uint64_t* odd_pos, uint8_t* odd_byte,
                              uint64_t n_odd) {
-    if ((n_bytes && !d_bases) || (n_runs && !runs) || (n_odd && (!odd_pos || !odd_byte))) return lt_fail(LEON_E_INVALID, "letters: null argument");
-    if ((n_bytes >> 62) || (n_runs >> 58) || (n_odd >> 58)) return lt_fail(LEON_E_INVALID, "letters: implausible sizes");
+    if ((n_bytes && !d_bases) || (n_runs && !runs) || (n_odd && (!odd_pos || !odd_byte))) return dev_fail(LEON_E_INVALID, "letters: null argument");
+    if ((n_bytes >> 62) || (n_runs >> 58) || (n_odd >> 58)) return dev_fail(LEON_E_INVALID, "letters: implausible sizes");
     auto differs = [&](uint64_t r, uint64_t x) {
-        return lt_fail(LEON_E_STATE, "letters: the buffer holds " + std::to_string(r) + " run(s) and " + std::to_string(x) + " other byte(s), not the " +
+        return dev_fail(LEON_E_STATE, "letters: the buffer holds " + std::to_string(r) + " run(s) and " + std::to_string(x) + " other byte(s), not the " +
                                          std::to_string(n_runs) + " and " + std::to_string(n_odd) + " the tables were sized for");
     };
     if (!n_bytes) return n_runs || n_odd ? differs(0, 0) : LEON_OK;
-    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return lt_fail(LEON_E_NO_DEVICE, "leon_letters_take_device: no such HIP device"); }
-    Stream st;
-    LCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    CallStream st;
+    if (const int rc = dev_open("leon_letters_take_device", device_id, st)) return rc;
     hipStream_t s = st.s;
     Counted C;
     if (const int rc = lt_count(s, d_bases, n_bytes, C)) return rc;
     if (C.totals[0] != n_runs || C.totals[1] != n_odd) return differs(C.totals[0], C.totals[1]);      // (nothing was written so far)
     if (!n_runs && !n_odd) return LEON_OK;                        // the bytes are their own folded form
-    Dev d_runs, d_pos, d_byte;
-    LCHK(d_runs.alloc(n_runs * 16)); LCHK(d_pos.alloc(n_odd * 8)); LCHK(d_byte.alloc(n_odd));
+    TmpBuf d_runs, d_pos, d_byte;
+    // (at least 8 bytes each: a kernel argument is never null, even for an empty table)
+    DEVCHK(d_runs.ensure(std::max<uint64_t>(n_runs * 16, 8))); DEVCHK(d_pos.ensure(std::max<uint64_t>(n_odd * 8, 8))); DEVCHK(d_byte.ensure(std::max<uint64_t>(n_odd, 8)));
     hipLaunchKernelGGL(k_letters_take, dim3(C.T.groups), dim3(LT_THREADS), 0, s, d_bases, n_bytes, C.T.n_tiles, C.T.per, C.base.as<ull>(), C.before.as<uint32_t>(),
                        d_runs.as<uint64_t>(), n_runs, d_pos.as<uint64_t>(), d_byte.as<uint8_t>(), n_odd);
-    LCHK(hipGetLastError());
-    if (n_runs) LCHK(hipMemcpyAsync(runs, d_runs.p, n_runs * 16, hipMemcpyDeviceToHost, s));
-    if (n_odd) { LCHK(hipMemcpyAsync(odd_pos, d_pos.p, n_odd * 8, hipMemcpyDeviceToHost, s)); LCHK(hipMemcpyAsync(odd_byte, d_byte.p, n_odd, hipMemcpyDeviceToHost, s)); }
-    LCHK(hipStreamSynchronize(s));
+    DEVCHK(hipGetLastError());
+    if (n_runs) DEVCHK(hipMemcpyAsync(runs, d_runs.p, n_runs * 16, hipMemcpyDeviceToHost, s));
+    if (n_odd) { DEVCHK(hipMemcpyAsync(odd_pos, d_pos.p, n_odd * 8, hipMemcpyDeviceToHost, s)); DEVCHK(hipMemcpyAsync(odd_byte, d_byte.p, n_odd, hipMemcpyDeviceToHost, s)); }
+    DEVCHK(hipStreamSynchronize(s));
     return LEON_OK;
 }
 
 int leon_letters_apply_device(int device_id, uint8_t* d_bases, uint64_t n_bytes, const uint64_t* runs, uint64_t n_runs, const uint64_t* odd_pos,
                               const uint8_t* odd_byte, uint64_t n_odd) {
-    if (const char* why = letters_tables_refusal(d_bases, n_bytes, runs, n_runs, odd_pos, odd_byte, n_odd)) return lt_fail(LEON_E_INVALID, why);
+    if (const char* why = letters_tables_refusal(d_bases, n_bytes, runs, n_runs, odd_pos, odd_byte, n_odd)) return dev_fail(LEON_E_INVALID, why);
     if (!n_bytes || (!n_runs && !n_odd)) return LEON_OK;
-    if (hipSetDevice(device_id) != hipSuccess) { (void)hipGetLastError(); return lt_fail(LEON_E_NO_DEVICE, "leon_letters_apply_device: no such HIP device"); }
-    Stream st;
-    LCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    CallStream st;
+    if (const int rc = dev_open("leon_letters_apply_device", device_id, st)) return rc;
     hipStream_t s = st.s;
-    Dev d_runs, d_pos, d_byte;
+    TmpBuf d_runs, d_pos, d_byte;
     if (n_runs) {
-        LCHK(d_runs.alloc(n_runs * 16));
-        LCHK(hipMemcpyAsync(d_runs.p, runs, n_runs * 16, hipMemcpyHostToDevice, s));
+        DEVCHK(d_runs.ensure(n_runs * 16));
+        DEVCHK(hipMemcpyAsync(d_runs.p, runs, n_runs * 16, hipMemcpyHostToDevice, s));
         const Tiles T = lt_tiles(d_bases, n_bytes, 0);
         hipLaunchKernelGGL(k_letters_case, dim3(T.groups), dim3(LT_THREADS), 0, s, d_bases, n_bytes, T.n_tiles, T.per, d_runs.as<uint64_t>(), n_runs);
-        LCHK(hipGetLastError());
+        DEVCHK(hipGetLastError());
     }
     if (n_odd) {
-        LCHK(d_pos.alloc(n_odd * 8)); LCHK(d_byte.alloc(n_odd));
-        LCHK(hipMemcpyAsync(d_pos.p, odd_pos, n_odd * 8, hipMemcpyHostToDevice, s));
-        LCHK(hipMemcpyAsync(d_byte.p, odd_byte, n_odd, hipMemcpyHostToDevice, s));
+        DEVCHK(d_pos.ensure(n_odd * 8)); DEVCHK(d_byte.ensure(n_odd));
+        DEVCHK(hipMemcpyAsync(d_pos.p, odd_pos, n_odd * 8, hipMemcpyHostToDevice, s));
+        DEVCHK(hipMemcpyAsync(d_byte.p, odd_byte, n_odd, hipMemcpyHostToDevice, s));
         const uint32_t groups = (uint32_t)std::min<uint64_t>((n_odd + 255) / 256, LETTERS_MAX_GROUPS);
         hipLaunchKernelGGL(k_letters_odd, dim3(groups), dim3(256), 0, s, d_bases, n_bytes, d_pos.as<uint64_t>(), d_byte.as<uint8_t>(), n_odd);
-        LCHK(hipGetLastError());
+        DEVCHK(hipGetLastError());
     }
-    LCHK(hipStreamSynchronize(s));
+    DEVCHK(hipStreamSynchronize(s));
     return LEON_OK;
 }
 

@@ -183,3 +183,96 @@ def test_host_anchor_dict_decode_on_skewed_streams(lib, kind):
             capi.anchor_dict_decode(stream[:cut], n, k)
         except capi.LeonDnaError:
             pass
+
+
+# ---- the stateless device calls when the device they are told to use does not exist ----
+# Every call gets valid arguments of the smallest size that makes it ask for its device, and an ordinal no machine has: what comes
+# back is the same with and without a GPU.  (code, leon_last_error(NULL)); a text that ends in ": " is a prefix, HIP's own words follow.
+_NO_DEVICE = 1 << 20
+_U8, _U32, _U64 = ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint64
+_PIECE_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, _U64, ctypes.c_void_p, _U64)
+_BLOCK_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, _U64, ctypes.POINTER(_U8), _U64, _U32)
+_piece_sink = _PIECE_SINK(lambda user, offset, p, size: 0)
+_block_sink = _BLOCK_SINK(lambda user, block_id, p, size, n_reads: 0)
+
+
+def _bgzf_member(text):
+    import struct
+    import zlib
+    z = zlib.compressobj(6, zlib.DEFLATED, -15)
+    raw = z.compress(text) + z.flush()
+    head = bytes([0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0]) + b"BC" + struct.pack("<HH", 2, 12 + 6 + len(raw) + 8 - 1)
+    return head + raw + struct.pack("<II", zlib.crc32(text), len(text))
+
+
+def _no_device_calls():
+    from leon_amd import capi
+    d = _NO_DEVICE
+    buf = (_U8 * 64)(*b"A" * 64)                                  # stands in for device memory: no call reaches it
+    ptr = ctypes.cast(buf, ctypes.c_void_p)
+    one32, two64 = (_U32 * 1)(1), (_U64 * 2)(0, 1)
+    out32, out64, w = (_U32 * 4)(), (_U64 * 4)(), [_U64() for _ in range(4)]
+    lay = capi.RecordLayout(struct_size=ctypes.sizeof(capi.RecordLayout), lead=ord(">"))
+    member = _bgzf_member(b"A")
+    m_off = (_U64 * 2)(0, len(member))
+    pay_off = (_U64 * 2)(0, 8)
+    hip = -3                                                      # LEON_E_HIP
+    return [
+        ("leon_records_format_device", lambda L: L.leon_records_format_device(d, ctypes.byref(lay), ptr, one32, _U64(1), _U64(1), None, None, None, ptr, _U64(64), None, ctypes.byref(w[0])), -2, None),
+        ("leon_qual_inflate_blocks_device", lambda L: L.leon_qual_inflate_blocks_device(d, ptr, pay_off, one32, (_U64 * 1)(1), _U64(1), None, ptr, _U64(16), None, None), -2, None),
+        ("leon_bgzf_inflate_device", lambda L: L.leon_bgzf_inflate_device(d, member, _U64(len(member)), m_off, _U64(1), ptr, _U64(16), ctypes.byref(w[0]), _U32(0), None), -2, None),
+        ("leon_crc32_segments_device", lambda L: L.leon_crc32_segments_device(d, ptr, _U64(1), two64, _U64(1), out32), -2, None),
+        ("leon_anchor_dict_encode_pieces_device", lambda L: L.leon_anchor_dict_encode_pieces_device(d, ptr, _U64(1), _U32(31), _U32(0), ptr, _U64(64), out64, ctypes.byref(w[0])), -2, None),
+        ("leon_anchor_dict_decode_pieces_device", lambda L: L.leon_anchor_dict_decode_pieces_device(d, ptr, (_U64 * 2)(0, 4), _U64(1), _U64(1), _U32(31), _U32(0), out64), -2, None),
+        ("leon_host_pinned_alloc", lambda L: L.leon_host_pinned_alloc(d, _U64(16), ctypes.byref(ctypes.c_void_p())), -2, None),
+        ("leon_device_download_pieces", lambda L: L.leon_device_download_pieces(d, ptr, _U64(1), _piece_sink, None), -2, None),
+        ("leon_letters_count_device", lambda L: L.leon_letters_count_device(d, ptr, _U64(1), ctypes.byref(w[0]), ctypes.byref(w[1])), -2, None),
+        ("leon_letters_take_device", lambda L: L.leon_letters_take_device(d, ptr, _U64(1), out64, _U64(0), out64, ptr, _U64(0)), -2, None),
+        ("leon_letters_apply_device", lambda L: L.leon_letters_apply_device(d, ptr, _U64(1), two64, _U64(1), None, None, _U64(0)), -2, None),
+        ("leon_text_bgzf_device", lambda L: L.leon_text_bgzf_device(d, ptr, _U64(1), 1, _piece_sink, None, ctypes.byref(w[0]), ctypes.byref(w[1]), None), -2, None),
+        ("leon_text_bgzf_records_device", lambda L: L.leon_text_bgzf_records_device(d, ptr, _U64(0), _U64(1), None, _U64(0), 1, _piece_sink, None, ctypes.byref(w[0]), ctypes.byref(w[1]), None, None, _U64(0), ctypes.byref(w[2])), -2, None),
+        ("leon_text_bgzf_records_device[records]", lambda L: L.leon_text_bgzf_records_device(d, ptr, _U64(0), _U64(1), two64, _U64(1), 1, _piece_sink, None, ctypes.byref(w[0]), ctypes.byref(w[1]), None, None, _U64(0), ctypes.byref(w[2])), -2, None),
+        ("leon_qual_deflate_blocks_device", lambda L: L.leon_qual_deflate_blocks_device(d, ptr, two64, _U64(1), _U32(1), _block_sink, None, _U64(0)), -2, "qual_deflate: no such HIP device"),
+        ("leon_kmer_solid_device", lambda L: L.leon_kmer_solid_device(d, ptr, two64, _U64(1), _U32(31), _U32(2), _U64(0), ctypes.byref(ctypes.c_void_p()), ctypes.byref(w[0]), None), -2, "kmer_solid: no such HIP device"),
+        ("leon_kmer_solid", lambda L: L.leon_kmer_solid(d, ptr, two64, _U64(1), _U32(31), _U32(2), _U64(0), out64, _U64(4), ctypes.byref(w[0]), None), -2, "kmer_solid: no such HIP device"),
+        ("leon_device_alloc", lambda L: L.leon_device_alloc(d, _U64(16), ctypes.byref(ctypes.c_void_p())), hip, "hipSetDevice(device_id): "),
+        ("leon_device_upload", lambda L: L.leon_device_upload(d, ptr, ptr, _U64(1)), hip, "hipSetDevice(device_id): "),
+        ("leon_device_copy", lambda L: L.leon_device_copy(d, ptr, ptr, _U64(1)), hip, "hipSetDevice(device_id): "),
+        ("leon_device_download", lambda L: L.leon_device_download(d, ptr, ptr, _U64(1)), hip, "hipSetDevice(device_id): "),
+    ]
+
+
+_NO_DEVICE_NAMES = [c[0] for c in _no_device_calls()]
+
+
+def _last_error(raw):
+    raw.leon_last_error.restype = ctypes.c_char_p
+    raw.leon_last_error.argtypes = [ctypes.c_void_p]
+    return raw.leon_last_error(None).decode()
+
+
+@pytest.mark.parametrize("name", _NO_DEVICE_NAMES)
+def test_stateless_call_without_its_device(lib, name):
+    """a device ordinal that does not exist: the call's code and its words behind leon_last_error(NULL) -- "<function>: no such HIP
+    device" unless the table says otherwise -- and nothing else happens"""
+    from leon_amd import capi
+    raw = ctypes.CDLL(capi.lib_path())
+    _, call, code, text = next(c for c in _no_device_calls() if c[0] == name)
+    if text is None:
+        text = name.split("[")[0] + ": no such HIP device"
+    assert call(raw) == code
+    got = _last_error(raw)
+    assert got.startswith(text) and len(got) > len(text) if text.endswith(": ") else got == text, got
+
+
+def test_device_count_without_a_device(lib):
+    """leon_device_count: LEON_E_NO_DEVICE and its words where no device answers, the devices' number where one does"""
+    import torch
+    from leon_amd import capi
+    raw = ctypes.CDLL(capi.lib_path())
+    n = ctypes.c_int(-1)
+    rc = raw.leon_device_count(ctypes.byref(n))
+    if torch.cuda.is_available():
+        assert rc == 0 and n.value >= 1
+    else:
+        assert (rc, n.value, _last_error(raw)) == (-2, 0, "no usable HIP device")
