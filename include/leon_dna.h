@@ -513,6 +513,58 @@ int leon_bgzf_inflate_device(int device_id, const uint8_t* bytes, uint64_t n_byt
 int leon_host_pinned_alloc(int device_id, uint64_t bytes, void** ptr);
 void leon_host_pinned_free(void* ptr);
 
+/* -- FASTQ text split into records --
+ * The text begins at a record start.  Lines end at '\n'; one '\r' directly in front of the '\n' is dropped, a '\r' anywhere else is
+ * kept; with last != 0 the end of the text ends a line that has no '\n' (that line keeps a '\r' at its end).  Lines are taken in fours
+ * from the start of the text: record r is lines 4r .. 4r + 3, and WHOLE when all four are there.  A whole record is REGULAR when
+ *   its first line is non-empty and begins with '@'                                   (else LEON_FASTQ_R_HEADER),
+ *   its third line begins with '+'                                                    (else LEON_FASTQ_R_PLUS),
+ *   its second and fourth lines have the same length, 0 allowed                       (else LEON_FASTQ_R_LENGTH),
+ *   its '+' line agrees with plus_kind                                                (else LEON_FASTQ_R_PLUS_TEXT):
+ *     0: it is bare; 1: it repeats the header (the first line without its '@'); -1: the '+' lines of the split records are all the
+ *     same one of the two.  A bare '+' under an empty header agrees with both and is counted in neither of plus_bare and plus_header;
+ *     any other text after the '+' agrees with nothing.
+ * The rules are tried in this order; `reason` is the first that record n_records broke.
+ * The call splits the longest prefix of records that are whole, regular and at most max_records, nothing after it: the headers without
+ * their '@', the second lines (bases) and the fourth lines (qualities), each back to back, header_off[n_records + 1] and
+ * base_off[n_records + 1] beginning with 0 (the qualities share the bases' offsets).  `consumed`: the first byte not taken.  `stop`:
+ *   LEON_FASTQ_MAX        n_records == max_records;
+ *   LEON_FASTQ_IRREGULAR  record n_records is whole and not regular -- or, with last != 0, fewer than four lines are left behind the
+ *                         split records and one of them is not empty (LEON_FASTQ_R_PARTIAL): the caller's parser is its judge;
+ *   LEON_FASTQ_END        the text ran out: what is left is no whole record, or nothing.  With last != 0 the lines left (fewer than
+ *                         four, all empty) are consumed: consumed == n_text.
+ * bytes_cap: the room of each of the three blobs; records_cap: the entries of each offset table.  LEON_E_OVERFLOW when header_bytes or
+ * base_bytes is above bytes_cap or n_records + 1 above records_cap (the result says what is needed; what the blobs and tables hold is not defined then, their ends are respected): a
+ * caller with bytes_cap >= n_text and records_cap >= n_text / 4 + 2 never sees it.  LEON_E_INVALID: null pointers, n_text >= 2^32, a
+ * plus_kind outside -1 .. 1.  Whatever else the text holds is data, never an error.
+ * The device form (fastq_kernels.hip: k_fq_newlines, k_fq_check, k_fq_split) takes every pointer but `res` in DEVICE memory, no
+ * alignment asked, works on a stream of its own and is complete on return; nothing outside the text is read, nothing behind
+ * header_bytes / base_bytes / n_records + 1 entries is written.  The host form is the same contract in plain serial code (host_fastq.h)
+ * and needs no GPU.  Errors: leon_last_error(NULL). */
+#define LEON_FASTQ_MAX 0u
+#define LEON_FASTQ_END 1u
+#define LEON_FASTQ_IRREGULAR 2u
+#define LEON_FASTQ_R_NONE 0u
+#define LEON_FASTQ_R_HEADER 1u
+#define LEON_FASTQ_R_PLUS 2u
+#define LEON_FASTQ_R_LENGTH 3u
+#define LEON_FASTQ_R_PLUS_TEXT 4u
+#define LEON_FASTQ_R_PARTIAL 5u
+typedef struct leon_fastq_split_result {
+    uint64_t n_records;      /* records 0 .. n_records-1 were split */
+    uint64_t consumed;       /* bytes of text they occupy: record n_records begins at text[consumed] */
+    uint64_t header_bytes, base_bytes;      /* quality bytes == base_bytes */
+    uint32_t stop;           /* LEON_FASTQ_MAX, LEON_FASTQ_END or LEON_FASTQ_IRREGULAR */
+    uint32_t reason;         /* under LEON_FASTQ_IRREGULAR: the LEON_FASTQ_R_* rule record n_records broke; else LEON_FASTQ_R_NONE */
+    uint64_t plus_bare, plus_header;        /* among the split records: '+' lines that are bare / repeat the header, headers non-empty */
+} leon_fastq_split_result;
+int leon_fastq_split_device(int device_id, const uint8_t* d_text, uint64_t n_text, int last, uint64_t max_records, int plus_kind,
+                            uint8_t* d_headers, uint64_t* d_header_off, uint8_t* d_bases, uint64_t* d_base_off, uint8_t* d_quals,
+                            uint64_t bytes_cap, uint64_t records_cap, leon_fastq_split_result* res);
+int leon_host_fastq_split(const uint8_t* text, uint64_t n_text, int last, uint64_t max_records, int plus_kind, uint8_t* headers,
+                          uint64_t* header_off, uint8_t* bases, uint64_t* base_off, uint8_t* quals, uint64_t bytes_cap, uint64_t records_cap,
+                          leon_fastq_split_result* res);
+
 /* -- every sequence letter kept: lower-case runs and bytes outside ACGTN --
  * For the n_bytes bases at d_bases (the reads' bases one after another): a RUN is a maximal interval [begin, end) of bytes in
  * 'a'..'z'; an ODD byte is one that, folded to upper case when it is lower-case, is none of A C G T N; the FOLDED buffer holds the

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "host_bgzf.h"
+#include "host_fastq.h"
 
 namespace leon { void set_create_error(const std::string& msg); }
 
@@ -617,4 +618,18 @@ int leon_host_bgzf_record_cuts(const uint64_t* rec_off, uint64_t n_records, uint
     if (n > 3 * (n_text / W) + 2) return fail(LEON_E_OVERFLOW, "bgzf records: more members than the bound allows");
     if (begin && n > cap) return fail(LEON_E_OVERFLOW, "bgzf records: the member table needs " + std::to_string(n) + " entries");
     return LEON_OK;
+}
+
+// ---- FASTQ text split into records: the host form of leon_fastq_split_device, the loop itself in host_fastq.h ----
+extern "C"
+int leon_host_fastq_split(const uint8_t* text, uint64_t n_text, int last, uint64_t max_records, int plus_kind, uint8_t* headers,
+                          uint64_t* header_off, uint8_t* bases, uint64_t* base_off, uint8_t* quals, uint64_t bytes_cap, uint64_t records_cap,
+                          leon_fastq_split_result* res) {
+    if (const char* why = leon::fastq_split_refusal(text, n_text, plus_kind, headers, header_off, bases, base_off, quals, res))
+        return fail(LEON_E_INVALID, std::string("leon_host_fastq_split: ") + why);
+    const int rc = leon::fastq_split(text, n_text, last, max_records, plus_kind, headers, header_off, bases, base_off, quals, bytes_cap, records_cap, res);
+    if (rc == LEON_E_OVERFLOW)
+        return fail(rc, "leon_host_fastq_split: " + std::to_string(res->n_records) + " records need " + std::to_string(res->header_bytes) + " header bytes, " +
+                            std::to_string(res->base_bytes) + " bases and " + std::to_string(res->n_records + 1) + " table entries");
+    return rc;
 }

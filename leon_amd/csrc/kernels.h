@@ -207,6 +207,10 @@ void launch_crc32_segments(hipStream_t s, const uint8_t* bytes, const uint64_t* 
 // ---- lower-case runs and bytes outside ACGTN of a device buffer (letters_kernels.hip), DESIGN.md 4.12 ----
 constexpr uint64_t LETTERS_MAX_GROUPS = 2048;                  // the grid's cap: a workgroup walks ceil(tiles / cap) consecutive 4 KiB tiles
 
+// ---- FASTQ text split into records (fastq_kernels.hip), DESIGN.md 4.16 ----
+constexpr uint32_t FASTQ_TILE = 4096;                          // bytes of text (cut at 16-byte aligned addresses) a workgroup of k_fq_newlines takes at a time
+constexpr uint64_t FASTQ_MAX_GROUPS = 1024;                    // the grid's cap: a workgroup walks ceil(tiles / cap) consecutive tiles
+
 // ---- the anchor dictionary in independently coded pieces (dict_kernels.hip), DESIGN.md 4.4 ----
 constexpr uint32_t DICT_PIECES_MAX_GROUPS = 1024;              // the grid's cap: a wave codes 64 pieces (lane = piece), then the 64 a grid further on
 // the pieces of d_kmers coded on stream s into d_dst, piece_off (host, n_pieces + 1 entries) where each begins: leon_dna_finish (capi.hip)

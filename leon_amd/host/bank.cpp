@@ -80,6 +80,7 @@ struct Bank::BgzfSource {
     std::future<uint64_t> inflight;                              // the bytes of text in pinned[turn]; 0: the end of the file
     int turn = 0;
     bool started = false, done = false;
+    std::function<uint8_t*(uint64_t)> place;                     // set: produce() leaves the text at place(its size), device memory, and downloads nothing
 
     ~BgzfSource() {
         if (inflight.valid()) { try { inflight.get(); } catch (...) {} }
@@ -125,20 +126,26 @@ struct Bank::BgzfSource {
                 if (!n_members) throw Exception(fail_later);
             }
             if (!n_members) continue;                            // (LEON_BGZF_PARTIAL: the chunk is smaller than its first member -- more of the file)
-            if (n_text > d_cap) {
-                leon_device_free(d_text); d_text = nullptr; d_cap = 0;
-                const uint64_t want = n_text + n_text / 8 + 64;
-                if (leon_device_alloc(device, want, &d_text) != LEON_OK) throw Exception(std::string("leon_device_alloc: ") + leon_last_error(nullptr));
-                d_cap = want;
-            }
-            if (n_text > pinned_cap[t]) {
-                leon_host_pinned_free(pinned[t]); pinned[t] = nullptr; pinned_cap[t] = 0;
-                const uint64_t want = n_text + n_text / 8 + 64;
-                if (leon_host_pinned_alloc(device, want, &pinned[t]) != LEON_OK) throw Exception(std::string("leon_host_pinned_alloc: ") + leon_last_error(nullptr));
-                pinned_cap[t] = want;
+            uint8_t* dst = nullptr;
+            uint64_t dst_cap = n_text;
+            if (place) dst = place(n_text);                      // (the device reader: the text stays where it asks for it)
+            else {
+                if (n_text > d_cap) {
+                    leon_device_free(d_text); d_text = nullptr; d_cap = 0;
+                    const uint64_t want = n_text + n_text / 8 + 64;
+                    if (leon_device_alloc(device, want, &d_text) != LEON_OK) throw Exception(std::string("leon_device_alloc: ") + leon_last_error(nullptr));
+                    d_cap = want;
+                }
+                if (n_text > pinned_cap[t]) {
+                    leon_host_pinned_free(pinned[t]); pinned[t] = nullptr; pinned_cap[t] = 0;
+                    const uint64_t want = n_text + n_text / 8 + 64;
+                    if (leon_host_pinned_alloc(device, want, &pinned[t]) != LEON_OK) throw Exception(std::string("leon_host_pinned_alloc: ") + leon_last_error(nullptr));
+                    pinned_cap[t] = want;
+                }
+                dst = static_cast<uint8_t*>(d_text); dst_cap = d_cap;
             }
             uint64_t got_text = 0;
-            const int rc = leon_bgzf_inflate_device(device, comp.data(), consumed, member_off.data(), n_members, static_cast<uint8_t*>(d_text), d_cap, &got_text, 0, nullptr);
+            const int rc = leon_bgzf_inflate_device(device, comp.data(), consumed, member_off.data(), n_members, dst, dst_cap, &got_text, 0, nullptr);
             if (rc == LEON_E_INVALID) {
                 // the call counts members and bytes from the chunk's first: said here as they lie in the file (the host way has zlib's words)
                 const std::string why = leon_last_error(nullptr);
@@ -149,7 +156,7 @@ struct Bank::BgzfSource {
             }
             if (rc != LEON_OK) throw Exception(std::string("leon_bgzf_inflate_device: ") + leon_last_error(nullptr));
             // (pieces below the size at which the download is staged: straight into the pinned buffer)
-            for (uint64_t a = 0; a < got_text; a += 32ull << 20) {
+            for (uint64_t a = 0; !place && a < got_text; a += 32ull << 20) {
                 const uint64_t m = std::min<uint64_t>(32ull << 20, got_text - a);
                 if (leon_device_download(device, static_cast<char*>(pinned[t]) + a, static_cast<const char*>(d_text) + a, m) != LEON_OK)
                     throw Exception(std::string("leon_device_download: ") + leon_last_error(nullptr));
@@ -213,11 +220,40 @@ Bank::Bank(const std::string& path, int inflate_device, bool verbose) : path_(pa
         gzbuffer((gzFile)gz_, 1 << 20);
     }
 }
+Bank::Bank(const std::string& path, Memory) : memory_(true), path_(path), decided_(true), fastq_(true) {}
+
+BgzfDeviceText::BgzfDeviceText(const std::string& path, int device) : src_(new Bank::BgzfSource()) {
+    src_->path = path; src_->device = device;
+    src_->fd = ::open(path.c_str(), O_RDONLY);
+    if (src_->fd < 0) { delete src_; throw Exception("cannot open " + path); }
+    if (const char* e = getenv("LEON_INPUT_CHUNK_KB")) { const long long kb = atoll(e); if (kb >= 1 && kb <= (4ll << 20)) src_->chunk_bytes = (uint64_t)kb << 10; }
+}
+BgzfDeviceText::~BgzfDeviceText() { delete src_; }
+uint64_t BgzfDeviceText::next(const std::function<uint8_t*(uint64_t)>& place) {
+    src_->place = place;
+    return src_->produce(0);
+}
+void Bank::dropSource() {
+    delete bz_; bz_ = nullptr;
+    if (gz_) gzclose((gzFile)gz_);
+    gz_ = nullptr;
+    if (fd_ >= 0) ::close(fd_);
+    fd_ = -1;
+    std::vector<char>().swap(buf_);
+    data_ = nullptr; buf_pos_ = buf_len_ = 0;
+    memory_ = true; more_ = nullptr;                             // (a read from here on finds the end of the text)
+}
 Bank::~Bank() { delete bz_; if (gz_) gzclose((gzFile)gz_); if (fd_ >= 0) ::close(fd_); }
 
 // the next piece of the file's text behind data_ (buf_pos_ = 0, buf_len_ its size); false at the end of the file
 bool Bank::refill() {
     long got;
+    if (memory_) {
+        const char* p = nullptr; size_t n = 0;
+        if (!more_ || !more_(p, n)) return false;
+        data_ = p; buf_pos_ = 0; buf_len_ = n;
+        return true;
+    }
     if (bz_) {
         const char* p = nullptr;
         const uint64_t n = bz_->next(p);

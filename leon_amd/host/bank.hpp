@@ -4,6 +4,7 @@
 // so the host never holds more than one batch of it.
 #pragma once
 #include <stdint.h>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -22,6 +23,21 @@ public:
     // throws leon_host::Exception when the file cannot be opened.  inflate_device >= 0 (`-c -input-inflate device`): a BGZF file is
     // inflated by that device, chunk by chunk; any other file is read as without it, and `verbose` says so in one line
     explicit Bank(const std::string& path, int inflate_device = -1, bool verbose = false);
+    // A FASTQ parser over text the caller hands over piece by piece (the device reader's hand-offs): no file is opened,
+    // `path` is for the messages.  attach() serves [p, p + n), then the pieces `more` gives (false: the end of the file); position() is
+    // how much of the piece being served has been taken; skipped(n): n reads the caller split itself, their '+' lines of the default
+    // kind -- the read counter and the '+'-line table stay what they would be had next() read those records too.
+    struct Memory {};
+    typedef std::function<bool(const char*&, size_t&)> More;
+    Bank(const std::string& path, Memory);
+    void attach(const char* p, size_t n, More more) { data_ = p; buf_pos_ = 0; buf_len_ = n; more_ = std::move(more); }
+    size_t position() const { return buf_pos_; }
+    void skipped(uint64_t n) { n_read_ += n; }
+    uint64_t readsSoFar() const { return n_read_; }
+    int plusDefault() const { return plus_default_; }             // 0 bare, 1 the header again; -1: no record seen yet
+    bool inflatesOnDevice() const { return bz_ != nullptr; }      // a BGZF file under `-input-inflate device`
+    bool isGzip() const { return gz_ != nullptr; }                // gzip input inflated by zlib on the reader's thread
+    void dropSource();                                            // the file is read by someone else from here on: closes it, gives its buffers up
     ~Bank();
     Bank(const Bank&) = delete;
     Bank& operator=(const Bank&) = delete;
@@ -36,11 +52,14 @@ public:
     // has a bare "+" (the usual case; nothing is stored then).  Valid once the whole file has been read.
     std::string plusLines() const;
 private:
+    friend class BgzfDeviceText;
     bool getline(std::string& line);
     bool view(const char*& p, size_t& n);         // the next line where it lies (in the read buffer when it ends there), else assembled in spill_
     bool refill();                                // the next piece of the text behind data_; false at the end of the file
     struct BgzfSource;                            // BGZF input inflated on the device: chunks of the file, one in flight while the previous is parsed
     BgzfSource* bz_ = nullptr;
+    bool memory_ = false;                         // Bank(path, Memory): refill() asks more_
+    More more_;
     void* gz_ = nullptr;                          // gzFile (gzip input)
     int fd_ = -1;                                 // plain input: read(2) straight into buf_ (zlib's transparent mode copies every byte once more)
     std::string path_, pending_, spill_;
@@ -55,6 +74,21 @@ private:
     int plus_default_ = -1;                       // kind of the first record's '+' line (0 bare, 1 repeats the header); -1: none seen
     std::string plus_exc_;                        // the records that differ from it: varint(read index delta), kind, [varint(length), text]
     uint64_t plus_prev_ = 0;
+};
+
+// The text of a BGZF file chunk by chunk (LEON_INPUT_CHUNK_KB of the file at a time), inflated on the device and LEFT there: what
+// `-c -input-inflate device` reads through Bank, without the download (the device reader of `-record-parse device`).
+// The messages are the ones Bank gives for the same file.
+class BgzfDeviceText {
+public:
+    BgzfDeviceText(const std::string& path, int device);
+    ~BgzfDeviceText();
+    BgzfDeviceText(const BgzfDeviceText&) = delete;
+    BgzfDeviceText& operator=(const BgzfDeviceText&) = delete;
+    // the next chunk's text at place(its size), device memory with room for it; returns the size, 0 at the end of the file
+    uint64_t next(const std::function<uint8_t*(uint64_t)>& place);
+private:
+    Bank::BgzfSource* src_;
 };
 
 // The '+' lines of a FASTQ file (third line of a record): bare, or the header again (older Illumina / SRA dumps), or -- never

@@ -9,6 +9,7 @@
 #include "leon_internal.hpp"
 
 #include "bank.hpp"
+#include "fastq_reader.hpp"
 
 #include <zlib.h>
 
@@ -96,6 +97,11 @@ struct ResidentReads {
         check(nullptr, leon_device_upload(device, d_bases() + n_bases, text.data(), text.size()), "leon_device_upload");
         n_bases += text.size();
     }
+    void append_device(const void* d_text, uint64_t n) {        // from memory of the same device
+        reserve(n_bases + n);
+        if (n) check(nullptr, leon_device_copy(device, d_bases() + n_bases, d_text, n), "leon_device_copy");
+        n_bases += n;
+    }
     void set_offsets(const std::vector<uint64_t>& offsets) {
         off.alloc(device, offsets.size() * 8);
         check(nullptr, leon_device_upload(device, off.get(), offsets.data(), offsets.size() * 8), "leon_device_upload");
@@ -127,10 +133,11 @@ struct Compressor {
     const std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
     const uint32_t k, rpb = Leon::READ_PER_BLOCK, cores;
     const int n_gpus;
-    const uint64_t batch_reads = 64ull * rpb;
+    uint64_t batch_reads = 64ull * rpb;                         // a batch of the pass over the file: LEON_BATCH_BLOCKS (test aid) blocks, 64 by default
     Choice qual_enc = Choice::Host;
     const bool checksum;
     Bank bank;
+    std::unique_ptr<FastqDeviceReader> dreader;                  // `-record-parse device`: the records are split on the device
     bool fastq = false, keep_header = false, keep_qual = false;
     std::string tmp_name;                                        // renamed at the very end: a failed run leaves no .leon behind
     struct TmpGuard { std::string p; bool keep = false; ~TmpGuard() { if (!keep) std::remove(p.c_str()); } } guard;
@@ -144,6 +151,7 @@ struct Compressor {
     // second pass over the file feeds them through.
     std::unique_ptr<ResidentReads> qstore;
     bool qstore_used = false;
+    uint64_t qual_resident_max = 0;
     std::vector<uint64_t> offsets{0};                            // base offsets of every read, absolute in the resident copy
     std::string first_header;
     uint64_t n_reads = 0, n_blocks = 0, n_bases = 0, header_bytes = 0, qual_bytes = 0;
@@ -151,6 +159,7 @@ struct Compressor {
     bool qual_on_device = false;
     ScratchMem d_qbuf;                                        // a batch's qualities on the device, for its deflate or smoothing (one job at a time uses it)
     ReadBatch buffers[2];
+    DeviceBatch dbuffers[2];                                     // ... their twins under `-record-parse device`
     double w_reader = 0, w_headers = 0, w_quals = 0, w_uploads = 0;   // where the pass's own thread spent its time (-verbose)
     // `-checksum`: a CRC-32 per read block and stream (leon/metadata/checksums), each taken where the bytes lie
     std::vector<uint32_t> sum_dna, sum_hdr, sum_qual;            // per block; the jobs of a batch fill their blocks' words
@@ -174,6 +183,10 @@ struct Compressor {
     explicit Compressor(Leon& leon);
     void run();
     void pass_over_file();
+    void begin_pass();
+    void pass_over_device_batches();
+    void end_pass();
+    void start_lossless_quals_device(const DeviceBatch& batch, uint64_t got, uint64_t block0);
     void start_header_sums(const ReadBatch& batch, uint64_t got, uint64_t block0);
     void start_lossless_quals(const ReadBatch& batch, uint64_t got, uint64_t block0);
     void take_letters();
@@ -194,6 +207,7 @@ Compressor::Compressor(Leon& leon)
       checksum(leon._checksum), bank(leon._inputFilename, input_inflate_device(leon._inputInflate, leon._inputFilename), leon._verbose) {
     fastq = bank.isFastq();
     keep_header = !o._noHeader; keep_qual = fastq && !o._noQual;
+    if (const char* e = getenv("LEON_BATCH_BLOCKS")) { const long v = atol(e); if (v > 0) batch_reads = (uint64_t)v * rpb; }   // (tests: several batches on a small file)
     // X.fastq.gz -> X.fastq.leon, data/toy.fasta -> data/toy.fasta.leon (/root/reference/scripts/simple_test.sh:51,54, INSTALL:21-23)
     std::string stem = o._inputFilename;
     if (ends_with(stem, ".gz")) stem.resize(stem.size() - 3);
@@ -206,6 +220,16 @@ Compressor::Compressor(Leon& leon)
     wd.in_order = n_gpus > 1;
     for (int g = 0; g < n_gpus; g++) { store.emplace_back(new ResidentReads()); store.back()->device = device_for(g); }
     dev0 = store[0]->device;
+    if (record_parse_on_device(o._recordParse)) {
+        const char* host_why = !fastq ? "FASTA input" : bank.isGzip() ? "gzip input that is not inflated on the device" : nullptr;
+        if (!host_why) {
+            const bool bgzf = bank.inflatesOnDevice();
+            bank.dropSource();                                   // (it has said what the file is; the device reader reads it from its first byte)
+            dreader.reset(new FastqDeviceReader(o._inputFilename, dev0, bgzf, o._verbose));
+        }
+        if (o._verbose && host_why) std::cout << "parse: records cut on the host (" << host_why << ")" << std::endl;
+        if (o._verbose && !host_why) std::cout << "parse: records split on the device (k_fq_split), spans of " << dreader->spanBytes() << " bytes" << std::endl;
+    }
 }
 
 void Compressor::run() {
@@ -253,14 +277,19 @@ void Compressor::start_lossless_quals(const ReadBatch& batch, uint64_t got, uint
     });
 }
 
-void Compressor::pass_over_file() {
-    CtxPtr hdr_ctx;
-    if (keep_header) hdr_ctx = make_ctx(k, 1000, dev0);
+void Compressor::begin_pass() {
     qual_enc = qual_encoder_choice(o._qualDeflate);
-    uint64_t qual_resident_max = 64ull << 30;
+    qual_resident_max = 64ull << 30;
     if (const char* e = getenv("LEON_QUAL_RESIDENT_MB")) qual_resident_max = (uint64_t)std::max<long long>(0, atoll(e)) << 20;
     if (fastq && !o._noQual && !o._lossless && qual_resident_max) { qstore.reset(new ResidentReads()); qstore->device = dev0; }
     qstore_used = qstore != nullptr;
+}
+
+void Compressor::pass_over_file() {
+    begin_pass();
+    if (dreader) { pass_over_device_batches(); end_pass(); return; }
+    CtxPtr hdr_ctx;
+    if (keep_header) hdr_ctx = make_ctx(k, 1000, dev0);
     // the reader runs one batch ahead on its own thread: batch i + 1 is parsed while batch i's headers are coded on the device
     // and its bases (and qualities) cross to it
     Bank* const reader = &bank;
@@ -310,6 +339,11 @@ void Compressor::pass_over_file() {
         n_reads += got;
         if (got < batch_reads) break;                            // the partial batch is the last one
     }
+    hdr_ctx.reset();
+    end_pass();
+}
+
+void Compressor::end_pass() {
     if (qual_job.valid()) qual_job.get();
     if (hdr_sum_job.valid()) hdr_sum_job.get();
     n_blocks = (n_reads + rpb - 1) / rpb; n_bases = offsets.back();
@@ -321,8 +355,99 @@ void Compressor::pass_over_file() {
         sums_on_device(dev0, store[0]->d_bases(), n_bases, file_block_off.data(), n_blocks, sum_dna.data());
     }
     if (o._letters) take_letters();
-    hdr_ctx.reset();
     t_parse = seconds_since(t_start);
+}
+
+// `-record-parse device`: the same pass over batches the device reader leaves in device memory (fastq_reader.hpp).  The offsets are
+// on the host; headers, bases and qualities go from device memory to where the host route uploads them.
+void Compressor::pass_over_device_batches() {
+    CtxPtr hdr_ctx;
+    if (keep_header) hdr_ctx = make_ctx(k, 1000, dev0);
+    FastqDeviceReader* const reader = dreader.get();
+    const uint64_t want = batch_reads;
+    auto parse_next = [reader, want](DeviceBatch* b) -> uint64_t { return reader->next(*b, want); };
+    std::future<uint64_t> parsing = std::async(std::launch::async, parse_next, &dbuffers[0]);
+    struct ParseJoin { std::future<uint64_t>& f; ~ParseJoin() { if (f.valid()) { try { f.get(); } catch (...) {} } } } parse_join{parsing};
+    ScratchMem d_header_off;
+    std::string host_bases;
+    for (uint32_t cur = 0;; cur ^= 1) {
+        auto t_w = std::chrono::steady_clock::now();
+        const uint64_t got = parsing.get();                      // (the reader's exceptions surface here)
+        w_reader += seconds_since(t_w);
+        if (!got) break;
+        DeviceBatch& batch = dbuffers[cur];
+        t_w = std::chrono::steady_clock::now();
+        if (qual_job.valid()) qual_job.get();                    // (it reads this buffer's twin in place, as on the host route)
+        w_quals += seconds_since(t_w);
+        if (got == batch_reads) parsing = std::async(std::launch::async, parse_next, &dbuffers[cur ^ 1]);
+        if (n_reads == 0) first_header = reader->firstHeader();
+        const uint64_t batch_blocks_n = (got + rpb - 1) / rpb, batch_block0 = n_reads / rpb;
+        if (checksum) { sum_hdr.resize(batch_block0 + batch_blocks_n, 0); sum_qual.resize(batch_block0 + batch_blocks_n, 0); }
+        t_w = std::chrono::steady_clock::now();
+        if (keep_header) {
+            if (checksum && batch.header_bytes) {
+                const std::vector<uint64_t> boff = block_offsets(batch.header_off.data(), got, rpb);
+                sums_on_device(dev0, batch.headers.get(), batch.header_bytes, boff.data(), boff.size() - 1, sum_hdr.data() + batch_block0);
+            }
+            uint64_t* const d_off = static_cast<uint64_t*>(d_header_off.fit(dev0, (got + 1) * 8));
+            check(nullptr, leon_device_upload(dev0, d_off, batch.header_off.data(), (got + 1) * 8), "leon_device_upload");
+            batch.reserve(1, 1);                                 // (a batch of empty headers has no blob yet)
+            check_sink(hdr_ctx.get(), leon_header_encode_batch_device(hdr_ctx.get(), batch.headers.as<uint8_t>(), d_off, got, n_reads, reinterpret_cast<const uint8_t*>(first_header.data()),
+                                                                      first_header.size(), StreamWriter::sink, &wh),
+                       wh, "leon_header_encode_batch_device");
+            header_bytes += batch.header_bytes;
+            for (uint64_t r = 0; r < got; r += rpb) hdr_text.push_back(batch.header_off[std::min<uint64_t>(got, r + rpb)] - batch.header_off[r]);
+        }
+        w_headers += seconds_since(t_w);
+        qual_bytes += batch.base_bytes;
+        t_w = std::chrono::steady_clock::now();
+        if (keep_qual && o._lossless) start_lossless_quals_device(batch, got, batch_block0);
+        w_quals += seconds_since(t_w);
+        t_w = std::chrono::steady_clock::now();
+        bool have_host_bases = false;
+        for (auto& st : store) {
+            if (st->device == dev0) { st->append_device(batch.bases.get(), batch.base_bytes); continue; }
+            if (!have_host_bases) {                              // the other devices get them through the host
+                have_host_bases = true;
+                host_bases.resize(batch.base_bytes);
+                if (batch.base_bytes) check(nullptr, leon_device_download(dev0, &host_bases[0], batch.bases.get(), batch.base_bytes), "leon_device_download");
+            }
+            st->append(host_bases);
+        }
+        if (qstore) {
+            try { qstore->append_device(batch.quals.get(), batch.base_bytes); }
+            catch (const Exception&) { qstore.reset(); }
+            if (qstore && qstore->n_bases > qual_resident_max) qstore.reset();
+        }
+        for (uint64_t i = 1; i <= got; i++) offsets.push_back(offsets[n_reads] + batch.base_off[i]);
+        w_uploads += seconds_since(t_w);
+        n_reads += got;
+        if (got < batch_reads) break;
+    }
+}
+
+// `-lossless` under `-record-parse device`: the batch's quality blocks from its device buffer -- deflated there, or downloaded once for
+// zlib on the host threads
+void Compressor::start_lossless_quals_device(const DeviceBatch& batch, uint64_t got, uint64_t block0) {
+    if (n_reads == 0) {                                          // the sample the host route takes: reads up to 256 KB of lines
+        uint64_t n = 0;
+        while (n < got && batch.base_off[n] + n < (256u << 10)) n++;
+        pick_qual_encoder_on_device(batch.quals.get(), batch.base_off.data(), n);
+    }
+    const DeviceBatch* b = &batch;
+    uint32_t* sums = checksum ? sum_qual.data() + block0 : nullptr;
+    qual_job = std::async(std::launch::async, [this, b, got, block0, sums] {
+        const std::vector<uint64_t> boff = sums ? block_offsets(b->base_off.data(), got, Leon::READ_PER_BLOCK) : std::vector<uint64_t>();
+        if (qual_on_device) {
+            if (sums) sums_on_device(dev0, b->quals.get(), b->base_bytes, boff.data(), boff.size() - 1, sums);
+            deflate_blocks(b->quals.as<uint8_t>(), nullptr, b->base_off.data(), got, block0);
+            return;
+        }
+        std::string quals(b->base_bytes, '\0');
+        if (b->base_bytes) check(nullptr, leon_device_download(dev0, &quals[0], b->quals.get(), b->base_bytes), "leon_device_download");
+        if (sums) sums_on_host(quals.data(), quals.size(), boff.data(), boff.size() - 1, cores, sums);
+        deflate_blocks(nullptr, quals.data(), b->base_off.data(), got, block0);
+    });
 }
 
 // `-letters`: lower-case runs and bytes outside ACGTN out of every device's resident copy, which is folded to what the coder carries
@@ -524,7 +649,7 @@ void Compressor::write_tables() {
         out->putU64(DS_QUAL_TABLE, table.data(), table.size());
     }
     if (fastq && keep_header && keep_qual) {                     // '+' lines that repeat the header (or carry text): `diff` sees them (simple_test.sh:62)
-        const std::string plus = bank.plusLines();
+        const std::string plus = dreader ? dreader->parser().plusLines() : bank.plusLines();
         if (!plus.empty()) out->putBytes(DS_PLUS_LINES, plus.data(), plus.size());
     }
     if (checksum) {                                              // kind, then per block: dna, header, quality (0 for a stream the file does not have)
@@ -577,6 +702,7 @@ void Compressor::report() {
         if (has_letters()) std::cout << "letters: " << letter_runs.size() / 2 << " lower-case run(s), " << letter_odd_pos.size() << " other byte(s) kept (" << letter_table_bytes << " bytes)\n";
         else std::cout << "letters: none\n";
     }
+    if (o._verbose && dreader) dreader->report();
     if (o._verbose)
         std::cout << "time: parse + headers" << (keep_qual && o._lossless ? " + qualities " : " ") << t_parse << " s, k-mer counting " << t_kmers << " s, contexts + bloom "
                   << t_bloom - t_kmers << " s, DNA encode " << t_encode << " s, total " << seconds_since(t_start) << " s\n"

@@ -56,6 +56,7 @@ public:
     bool _gzIndex = false;                // -d -gz: -gz-index: X.d.gz.gzi beside the file, every member's offset in the file and in the text
     std::string _qualDeflate;             // -qual-deflate host|device|auto; empty = not given: zlib on the host threads (the reference's bytes)
     std::string _inputInflate;            // -c: -input-inflate host|device|auto; empty = not given: a gzip input inflated by zlib on the reader's thread
+    std::string _recordParse;             // -c: -record-parse host|device; empty = not given: the FASTQ records cut by the reader's thread on the host
     std::string _headerText;              // -d: -header-text host|device|auto; empty = not given: the header text on the host threads
     std::string _recordText;              // -d: -record-text host|device|auto; empty = not given: the records formatted on the host threads
     std::string _qualInflate;             // -d: -qual-inflate host|device|auto; empty = not given: the quality blocks inflated by zlib on the host threads

@@ -82,6 +82,12 @@ inline Choice parse_choice(const char* flag_name, const std::string& value) {
 inline bool device_chosen(Choice c, uint64_t n_blocks, uint64_t auto_blocks) {
     return c == Choice::Device || (c == Choice::Auto && n_blocks >= auto_blocks);
 }
+// `-c -record-parse host|device`: who cuts the FASTQ text into records; no `auto`
+inline bool record_parse_on_device(const std::string& value) {
+    if (value.empty() || value == "host") return false;
+    if (value == "device") return true;
+    throw Exception("option -record-parse: '" + value + "': expected host or device");
+}
 // `-c -input-inflate`: which device inflates a BGZF input (k_bgzf_inflate), or -1: the file is read on the host, as
 // without the option.  `auto` chooses the device for files of at least kInputInflateAutoBytes (DESIGN.md 8 has the runs behind it);
 // LEON_INPUT_INFLATE_AUTO_KB in the environment overrides that size, so that a test's small file takes the device way under `auto`.
