@@ -16,7 +16,21 @@ struct ReadBatch {
     std::vector<uint64_t> base_off{0}, header_off{0}, qual_off{0};
     uint64_t size() const { return base_off.size() - 1; }
     void clear() { bases.clear(); headers.clear(); quals.clear(); base_off.assign(1, 0); header_off.assign(1, 0); qual_off.assign(1, 0); }
+    struct BatchView view() const;
 };
+
+// Where a batch lies, for whoever consumes it (`leon -c`'s pass, leon_compress.cpp): every blob in host memory, in device memory, or
+// both; the offsets (n + 1 each, from 0) on the host either way.  A ReadBatch gives `host`, a DeviceBatch (fastq_reader.hpp) `dev`.
+struct Blob { const char* host = nullptr; const void* dev = nullptr; uint64_t bytes = 0; };
+struct BatchView {
+    Blob headers, bases, quals;
+    const uint64_t* header_off = nullptr; const uint64_t* base_off = nullptr; const uint64_t* qual_off = nullptr;
+    uint64_t n = 0;                               // reads
+};
+inline BatchView ReadBatch::view() const {
+    return BatchView{{headers.data(), nullptr, headers.size()}, {bases.data(), nullptr, bases.size()}, {quals.data(), nullptr, quals.size()},
+                     header_off.data(), base_off.data(), qual_off.data(), size()};
+}
 
 class Bank {
 public:

@@ -176,6 +176,7 @@ void FastqDeviceReader::split(DeviceBatch& batch, uint64_t want) {
 uint64_t FastqDeviceReader::next(DeviceBatch& batch, uint64_t want) {
     batch.device = device_;
     batch.clear();
+    batch.reserve(1, 1);                                         // (every blob is there, also for a batch of empty lines)
     if (!started_) {                                             // the file's first record says which kind the '+' lines are of
         started_ = true;
         if (load()) hand_off(batch, 1, "the file's first record");

@@ -20,6 +20,10 @@ struct DeviceBatch {
     uint64_t size() const { return base_off.size() - 1; }
     void clear() { header_bytes = base_bytes = 0; header_off.assign(1, 0); base_off.assign(1, 0); }
     void reserve(uint64_t header_need, uint64_t base_need);      // what the blobs hold is kept
+    BatchView view() const {                                     // (good until the next reserve)
+        return BatchView{{nullptr, headers.get(), header_bytes}, {nullptr, bases.get(), base_bytes}, {nullptr, quals.get(), base_bytes},
+                         header_off.data(), base_off.data(), base_off.data(), size()};
+    }
 };
 
 class FastqDeviceReader {

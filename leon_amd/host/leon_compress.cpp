@@ -1,11 +1,16 @@
-// leon_compress.cpp -- `leon -c` (see leon_host.hpp).  One pass over the input (bank.hpp), batch by batch:
-//      headers  -> leon_header_encode_batch            -> leon/header/block_<i>
-//      bases    -> appended to a device-resident copy of the reads (never all of it on the host)
-//      qualities (-lossless) -> leon_host_qual_encode_blocks (zlib on host threads) -> leon/qual/block_<i>
+// leon_compress.cpp -- `leon -c` (see leon_host.hpp).  One pass over the input, batch by batch.  A batch is cut into records by the host
+// parser (bank.hpp: its blobs are in host memory) or, under `-record-parse device`, split on the device (fastq_reader.hpp: they are in
+// device memory); the pass sees a BatchView either way and every consumer takes each blob where it lies:
+//      headers  -> leon_header_encode_batch / _device  -> leon/header/block_<i>
+//      bases    -> appended to a device-resident copy of the reads per GPU (never all of it on the host)
+//      qualities, -lossless -> leon/qual/block_<i>, by the encoder `-qual-deflate` picks: zlib on the host threads
+//                 (leon_host_qual_encode_blocks) or the device's deflate (leon_qual_deflate_blocks_device)
+//      qualities, lossy (the default) -> resident on device 0 beside the bases, while they fit (LEON_QUAL_RESIDENT_MB)
+//      -checksum: a CRC-32 per block and stream, on the device or the host threads, wherever the bytes are
 //    then: solid k-mers of the resident reads (leon_kmer_solid_device, automatic threshold unless -abundance) -> bloom ->
 //      leon_dna_encode_batch_device over the resident reads -> leon/dna/block_<i>, anchor dictionary, bloom, tables;
-//      lossy qualities (the default) need the bloom: a second pass over the file smooths them on the device
-//      (leon_qual_smooth_batch_device) before the same zlib blocks.
+//      lossy qualities need the bloom: smoothed on the device (leon_qual_smooth_batch_device) where they are resident, else fed
+//      through from a second pass over the file; then the same blocks by the same encoders.
 #include "leon_internal.hpp"
 
 #include "bank.hpp"
@@ -92,15 +97,11 @@ struct ResidentReads {
         if (n_bases) check(nullptr, leon_device_copy(device, grown.get(), bases.get(), n_bases), "leon_device_copy");
         bases = std::move(grown); cap = nc;
     }
-    void append(const std::string& text) {
-        reserve(n_bases + text.size());
-        check(nullptr, leon_device_upload(device, d_bases() + n_bases, text.data(), text.size()), "leon_device_upload");
-        n_bases += text.size();
-    }
-    void append_device(const void* d_text, uint64_t n) {        // from memory of the same device
-        reserve(n_bases + n);
-        if (n) check(nullptr, leon_device_copy(device, d_bases() + n_bases, d_text, n), "leon_device_copy");
-        n_bases += n;
+    void append(const Blob& text) {                              // text.dev: memory of the same device
+        reserve(n_bases + text.bytes);
+        if (text.dev && text.bytes) check(nullptr, leon_device_copy(device, d_bases() + n_bases, text.dev, text.bytes), "leon_device_copy");
+        if (!text.dev) check(nullptr, leon_device_upload(device, d_bases() + n_bases, text.host, text.bytes), "leon_device_upload");
+        n_bases += text.bytes;
     }
     void set_offsets(const std::vector<uint64_t>& offsets) {
         off.alloc(device, offsets.size() * 8);
@@ -126,6 +127,24 @@ bool runs_are_enough(const char* quals, const uint64_t* off, uint64_t n_reads) {
     const size_t d = deflated_size(text, Z_DEFAULT_STRATEGY), r = deflated_size(text, Z_RLE);
     return d && r && (double)r <= 1.02 * (double)d;
 }
+
+// A blob's bytes in memory of `device`: where they lie, or uploaded into `room`.  On the host: where they lie, or downloaded into `room`.
+// (A blob is on `device` when it is on a device at all: the device reader splits on device 0 of the run.)
+const void* on_device(const Blob& b, int device, ScratchMem& room) {
+    if (b.dev) return b.dev;
+    void* const d = room.fit(device, b.bytes);
+    if (b.bytes) check(nullptr, leon_device_upload(device, d, b.host, b.bytes), "leon_device_upload");
+    return d;
+}
+const char* on_host(const Blob& b, int device, std::string& room) {
+    if (b.host) return b.host;
+    room.resize(b.bytes);
+    if (b.bytes) check(nullptr, leon_device_download(device, &room[0], b.dev, b.bytes), "leon_device_download");
+    return room.data();
+}
+
+// a job that runs beside the pass is never left running over what it reads
+template <class T> struct Join { std::future<T>& f; ~Join() { if (f.valid()) { try { f.get(); } catch (...) {} } } };
 
 // `-c` from the first byte read to the last line printed; the stages below run in the order of run()
 struct Compressor {
@@ -158,8 +177,9 @@ struct Compressor {
     std::vector<uint64_t> hdr_text;                              // bytes of header text per read block: the decoder sizes its buffers from it
     bool qual_on_device = false;
     ScratchMem d_qbuf;                                        // a batch's qualities on the device, for its deflate or smoothing (one job at a time uses it)
-    ReadBatch buffers[2];
-    DeviceBatch dbuffers[2];                                     // ... their twins under `-record-parse device`
+    std::string h_qbuf;                                          // ... and on the host, for zlib, when they were split on the device
+    ReadBatch buffers[2];                                        // the reader's two batches: the host parser's,
+    DeviceBatch dbuffers[2];                                     // or the device reader's
     double w_reader = 0, w_headers = 0, w_quals = 0, w_uploads = 0;   // where the pass's own thread spent its time (-verbose)
     // `-checksum`: a CRC-32 per read block and stream (leon/metadata/checksums), each taken where the bytes lie
     std::vector<uint32_t> sum_dna, sum_hdr, sum_qual;            // per block; the jobs of a batch fill their blocks' words
@@ -178,23 +198,19 @@ struct Compressor {
     // The jobs that run beside the pass read the members above (the batch buffers, d_qbuf, the writers) in place: they are the last
     // members, so they are joined before anything they read goes.
     std::future<void> qual_job, hdr_sum_job;
-    struct Join { std::future<void>& f; ~Join() { if (f.valid()) { try { f.get(); } catch (...) {} } } } join_quals{qual_job}, join_sums{hdr_sum_job};
+    Join<void> join_quals{qual_job}, join_sums{hdr_sum_job};
 
     explicit Compressor(Leon& leon);
     void run();
     void pass_over_file();
-    void begin_pass();
-    void pass_over_device_batches();
-    void end_pass();
-    void start_lossless_quals_device(const DeviceBatch& batch, uint64_t got, uint64_t block0);
-    void start_header_sums(const ReadBatch& batch, uint64_t got, uint64_t block0);
-    void start_lossless_quals(const ReadBatch& batch, uint64_t got, uint64_t block0);
+    void header_sums(const BatchView& batch, uint64_t got, uint64_t block0);
+    void start_lossless_quals(const BatchView& batch, uint64_t got, uint64_t block0);
     void take_letters();
     void kmers_and_bloom();
     void encode_dna();
-    void pick_qual_encoder(const char* sample, const uint64_t* off, uint64_t n);
-    void pick_qual_encoder_on_device(const void* d_quals, const uint64_t* off, uint64_t n);
-    void deflate_blocks(const uint8_t* d_quals, const char* h_quals, const uint64_t* off, uint64_t got, uint64_t first_block);
+    void pick_qual_encoder(const BatchView& batch, uint64_t n);
+    Blob stage_quals(const BatchView& batch, uint64_t got, uint64_t block0, std::string& room);
+    void deflate_blocks(const Blob& quals, const uint64_t* off, uint64_t got, uint64_t first_block);
     void lossy_quals_resident();
     void lossy_quals_second_pass();
     void write_tables();
@@ -243,92 +259,114 @@ void Compressor::run() {
     report();
 }
 
-// `-checksum`: the headers' words are taken on the host threads by a job of their own, beside the next batch's parsing: the pass's
-// thread is its bottleneck.  (Reads the batch's buffer in place, like qual_job: joined before the reader gets it back.)
-void Compressor::start_header_sums(const ReadBatch& batch, uint64_t got, uint64_t block0) {
-    const std::string* headers = &batch.headers;
-    const std::vector<uint64_t>* hoff = &batch.header_off;
+// `-checksum`: the headers' words.  Of headers in device memory, there; of the host parser's, on the host threads by a job of their own,
+// beside the next batch's parsing: the pass's thread is its bottleneck.  (Reads the batch's buffer in place, like qual_job: joined
+// before the reader gets it back.)
+void Compressor::header_sums(const BatchView& batch, uint64_t got, uint64_t block0) {
+    const Blob headers = batch.headers;
+    const uint64_t* const hoff = batch.header_off;
     uint32_t* sums = sum_hdr.data() + block0;
+    if (headers.dev) {                                           // (no bytes: the words stay 0, the CRC of nothing)
+        const std::vector<uint64_t> boff = block_offsets(hoff, got, rpb);
+        if (headers.bytes) sums_on_device(dev0, headers.dev, headers.bytes, boff.data(), boff.size() - 1, sums);
+        return;
+    }
     const uint32_t n_thr = cores;
     hdr_sum_job = std::async(std::launch::async, [headers, hoff, got, n_thr, sums] {
-        const std::vector<uint64_t> boff = block_offsets(hoff->data(), got, Leon::READ_PER_BLOCK);
-        sums_on_host(headers->data(), headers->size(), boff.data(), boff.size() - 1, n_thr, sums);
+        const std::vector<uint64_t> boff = block_offsets(hoff, got, Leon::READ_PER_BLOCK);
+        sums_on_host(headers.host, headers.bytes, boff.data(), boff.size() - 1, n_thr, sums);
     });
 }
 
 // `-lossless`: the batch's quality blocks, deflated while the next batch is being parsed: on the device, or on the host threads
-void Compressor::start_lossless_quals(const ReadBatch& batch, uint64_t got, uint64_t block0) {
-    if (n_reads == 0) pick_qual_encoder(batch.quals.data(), batch.qual_off.data(), got);
-    // (read in place: moving the strings out would make the reader allocate and fault in half a gigabyte per batch -- 0.23 s
-    // of every batch at 100 M reads when this path did)
-    const std::string* quals = &batch.quals;
-    const std::vector<uint64_t>* qoff = &batch.qual_off;
-    uint32_t* sums = checksum ? sum_qual.data() + block0 : nullptr;
-    qual_job = std::async(std::launch::async, [this, quals, qoff, got, block0, sums] {
-        // (`-checksum`: the file's own quality bytes -- on the device where the deflate has uploaded them, else beside compress2)
-        const std::vector<uint64_t> boff = sums ? block_offsets(qoff->data(), got, Leon::READ_PER_BLOCK) : std::vector<uint64_t>();
-        void* d_q = nullptr;
-        if (qual_on_device) {
-            d_q = d_qbuf.fit(dev0, quals->size());
-            if (!quals->empty()) check(nullptr, leon_device_upload(dev0, d_q, quals->data(), quals->size()), "leon_device_upload");
-            if (sums) sums_on_device(dev0, d_q, quals->size(), boff.data(), boff.size() - 1, sums);
-        } else if (sums) sums_on_host(quals->data(), quals->size(), boff.data(), boff.size() - 1, cores, sums);
-        deflate_blocks(static_cast<const uint8_t*>(d_q), quals->data(), qoff->data(), got, block0);
+void Compressor::start_lossless_quals(const BatchView& batch, uint64_t got, uint64_t block0) {
+    if (n_reads == 0) pick_qual_encoder(batch, got);
+    // (the host parser's are read in place: moving the strings out would make the reader allocate and fault in half a gigabyte per
+    // batch -- 0.23 s of every batch at 100 M reads when this path did)
+    qual_job = std::async(std::launch::async, [this, batch, got, block0] {
+        deflate_blocks(stage_quals(batch, got, block0, h_qbuf), batch.qual_off, got, block0);
     });
 }
 
-void Compressor::begin_pass() {
+// A batch's qualities on their way into blocks: to where the picked encoder reads them -- device memory (d_qbuf when they have to be
+// uploaded) or the host (`room` when they have to be downloaded) --, the `-checksum` words taken on the device when the bytes are or
+// have just been put there, else on the host threads.  What comes back says where the encoder finds them.
+Blob Compressor::stage_quals(const BatchView& batch, uint64_t got, uint64_t block0, std::string& room) {
+    Blob q = batch.quals;
+    if (qual_on_device) q.dev = on_device(q, dev0, d_qbuf);
+    if (checksum) {
+        const std::vector<uint64_t> boff = block_offsets(batch.qual_off, got, rpb);
+        if (q.dev) sums_on_device(dev0, q.dev, q.bytes, boff.data(), boff.size() - 1, sum_qual.data() + block0);
+        else sums_on_host(q.host, q.bytes, boff.data(), boff.size() - 1, cores, sum_qual.data() + block0);
+    }
+    if (!qual_on_device) q.host = on_host(q, dev0, room);
+    return q;
+}
+
+void Compressor::pass_over_file() {
     qual_enc = qual_encoder_choice(o._qualDeflate);
     qual_resident_max = 64ull << 30;
     if (const char* e = getenv("LEON_QUAL_RESIDENT_MB")) qual_resident_max = (uint64_t)std::max<long long>(0, atoll(e)) << 20;
     if (fastq && !o._noQual && !o._lossless && qual_resident_max) { qstore.reset(new ResidentReads()); qstore->device = dev0; }
     qstore_used = qstore != nullptr;
-}
-
-void Compressor::pass_over_file() {
-    begin_pass();
-    if (dreader) { pass_over_device_batches(); end_pass(); return; }
     CtxPtr hdr_ctx;
     if (keep_header) hdr_ctx = make_ctx(k, 1000, dev0);
     // the reader runs one batch ahead on its own thread: batch i + 1 is parsed while batch i's headers are coded on the device
-    // and its bases (and qualities) cross to it
-    Bank* const reader = &bank;
+    // and its bases (and qualities) cross to it -- or, split on the device, are copied there
     const uint64_t want = batch_reads;
-    auto parse_next = [reader, want](ReadBatch* b) -> uint64_t { b->clear(); return reader->next(*b, want); };
-    std::future<uint64_t> parsing = std::async(std::launch::async, parse_next, &buffers[0]);
-    struct ParseJoin { std::future<uint64_t>& f; ~ParseJoin() { if (f.valid()) { try { f.get(); } catch (...) {} } } } parse_join{parsing};   // (never left running over dead buffers)
+    std::function<BatchView(uint32_t)> parse_next;               // fills buffer i of the reader's kind
+    if (dreader) parse_next = [r = dreader.get(), b = dbuffers, want](uint32_t i) { r->next(b[i], want); return b[i].view(); };
+    else parse_next = [r = &bank, b = buffers, want](uint32_t i) { b[i].clear(); r->next(b[i], want); return b[i].view(); };
+    std::future<BatchView> parsing = std::async(std::launch::async, parse_next, 0u);
+    Join<BatchView> parse_join{parsing};                         // (never left running over dead buffers)
+    ScratchMem d_header_off;
+    std::string host_bases;
     for (uint32_t cur = 0;; cur ^= 1) {
         auto t_w = std::chrono::steady_clock::now();
-        const uint64_t got = parsing.get();                      // (the reader's exceptions surface here)
+        const BatchView batch = parsing.get();                   // (the reader's exceptions surface here)
+        const uint64_t got = batch.n;
         w_reader += seconds_since(t_w);
         if (!got) break;
-        ReadBatch& batch = buffers[cur];
         // the quality blocks of the batch before read this buffer's twin in place: they are done (they started a whole batch ago)
         // before the reader is allowed to fill it again
         t_w = std::chrono::steady_clock::now();
         if (qual_job.valid()) qual_job.get();
         if (hdr_sum_job.valid()) hdr_sum_job.get();
         w_quals += seconds_since(t_w);
-        if (got == batch_reads) parsing = std::async(std::launch::async, parse_next, &buffers[cur ^ 1]);
-        if (n_reads == 0) first_header.assign(batch.headers, 0, batch.header_off[1]);
+        if (got == batch_reads) parsing = std::async(std::launch::async, parse_next, cur ^ 1);
+        if (n_reads == 0) first_header = dreader ? dreader->firstHeader() : std::string(batch.headers.host, batch.header_off[1]);
         const uint64_t batch_blocks_n = (got + rpb - 1) / rpb, batch_block0 = n_reads / rpb;
         if (checksum) { sum_hdr.resize(batch_block0 + batch_blocks_n, 0); sum_qual.resize(batch_block0 + batch_blocks_n, 0); }   // (no job is running: both were joined above)
         t_w = std::chrono::steady_clock::now();
-        if (keep_header && checksum) start_header_sums(batch, got, batch_block0);
+        if (keep_header && checksum) header_sums(batch, got, batch_block0);
         if (keep_header) {
-            check_sink(hdr_ctx.get(), leon_header_encode_batch(hdr_ctx.get(), reinterpret_cast<const uint8_t*>(batch.headers.data()), batch.header_off.data(), got, n_reads,
-                                                               reinterpret_cast<const uint8_t*>(first_header.data()), first_header.size(), StreamWriter::sink, &wh),
-                       wh, "leon_header_encode_batch");
-            header_bytes += batch.headers.size();
+            const uint8_t* const first = reinterpret_cast<const uint8_t*>(first_header.data());
+            if (batch.headers.dev) {
+                uint64_t* const d_off = static_cast<uint64_t*>(d_header_off.fit(dev0, (got + 1) * 8));
+                check(nullptr, leon_device_upload(dev0, d_off, batch.header_off, (got + 1) * 8), "leon_device_upload");
+                check_sink(hdr_ctx.get(), leon_header_encode_batch_device(hdr_ctx.get(), static_cast<const uint8_t*>(batch.headers.dev), d_off, got, n_reads, first, first_header.size(),
+                                                                          StreamWriter::sink, &wh),
+                           wh, "leon_header_encode_batch_device");
+            } else
+                check_sink(hdr_ctx.get(), leon_header_encode_batch(hdr_ctx.get(), reinterpret_cast<const uint8_t*>(batch.headers.host), batch.header_off, got, n_reads, first,
+                                                                   first_header.size(), StreamWriter::sink, &wh),
+                           wh, "leon_header_encode_batch");
+            header_bytes += batch.headers.bytes;
             for (uint64_t r = 0; r < got; r += rpb) hdr_text.push_back(batch.header_off[std::min<uint64_t>(got, r + rpb)] - batch.header_off[r]);   // (batches are whole blocks but the last)
         }
         w_headers += seconds_since(t_w);
-        qual_bytes += batch.quals.size();
+        qual_bytes += batch.quals.bytes;
         t_w = std::chrono::steady_clock::now();
         if (keep_qual && o._lossless) start_lossless_quals(batch, got, batch_block0);
         w_quals += seconds_since(t_w);
         t_w = std::chrono::steady_clock::now();
-        for (auto& st : store) st->append(batch.bases);
+        Blob through_host = batch.bases;                         // for the devices the bases are not on: downloaded once if they have to be
+        through_host.dev = nullptr;
+        for (auto& st : store) {
+            if (batch.bases.dev && st->device == dev0) { st->append(batch.bases); continue; }
+            if (!through_host.host) through_host.host = on_host(batch.bases, dev0, host_bases);
+            st->append(through_host);
+        }
         if (qstore) {                                            // lossy mode: the qualities wait in HBM, beside the bases, for the bloom
             try { qstore->append(batch.quals); }
             catch (const Exception&) { qstore.reset(); }         // no room: they are read again from the file afterwards
@@ -340,10 +378,6 @@ void Compressor::pass_over_file() {
         if (got < batch_reads) break;                            // the partial batch is the last one
     }
     hdr_ctx.reset();
-    end_pass();
-}
-
-void Compressor::end_pass() {
     if (qual_job.valid()) qual_job.get();
     if (hdr_sum_job.valid()) hdr_sum_job.get();
     n_blocks = (n_reads + rpb - 1) / rpb; n_bases = offsets.back();
@@ -356,98 +390,6 @@ void Compressor::end_pass() {
     }
     if (o._letters) take_letters();
     t_parse = seconds_since(t_start);
-}
-
-// `-record-parse device`: the same pass over batches the device reader leaves in device memory (fastq_reader.hpp).  The offsets are
-// on the host; headers, bases and qualities go from device memory to where the host route uploads them.
-void Compressor::pass_over_device_batches() {
-    CtxPtr hdr_ctx;
-    if (keep_header) hdr_ctx = make_ctx(k, 1000, dev0);
-    FastqDeviceReader* const reader = dreader.get();
-    const uint64_t want = batch_reads;
-    auto parse_next = [reader, want](DeviceBatch* b) -> uint64_t { return reader->next(*b, want); };
-    std::future<uint64_t> parsing = std::async(std::launch::async, parse_next, &dbuffers[0]);
-    struct ParseJoin { std::future<uint64_t>& f; ~ParseJoin() { if (f.valid()) { try { f.get(); } catch (...) {} } } } parse_join{parsing};
-    ScratchMem d_header_off;
-    std::string host_bases;
-    for (uint32_t cur = 0;; cur ^= 1) {
-        auto t_w = std::chrono::steady_clock::now();
-        const uint64_t got = parsing.get();                      // (the reader's exceptions surface here)
-        w_reader += seconds_since(t_w);
-        if (!got) break;
-        DeviceBatch& batch = dbuffers[cur];
-        t_w = std::chrono::steady_clock::now();
-        if (qual_job.valid()) qual_job.get();                    // (it reads this buffer's twin in place, as on the host route)
-        w_quals += seconds_since(t_w);
-        if (got == batch_reads) parsing = std::async(std::launch::async, parse_next, &dbuffers[cur ^ 1]);
-        if (n_reads == 0) first_header = reader->firstHeader();
-        const uint64_t batch_blocks_n = (got + rpb - 1) / rpb, batch_block0 = n_reads / rpb;
-        if (checksum) { sum_hdr.resize(batch_block0 + batch_blocks_n, 0); sum_qual.resize(batch_block0 + batch_blocks_n, 0); }
-        t_w = std::chrono::steady_clock::now();
-        if (keep_header) {
-            if (checksum && batch.header_bytes) {
-                const std::vector<uint64_t> boff = block_offsets(batch.header_off.data(), got, rpb);
-                sums_on_device(dev0, batch.headers.get(), batch.header_bytes, boff.data(), boff.size() - 1, sum_hdr.data() + batch_block0);
-            }
-            uint64_t* const d_off = static_cast<uint64_t*>(d_header_off.fit(dev0, (got + 1) * 8));
-            check(nullptr, leon_device_upload(dev0, d_off, batch.header_off.data(), (got + 1) * 8), "leon_device_upload");
-            batch.reserve(1, 1);                                 // (a batch of empty headers has no blob yet)
-            check_sink(hdr_ctx.get(), leon_header_encode_batch_device(hdr_ctx.get(), batch.headers.as<uint8_t>(), d_off, got, n_reads, reinterpret_cast<const uint8_t*>(first_header.data()),
-                                                                      first_header.size(), StreamWriter::sink, &wh),
-                       wh, "leon_header_encode_batch_device");
-            header_bytes += batch.header_bytes;
-            for (uint64_t r = 0; r < got; r += rpb) hdr_text.push_back(batch.header_off[std::min<uint64_t>(got, r + rpb)] - batch.header_off[r]);
-        }
-        w_headers += seconds_since(t_w);
-        qual_bytes += batch.base_bytes;
-        t_w = std::chrono::steady_clock::now();
-        if (keep_qual && o._lossless) start_lossless_quals_device(batch, got, batch_block0);
-        w_quals += seconds_since(t_w);
-        t_w = std::chrono::steady_clock::now();
-        bool have_host_bases = false;
-        for (auto& st : store) {
-            if (st->device == dev0) { st->append_device(batch.bases.get(), batch.base_bytes); continue; }
-            if (!have_host_bases) {                              // the other devices get them through the host
-                have_host_bases = true;
-                host_bases.resize(batch.base_bytes);
-                if (batch.base_bytes) check(nullptr, leon_device_download(dev0, &host_bases[0], batch.bases.get(), batch.base_bytes), "leon_device_download");
-            }
-            st->append(host_bases);
-        }
-        if (qstore) {
-            try { qstore->append_device(batch.quals.get(), batch.base_bytes); }
-            catch (const Exception&) { qstore.reset(); }
-            if (qstore && qstore->n_bases > qual_resident_max) qstore.reset();
-        }
-        for (uint64_t i = 1; i <= got; i++) offsets.push_back(offsets[n_reads] + batch.base_off[i]);
-        w_uploads += seconds_since(t_w);
-        n_reads += got;
-        if (got < batch_reads) break;
-    }
-}
-
-// `-lossless` under `-record-parse device`: the batch's quality blocks from its device buffer -- deflated there, or downloaded once for
-// zlib on the host threads
-void Compressor::start_lossless_quals_device(const DeviceBatch& batch, uint64_t got, uint64_t block0) {
-    if (n_reads == 0) {                                          // the sample the host route takes: reads up to 256 KB of lines
-        uint64_t n = 0;
-        while (n < got && batch.base_off[n] + n < (256u << 10)) n++;
-        pick_qual_encoder_on_device(batch.quals.get(), batch.base_off.data(), n);
-    }
-    const DeviceBatch* b = &batch;
-    uint32_t* sums = checksum ? sum_qual.data() + block0 : nullptr;
-    qual_job = std::async(std::launch::async, [this, b, got, block0, sums] {
-        const std::vector<uint64_t> boff = sums ? block_offsets(b->base_off.data(), got, Leon::READ_PER_BLOCK) : std::vector<uint64_t>();
-        if (qual_on_device) {
-            if (sums) sums_on_device(dev0, b->quals.get(), b->base_bytes, boff.data(), boff.size() - 1, sums);
-            deflate_blocks(b->quals.as<uint8_t>(), nullptr, b->base_off.data(), got, block0);
-            return;
-        }
-        std::string quals(b->base_bytes, '\0');
-        if (b->base_bytes) check(nullptr, leon_device_download(dev0, &quals[0], b->quals.get(), b->base_bytes), "leon_device_download");
-        if (sums) sums_on_host(quals.data(), quals.size(), boff.data(), boff.size() - 1, cores, sums);
-        deflate_blocks(nullptr, quals.data(), b->base_off.data(), got, block0);
-    });
 }
 
 // `-letters`: lower-case runs and bytes outside ACGTN out of every device's resident copy, which is folded to what the coder carries
@@ -545,22 +487,25 @@ void Compressor::encode_dna() {
     t_encode = seconds_since(t_dna);
 }
 
-// the sample that picks the encoder: the first n reads' lines (off: n + 1 offsets, the sample begins at off[0])
-void Compressor::pick_qual_encoder(const char* sample, const uint64_t* off, uint64_t n) {
-    qual_on_device = qual_enc == Choice::Device || (qual_enc == Choice::Auto && runs_are_enough(sample, off, n));
+// the sample that picks the encoder under `auto`: of the batch's first n reads those of the first 256 KB of lines (where runs_are_enough
+// stops reading), downloaded when they are in device memory
+void Compressor::pick_qual_encoder(const BatchView& batch, uint64_t n) {
+    qual_on_device = qual_enc == Choice::Device;
+    if (qual_enc != Choice::Auto) return;
+    uint64_t m = 0;
+    while (m < n && batch.qual_off[m] + m < (256u << 10)) m++;
+    Blob sample = batch.quals;
+    sample.bytes = batch.qual_off[m];
+    std::string room;
+    qual_on_device = runs_are_enough(on_host(sample, dev0, room), batch.qual_off, m);
 }
-void Compressor::pick_qual_encoder_on_device(const void* d_quals, const uint64_t* off, uint64_t n) {
-    std::string sample(off[n] - off[0], '\0');
-    if (!sample.empty()) check(nullptr, leon_device_download(dev0, &sample[0], d_quals, sample.size()), "leon_device_download");
-    pick_qual_encoder(sample.data(), off, n);
-}
-// `got` reads' quality blocks into the container, by whoever was picked: from d_quals (device memory) or h_quals
-void Compressor::deflate_blocks(const uint8_t* d_quals, const char* h_quals, const uint64_t* off, uint64_t got, uint64_t first_block) {
+// `got` reads' quality blocks into the container, by whoever was picked: from quals.dev (device memory) or quals.host
+void Compressor::deflate_blocks(const Blob& quals, const uint64_t* off, uint64_t got, uint64_t first_block) {
     if (qual_on_device) {
-        const int rc = leon_qual_deflate_blocks_device(dev0, d_quals, off, got, Leon::READ_PER_BLOCK, StreamWriter::sink, &wq, first_block);
+        const int rc = leon_qual_deflate_blocks_device(dev0, static_cast<const uint8_t*>(quals.dev), off, got, Leon::READ_PER_BLOCK, StreamWriter::sink, &wq, first_block);
         check_sink(nullptr, rc, wq, "leon_qual_deflate_blocks_device");
     } else {
-        const int rc = leon_host_qual_encode_blocks(reinterpret_cast<const uint8_t*>(h_quals), off, got, Leon::READ_PER_BLOCK, -1, cores, StreamWriter::sink, &wq, first_block);
+        const int rc = leon_host_qual_encode_blocks(reinterpret_cast<const uint8_t*>(quals.host), off, got, Leon::READ_PER_BLOCK, -1, cores, StreamWriter::sink, &wq, first_block);
         check_sink(nullptr, rc, wq, "leon_host_qual_encode_blocks");
     }
 }
@@ -581,24 +526,22 @@ void Compressor::lossy_quals_resident() {
         check(ctx[0].get(), rc, "leon_qual_smooth_batch_device");
         r += got;
     }
-    if (checksum) sums_on_device(dev0, qstore->d_bases(), n_bases, file_block_off.data(), n_blocks, sum_qual.data());    // what is stored: the smoothed bytes
-    pick_qual_encoder_on_device(qstore->d_bases(), offsets.data(), std::min<uint64_t>(n_reads, 4000));
-    for (uint64_t r = 0; r < n_reads;) {
-        const uint64_t got = std::min<uint64_t>(batch_reads, n_reads - r);
-        const uint64_t nb = offsets[r + got] - offsets[r];
-        const uint64_t first_block = r / rpb;
-        if (qual_on_device) {                                    // deflated where they lie
-            deflate_blocks(qstore->d_bases() + offsets[r], nullptr, offsets.data() + r, got, first_block);
-            r += got;
-            continue;
-        }
-        auto quals = std::make_shared<std::string>();
-        quals->resize(nb);
-        if (nb) check(nullptr, leon_device_download(dev0, &(*quals)[0], qstore->d_bases() + offsets[r], nb), "leon_device_download");
-        auto qoff = std::make_shared<std::vector<uint64_t>>(got + 1);
-        for (uint64_t i = 0; i <= got; i++) (*qoff)[i] = offsets[r + i] - offsets[r];
+    // what is stored, and summed under `-checksum`, is the smoothed bytes: chunk by chunk through the tail every quality batch takes
+    struct { std::string quals; std::vector<uint64_t> off; } chunk[2];   // (chunk i's job reads its own while chunk i + 1 is staged)
+    Join<void> join{qual_job};
+    for (uint64_t r = 0, i = 0; r < n_reads; i ^= 1) {
+        const uint64_t got = std::min<uint64_t>(batch_reads, n_reads - r), first_block = r / rpb;
+        std::vector<uint64_t>& off = chunk[i].off;
+        off.resize(got + 1);
+        for (uint64_t j = 0; j <= got; j++) off[j] = offsets[r + j] - offsets[r];
+        BatchView batch;
+        batch.quals.dev = qstore->d_bases() + offsets[r]; batch.quals.bytes = off[got];
+        batch.qual_off = off.data(); batch.n = got;
+        if (r == 0) pick_qual_encoder(batch, std::min<uint64_t>(got, 4000));
+        const Blob quals = stage_quals(batch, got, first_block, chunk[i].quals);
         if (qual_job.valid()) qual_job.get();
-        qual_job = std::async(std::launch::async, [this, quals, qoff, got, first_block] { deflate_blocks(nullptr, quals->data(), qoff->data(), got, first_block); });
+        if (qual_on_device) deflate_blocks(quals, batch.qual_off, got, first_block);       // deflated where they lie
+        else qual_job = std::async(std::launch::async, [this, quals, batch, got, first_block] { deflate_blocks(quals, batch.qual_off, got, first_block); });
         r += got;
     }
     if (qual_job.valid()) qual_job.get();
@@ -618,13 +561,10 @@ void Compressor::lossy_quals_second_pass() {
         uint8_t* const d_q = static_cast<uint8_t*>(d_qbuf.fit(dev0, batch.quals.size()));
         check(nullptr, leon_device_upload(dev0, d_q, batch.quals.data(), batch.quals.size()), "leon_device_upload");
         check(ctx[0].get(), leon_qual_smooth_batch_device(ctx[0].get(), store[0]->d_bases(), store[0]->d_off() + r, got, d_q), "leon_qual_smooth_batch_device");
-        if (checksum) {
-            const std::vector<uint64_t> boff = block_offsets(batch.qual_off.data(), got, rpb);
-            sums_on_device(dev0, d_q, batch.quals.size(), boff.data(), boff.size() - 1, sum_qual.data() + r / rpb);
-        }
-        if (r == 0) pick_qual_encoder_on_device(d_q, batch.qual_off.data(), std::min<uint64_t>(got, 4000));
-        if (!qual_on_device) check(nullptr, leon_device_download(dev0, &batch.quals[0], d_q, batch.quals.size()), "leon_device_download");
-        deflate_blocks(d_q, batch.quals.data(), batch.qual_off.data(), got, r / rpb);
+        BatchView smoothed = batch.view();                       // on the device only: what the host holds is the file's own bytes
+        smoothed.quals.host = nullptr; smoothed.quals.dev = d_q;
+        if (r == 0) pick_qual_encoder(smoothed, std::min<uint64_t>(got, 4000));
+        deflate_blocks(stage_quals(smoothed, got, r / rpb, batch.quals), smoothed.qual_off, got, r / rpb);   // (zlib: downloaded over them)
         r += got;
         if (got < batch_reads) break;
     }

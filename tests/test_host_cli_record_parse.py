@@ -75,7 +75,8 @@ def both_routes(leon_bin, path, *opts, env=None, keep=False):
     return r.stdout
 
 
-OPTS = [["-lossless"], [], ["-lossless", "-checksum", "-letters"], ["-lossless", "-qual-deflate", "device"]]
+OPTS = [["-lossless"], [], ["-lossless", "-checksum", "-letters"], ["-lossless", "-qual-deflate", "device"], ["-lossless", "-qual-deflate", "auto"],
+        ["-qual-deflate", "auto"]]
 
 
 @pytest.mark.parametrize("opts", OPTS, ids=lambda o: "+".join(o) or "lossy")
