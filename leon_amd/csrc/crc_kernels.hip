@@ -197,7 +197,7 @@ extern "C" int leon_crc32_segments_device(int device_id, const uint8_t* d_bytes,
     CallStream st;
     if (const int rc = dev_open("leon_crc32_segments_device", device_id, st)) return rc;
     hipStream_t s = st.s;
-    TmpBuf d_off, d_acc;
+    OwnBuf d_off, d_acc;
     DEVCHK(d_off.ensure((n_seg + 1) * sizeof(uint64_t))); DEVCHK(d_acc.ensure(n_seg * sizeof(uint32_t)));
     DEVCHK(hipMemcpyAsync(d_off.p, seg_off, (n_seg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     DEVCHK(hipMemsetAsync(d_acc.p, 0, n_seg * sizeof(uint32_t), s));

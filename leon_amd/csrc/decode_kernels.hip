@@ -6,9 +6,11 @@
 // symbol in the model's cumulative counts (two ballots over the two-level table of rc_model.h), the model update,
 // the refill of the payload window (256 bytes, 4 per lane).  2 000 blocks keep 2 000 waves in flight, which is what
 // hides the memory latency of the bloom probes (one dependent probe set per decoded base).
-#include "kernels.h"
+#include "ctx.h"
 #include "rc_model.h"
+#include "staging.h"
 #include <cstdlib>
+#include <thread>
 
 namespace leon {
 
@@ -715,7 +717,6 @@ void launch_hdr_decode_symbols(hipStream_t s, const uint8_t* payloads, const uin
     hipLaunchKernelGGL(k_hdr_decode_symbols, dim3(g), dim3(64), 0, s, payloads, pay_off, blk_reads, n_blocks, syms, sym_begin, sym_count, err);
 }
 
-
 // ---- header blocks: the TEXT from the symbols, on the device too --------------------------------------------------------
 // The device form of host_streams.cpp's decode_header_block<SymbolSource>, record for record.  A block is a serial chain --
 // header r is built from header r - 1, every block starts from the file's first header -- so again one wave per block, all
@@ -1035,4 +1036,188 @@ void launch_decode_blocks(hipStream_t s, BloomDev B, PathCache C, const uint16_t
 #undef DC_LAUNCH
 }
 
+int block_table_to_device(leon_dna_ctx* c, const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads, uint64_t n_blocks,
+                          DevBuf& pay, BlockTableDev& T, uint64_t* ordered) {
+    hipStream_t s = c->stream;
+    std::vector<uint64_t> rel_off(n_blocks + 1, 0);
+    for (uint64_t b = 0; b < n_blocks; b++) {
+        if (payload_off[b + 1] < payload_off[b]) { if (ordered) *ordered = b; return fail(c, LEON_E_INVALID, "payload offsets are not monotonic"); }
+        rel_off[b + 1] = payload_off[b + 1] - payload_off[0];
+    }
+    const uint64_t pay_bytes = rel_off[n_blocks];
+    HIPCHK(c, pay.ensure(pay_bytes + 1024)); HIPCHK(c, T.off.ensure((n_blocks + 1) * 8)); HIPCHK(c, T.nreads.ensure(n_blocks * 4));
+    HIPCHK(c, staged_h2d(c->device, pay.p, payloads + payload_off[0], pay_bytes));
+    HIPCHK(c, hipMemsetAsync((uint8_t*)pay.p + pay_bytes, 0, 1024, s));
+    HIPCHK(c, hipMemcpyAsync(T.off.p, rel_off.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(T.nreads.p, block_n_reads, n_blocks * 4, hipMemcpyHostToDevice, s));
+    return LEON_OK;
+}
+
+// The decoder's path cache (c->dc): a few bytes per solid k-mer, kept from call to call for as long as the bloom's bits stay what they
+// were (their fingerprint is taken again at every call, through the device word d_fp: 0.3 ms for a gigabyte).  4 slots per k-mer the
+// bloom was sized for (two orientations, half full), at most 40 % of the free memory and what the cache holds; LEON_DC_CACHE_MB
+// overrides (0: no cache).  is_new: the table was (re)built -- another geometry, another bloom -- and is empty.
+static int refresh_path_cache(leon_dna_ctx* c, uint64_t* d_fp, bool& is_new) {
+    hipStream_t s = c->stream; DecoderState& dc = c->dc;
+    uint64_t want_buckets = std::max<uint64_t>(c->cfg.bloom_tai / 12 * (kmer_words(c->cfg.kmer_size) == 2 ? 2 : 1), 1024);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+    uint64_t budget = (uint64_t)(free_b + dc.cache.cap) * 2 / 5;
+    if (const char* e = getenv("LEON_DC_CACHE_MB")) budget = (uint64_t)std::max<long long>(0, atoll(e)) << 20;
+    uint64_t buckets = 1024;
+    while (buckets < want_buckets) buckets <<= 1;
+    while (buckets > 1024 && buckets * 64 > budget) buckets >>= 1;
+    if (buckets * 64 > budget) buckets = 0;
+    HIPCHK(c, hipMemsetAsync(d_fp, 0, 8, s));
+    launch_bloom_fingerprint(s, c->d_bloom.as<uint8_t>(), c->bloom_nchar, d_fp);
+    uint64_t fp = 0;
+    HIPCHK(c, hipMemcpyAsync(&fp, d_fp, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (!buckets) dc.drop_cache();
+    else if (!dc.pc.slots || dc.pc.bucket_mask != buckets - 1 || !dc.filled || fp != dc.bloom_fp) {
+        if (dc.pc.bucket_mask != buckets - 1 || !dc.pc.slots) {
+            dc.cache.release();
+            if (dc.cache.ensure(buckets * 64) != hipSuccess) { (void)hipGetLastError(); dc.pc = PathCache{}; buckets = 0; }   // no room: decode without it
+            else { dc.pc.slots = dc.cache.as<uint64_t>(); dc.pc.bucket_mask = buckets - 1; }
+        }
+        if (buckets) { launch_path_cache_init(s, dc.pc, c->cfg.kmer_size); dc.bloom_fp = fp; dc.filled = true; is_new = true; }
+    }
+    return LEON_OK;
+}
 }  // namespace leon
+
+// ---- the context's calls that end in this file's kernels (ctx.h) ----
+using namespace leon;
+extern "C" {
+// leon_dna_decode_blocks and leon_dna_decode_blocks_device: the same call up to where the bases go once every block has decoded --
+// to the caller's host memory (out_bases, out_len), or to the caller's device buffers (d_user_bases, d_user_len; out_len then
+// optional, the host's copy of the lengths)
+static int decode_blocks_impl(leon_dna_ctx* c, const uint64_t* anchors, uint64_t n_anchors, const uint8_t* payloads,
+                              const uint64_t* payload_off, const uint32_t* block_n_reads, const uint64_t* block_n_bases,
+                              uint64_t n_blocks, uint8_t* out_bases, uint64_t out_cap, uint32_t* out_len, uint8_t* d_user_bases,
+                              uint32_t* d_user_len) {
+    if (!c) return LEON_E_INVALID;
+    if (n_blocks == 0) return LEON_OK;
+    const bool to_device = d_user_bases != nullptr;
+    if (!payloads || !payload_off || !block_n_reads || !block_n_bases || (!to_device && (!out_bases || !out_len)) || (to_device && !d_user_len) ||
+        (!anchors && n_anchors))
+        return fail(c, LEON_E_INVALID, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    static const bool trace = getenv("LEON_TRACE_DECODE") != nullptr;    // where a call's time goes, on stderr
+    auto t_prev = std::chrono::steady_clock::now();
+    auto lap = [&](const char* what) {
+        if (!trace) return;
+        (void)hipStreamSynchronize(s);
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[leon decode] %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
+        t_prev = now;
+    };
+    const uint32_t W = kmer_words(c->cfg.kmer_size);
+    OwnBuf d_anchors, d_read0, d_out0, d_err;
+    BlockTableDev T;
+    DevBuf &d_pay = c->dc.pay, &d_out = c->dc.out, &d_len = c->dc.len, &d_scr = c->dc.scr, &d_pool = c->dc.pool;
+    uint64_t ordered = n_blocks;                              // the blocks before the first whose payload would end before it begins
+    const int table_rc = block_table_to_device(c, payloads, payload_off, block_n_reads, n_blocks, d_pay, T, &ordered);
+    std::vector<uint64_t> read0(n_blocks + 1, 0), out0(n_blocks + 1, 0);
+    for (uint64_t b = 0; b < ordered; b++) {                  // (an earlier block that overruns out_cap is refused first, as it always was)
+        read0[b + 1] = read0[b] + block_n_reads[b];
+        out0[b + 1] = out0[b] + block_n_bases[b];
+        if (out0[b + 1] < out0[b] || out0[b + 1] > out_cap) return fail(c, LEON_E_INVALID, "output capacity below the sum of block_n_bases");
+    }
+    if (table_rc) return table_rc;
+    HIPCHK(c, d_anchors.ensure(std::max<uint64_t>(n_anchors * W, 1) * 8));
+    HIPCHK(c, d_read0.ensure((n_blocks + 1) * 8)); HIPCHK(c, d_out0.ensure((n_blocks + 1) * 8));
+    HIPCHK(c, d_out.ensure(out0[n_blocks] + 64)); HIPCHK(c, d_len.ensure(std::max<uint64_t>(read0[n_blocks], 1) * 4));
+    HIPCHK(c, d_scr.ensure(decode_scratch_bytes(n_blocks))); HIPCHK(c, d_err.ensure(256));
+    // position lists longer than a block's own scratch (8192 N or error positions in ONE read) come from this pool
+    const uint64_t pool_words = std::min<uint64_t>(std::max<uint64_t>(out0[n_blocks] / 2, 1ull << 20), 1ull << 28);
+    HIPCHK(c, d_pool.ensure(pool_words * 4 + 16));
+    lap("buffers and payloads");
+    bool cache_is_new = false;
+    if (int rc = refresh_path_cache(c, d_err.as<uint64_t>() + 1, cache_is_new)) return rc;
+    lap("path cache");
+    if (n_anchors) HIPCHK(c, hipMemcpyAsync(d_anchors.p, anchors, n_anchors * W * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_read0.p, read0.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_out0.p, out0.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(d_err.p, 0, 256, s));
+    HIPCHK(c, hipMemsetAsync((uint8_t*)d_pool.p + pool_words * 4, 0, 16, s));           // the pool's cursor lives behind it
+    lap("tables to the device");
+    if (cache_is_new) {                                       // what the bloom says around every anchor, before the blocks ask (decode_kernels.hip)
+        static const char* pw = getenv("LEON_DC_PREWALK");    // measurement override: steps per anchor and orientation, 0 = none
+        // probes per anchor and orientation.  The walks are throughput (0.25 s for 25 M lanes x 64), the blocks' chains latency:
+        // 128 pays for files of a few hundred blocks (10 M reads: 26 + 1 697 ms -> 52 + 1 593) and for two-word k-mers, 64 at
+        // 2 000 blocks (249 + 2 215 ms against 534 + 2 065)
+        const uint32_t steps = pw ? (uint32_t)std::max(0, atoi(pw)) : ((c->cfg.kmer_size >= 32 || n_anchors < (4u << 20)) ? 128u : 64u);
+        if (steps) launch_path_cache_prewalk(s, c->B, c->dc.pc, c->rv16(), d_anchors.as<uint64_t>(), n_anchors, steps);
+        lap("path cache: walks from the anchors");
+    }
+    launch_decode_blocks(s, c->B, c->dc.pc, c->rv16(), d_anchors.as<uint64_t>(), n_anchors, d_pay.as<uint8_t>(), T.off.as<uint64_t>(),
+                         T.nreads.as<uint32_t>(), d_read0.as<uint64_t>(), d_out0.as<uint64_t>(), n_blocks, d_out.as<uint8_t>(),
+                         d_len.as<uint32_t>(), d_scr.as<uint32_t>(), d_pool.as<uint32_t>(),
+                         (unsigned long long*)((uint8_t*)d_pool.p + pool_words * 4), pool_words, d_err.as<int>(),
+                         trace ? (unsigned long long*)((uint8_t*)d_err.p + 64) : nullptr);
+    HIPCHK(c, hipGetLastError());
+    // While the blocks decode (seconds), the caller's output buffer is touched page by page: fresh memory is mapped on first
+    // write, which would otherwise happen inside the copy back -- 3.7 M page faults for a 100 M-read file, on the critical path.
+    // Each page's first byte is written back as it was read, so the buffer's contents survive a call that then fails (a corrupt
+    // block, a HIP error): a successful call overwrites all of it, a failed one changes nothing.
+    std::vector<std::thread> toucher;
+    {
+        const uint64_t nb_out = out0[n_blocks];
+        const uint32_t nt = !to_device && nb_out >= (256ull << 20) ? 4u : 0u;
+        for (uint32_t w = 0; w < nt; w++)
+            toucher.emplace_back([out_bases, nb_out, w, nt] {
+                volatile uint8_t* q = out_bases;
+                for (uint64_t a = nb_out * w / nt; a < nb_out * (w + 1) / nt; a += 4096) q[a] = q[a];
+            });
+    }
+    struct Join { std::vector<std::thread>& t; ~Join() { for (auto& x : t) if (x.joinable()) x.join(); } } join_touchers{toucher};
+    int err[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(err, d_err.p, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    for (auto& x : toucher) x.join();
+    toucher.clear();
+    lap("k_decode_blocks");
+    if (trace) {
+        unsigned long long st[16] = {0};
+        HIPCHK(c, hipMemcpy(st, (uint8_t*)d_err.p + 64, 128, hipMemcpyDeviceToHost));
+        const double nr = st[5] ? (double)st[5] : 1.0;
+        fprintf(stderr, "[leon decode] per read: %.2f table jumps (%.1f positions), %.2f table misses, %.2f one-k-mer probe rounds, %.2f deep probe rounds, %.2f more answered by the table\n",
+                st[0] / nr, st[4] / nr, st[1] / nr, st[6] / nr, st[2] / nr, st[3] / nr);
+        fprintf(stderr, "[leon decode] per read: %.2f entries taken to their end before the last base, one-k-mer rounds: %.2f on a branching k-mer, %.2f found the successor in the table\n", st[10] / nr, st[11] / nr, st[9] / nr);
+        fprintf(stderr, "[leon decode] per read: %.2f us in its fields, %.2f us in its walks (100 MHz clock, the wave's own time)\n", st[7] / nr / 100.0, st[8] / nr / 100.0);
+    }
+    if (err[0]) {
+        const char* what = err[0] == 1 ? "anchor address or position out of range" : err[0] == 2 ? "more or fewer bases than the block table says"
+                         : err[0] == 4 ? "the payload ends before its reads do" : "too many N / error positions in one read";
+        return fail(c, LEON_E_INVALID, std::string("block ") + std::to_string(err[1]) + " does not decode: " + what);
+    }
+    if (to_device) {                                          // the bases stay in HBM: into the caller's buffers, complete on return
+        if (out0[n_blocks]) HIPCHK(c, hipMemcpyAsync(d_user_bases, d_out.p, out0[n_blocks], hipMemcpyDeviceToDevice, s));
+        if (read0[n_blocks]) HIPCHK(c, hipMemcpyAsync(d_user_len, d_len.p, read0[n_blocks] * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        if (out_len && read0[n_blocks]) HIPCHK(c, staged_d2h(c->device, out_len, d_len.p, read0[n_blocks] * 4));
+        lap("bases to the caller's device buffers");
+        return LEON_OK;
+    }
+    HIPCHK(c, staged_d2h(c->device, out_bases, d_out.p, out0[n_blocks]));     // gigabytes into the caller's pageable memory: at PCIe's rate (staging.h)
+    if (read0[n_blocks]) HIPCHK(c, staged_d2h(c->device, out_len, d_len.p, read0[n_blocks] * 4));
+    lap("bases to the host");
+    return LEON_OK;
+}
+
+int leon_dna_decode_blocks(leon_dna_ctx* c, const uint64_t* anchors, uint64_t n_anchors, const uint8_t* payloads,
+                           const uint64_t* payload_off, const uint32_t* block_n_reads, const uint64_t* block_n_bases,
+                           uint64_t n_blocks, uint8_t* out_bases, uint64_t out_cap, uint32_t* out_len) {
+    return decode_blocks_impl(c, anchors, n_anchors, payloads, payload_off, block_n_reads, block_n_bases, n_blocks, out_bases, out_cap, out_len, nullptr, nullptr);
+}
+
+int leon_dna_decode_blocks_device(leon_dna_ctx* c, const uint64_t* anchors, uint64_t n_anchors, const uint8_t* payloads,
+                                  const uint64_t* payload_off, const uint32_t* block_n_reads, const uint64_t* block_n_bases,
+                                  uint64_t n_blocks, uint8_t* d_out_bases, uint64_t out_cap, uint32_t* d_out_len, uint32_t* out_len) {
+    if (!c) return LEON_E_INVALID;
+    if (n_blocks && (!d_out_bases || !d_out_len)) return fail(c, LEON_E_INVALID, "null argument");
+    return decode_blocks_impl(c, anchors, n_anchors, payloads, payload_off, block_n_reads, block_n_bases, n_blocks, nullptr, out_cap, out_len, d_out_bases, d_out_len);
+}
+}  // extern "C"

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <utility>
 
 namespace leon {
 
@@ -41,17 +42,21 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
     template <typename T> T* as() const { return (T*)p; }
 };
-// a device buffer that lives for one call: released on every way out of the scope
-struct TmpBuf : DevBuf {
-    TmpBuf() = default;
-    TmpBuf(const TmpBuf&) = delete;
-    TmpBuf& operator=(const TmpBuf&) = delete;
-    ~TmpBuf() { release(); }
+struct NoCopy { NoCopy() = default; NoCopy(const NoCopy&) = delete; NoCopy& operator=(const NoCopy&) = delete; };
+// a device buffer with an owner -- a call's scope, a context (ctx.h), a set a call hands out: released when the owner goes.
+// (DevBuf itself has no destructor: the stateless calls' parked scratch lives as long as the process and must not be freed at exit.)
+struct OwnBuf : DevBuf, NoCopy {
+    // `bytes` and no slack (tables of gigabytes, sized once); nothing kept on failure
+    hipError_t exactly(size_t bytes) { release(); const hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) cap = bytes; else p = nullptr; return e; }
+    void swap(OwnBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(slack, o.slack); }
+    ~OwnBuf() { release(); }
 };
 
-// a stream of the call's own: the call runs beside calls on the contexts' streams; waited for and destroyed on every way out
-struct CallStream {
+// a stream with an owner -- a stateless call (it runs beside calls on the contexts' streams), a context: waited for and destroyed
+// when the owner goes
+struct CallStream : NoCopy {
     hipStream_t s = nullptr;
+    operator hipStream_t() const { return s; }
     ~CallStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
 };
 inline int dev_stream(CallStream& st) { DEVCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking)); return LEON_OK; }

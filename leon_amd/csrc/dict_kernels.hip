@@ -14,6 +14,7 @@
 #include "device_call.h"
 
 #include <algorithm>
+#include <cstring>
 #include <vector>
 
 namespace leon {
@@ -216,13 +217,13 @@ void launch_dict_decode_pieces(hipStream_t s, const uint8_t* payload, const uint
 // A piece's slot is first P * k / 2 + 64 bytes, twice what a genomic dictionary needs (2 bits a base); a list that does not fit --
 // nothing but adversarial k-mers -- is coded again with 8 bytes per symbol, the most a step can shift out (k_dict_encode_pieces).
 // LEON_OK, or the code with `why`: leon_dna_finish (capi.hip) keeps it with its context, the stateless call below with the thread.
-int dict_pieces_code(hipStream_t s, const uint64_t* d_kmers, uint64_t n_anchors, uint32_t k, uint32_t P, uint64_t* piece_off, TmpBuf& d_dst, std::string& why) {
+int dict_pieces_code(hipStream_t s, const uint64_t* d_kmers, uint64_t n_anchors, uint32_t k, uint32_t P, uint64_t* piece_off, OwnBuf& d_dst, std::string& why) {
 #define PIECES_CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { why = hip_failure(#call, e_); return LEON_E_HIP; } } while (0)
     const uint64_t n_pieces = dict_piece_count(n_anchors, P);
     piece_off[0] = 0;
     if (!n_pieces) return LEON_OK;
     const uint64_t piece_syms = (uint64_t)std::min<uint64_t>(P, n_anchors) * k;
-    TmpBuf d_scratch, d_sizes, d_off, d_err, d_tmp;
+    OwnBuf d_scratch, d_sizes, d_off, d_err, d_tmp;
     PIECES_CHK(d_sizes.ensure((n_pieces + 1) * 8)); PIECES_CHK(d_off.ensure((n_pieces + 1) * 8)); PIECES_CHK(d_err.ensure(4));
     PIECES_CHK(hipMemsetAsync((uint64_t*)d_sizes.p + n_pieces, 0, 8, s));
     uint64_t stride = 0;
@@ -264,7 +265,7 @@ extern "C" int leon_anchor_dict_encode_pieces_device(int device_id, const uint64
     if (!n_anchors) return LEON_OK;                               // no piece: no device is asked
     CallStream st;
     if (const int rc = dev_open("leon_anchor_dict_encode_pieces_device", device_id, st)) return rc;
-    TmpBuf d_dst;
+    OwnBuf d_dst;
     std::string why;
     if (const int rc = dict_pieces_code(st.s, d_kmers, n_anchors, k, P, piece_off, d_dst, why)) return dev_fail(rc, why);
     *size = piece_off[dict_piece_count(n_anchors, P)];
@@ -286,7 +287,7 @@ extern "C" int leon_anchor_dict_decode_pieces_device(int device_id, const uint8_
     const uint64_t first = piece_off[0], bytes = piece_off[n_pieces] - first;
     std::vector<uint64_t> rel(n_pieces + 1);
     for (uint64_t p = 0; p <= n_pieces; p++) rel[p] = piece_off[p] - first;
-    TmpBuf d_pay, d_off, d_out, d_bad;
+    OwnBuf d_pay, d_off, d_out, d_bad;
     DEVCHK(d_pay.ensure(bytes + 16)); DEVCHK(d_off.ensure((n_pieces + 1) * 8));
     DEVCHK(d_out.ensure(n_anchors * W * 8)); DEVCHK(d_bad.ensure(n_pieces * 4));
     if (bytes && staged_h2d(device_id, d_pay.p, payload + first, bytes) != hipSuccess) { (void)hipGetLastError(); return dev_fail(LEON_E_HIP, "leon_anchor_dict_decode_pieces_device: the pieces' copy to the device failed"); }
@@ -301,4 +302,44 @@ extern "C" int leon_anchor_dict_decode_pieces_device(int device_id, const uint8_
     DEVCHK(hipMemcpyAsync(out_kmers, d_out.p, n_anchors * W * 8, hipMemcpyDeviceToHost, s));
     DEVCHK(hipStreamSynchronize(s));
     return LEON_OK;
+}
+
+// host-only: the dictionary stream of a list of anchors (what the worker thread produces); no GPU involved
+extern "C" int leon_host_anchor_dict_encode(const uint64_t* kmers, uint64_t n, uint32_t k, uint8_t* out, uint64_t out_cap, uint64_t* size) {
+    if ((!kmers && n) || !size || k < 1 || k > 63) return LEON_E_INVALID;
+    // the same worker (chain thread + reciprocal helper thread) the contexts use, fed in a few batches
+    AnchorDictWorker worker(k);
+    const uint32_t W = kmer_words(k);
+    const uint64_t step = std::max<uint64_t>(1, n / 3);
+    for (uint64_t i = 0; i < n; i += step) {
+        const uint64_t m = std::min(step, n - i);
+        worker.push(std::vector<uint64_t>(kmers + i * W, kmers + (i + m) * W));
+    }
+    worker.drain();
+    AnchorDictCoder& coder = worker.coder();
+    coder.flush();
+    *size = coder.size();
+    if (coder.size() > out_cap) return LEON_E_OVERFLOW;
+    if (out) memcpy(out, coder.data(), coder.size());
+    return LEON_OK;
+}
+
+extern "C" int leon_host_anchor_dict_decode(const uint8_t* payload, uint64_t size, uint64_t n_anchors, uint32_t k, uint64_t* out) {
+    if ((!payload && size) || (!out && n_anchors)) return dev_fail(LEON_E_INVALID, "null argument");
+    if (k < 3 || k > 63) return dev_fail(LEON_E_INVALID, "kmer_size must be in 3..63");
+    if (!decode_anchor_dict(payload, size, n_anchors, k, out)) return dev_fail(LEON_E_INVALID, "anchor dictionary stream does not decode");
+    return LEON_OK;
+}
+
+extern "C" int leon_host_anchor_dict_encode_pieces(const uint64_t* kmers, uint64_t n_anchors, uint32_t k, uint32_t piece_anchors, uint8_t* out, uint64_t out_cap,
+                                        uint64_t* piece_off, uint64_t* size, uint32_t n_threads) {
+    std::string why;
+    const int rc = host_dict_encode_pieces(kmers, n_anchors, k, piece_anchors, out, out_cap, piece_off, size, n_threads, why);
+    return rc ? dev_fail(rc, why) : LEON_OK;
+}
+extern "C" int leon_host_anchor_dict_decode_pieces(const uint8_t* payload, const uint64_t* piece_off, uint64_t n_pieces, uint64_t n_anchors, uint32_t k,
+                                        uint32_t piece_anchors, uint64_t* out_kmers, uint32_t n_threads) {
+    std::string why;
+    const int rc = host_dict_decode_pieces(payload, piece_off, n_pieces, n_anchors, k, piece_anchors, out_kmers, n_threads, why);
+    return rc ? dev_fail(rc, why) : LEON_OK;
 }

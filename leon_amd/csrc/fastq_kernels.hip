@@ -201,7 +201,7 @@ extern "C" int leon_fastq_split_device(int device_id, const uint8_t* d_text, uin
     CallStream st;
     if (const int rc = dev_open("leon_fastq_split_device", device_id, st)) return rc;
     hipStream_t s = st.s;
-    TmpBuf d_cnt, d_first, d_nl, d_in, d_off, d_found, d_tmp;
+    OwnBuf d_cnt, d_first, d_nl, d_in, d_off, d_found, d_tmp;
     size_t tmp_bytes = 0;
     // every '\n' of the text, in order
     const uint64_t n_tiles = n_text ? (((uintptr_t)d_text & 15) + n_text + FASTQ_TILE - 1) / FASTQ_TILE : 0;

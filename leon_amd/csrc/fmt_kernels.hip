@@ -282,7 +282,7 @@ extern "C" int leon_records_format_device(int device_id, const leon_record_layou
     FmtLayout L{};
     L.first_read_index = lay->first_read_index; L.hdr_bytes = lay->hdr_bytes; L.wrap = lay->wrap;
     L.lead = lay->lead; L.fastq = lay->fastq ? 1 : 0; L.plus_kind = lay->fastq ? lay->plus_kind : 0;
-    TmpBuf d_in, d_off, d_flags, d_tmp;
+    OwnBuf d_in, d_off, d_flags, d_tmp;
     DEVCHK(d_in.ensure((n_reads + 1) * sizeof(FmtPair))); DEVCHK(d_off.ensure((n_reads + 1) * sizeof(FmtPair)));
     DEVCHK(d_flags.ensure(64));
     DEVCHK(hipMemsetAsync(d_flags.p, 0, 64, s));

@@ -5,8 +5,10 @@
 // are produced in parallel -- one lane per header, count pass / scan / emit pass like k_symbols -- and the per-block
 // serial part is left to k_rc_encode (rc_kernels.hip) with this stream's model set.  The record layout is the one
 // DESIGN.md section 1.3 states; the tests compare payload bytes with the CPU restatement of the same rules.
-#include "kernels.h"
-#include <algorithm>
+#include "ctx.h"
+#include "prim.h"
+#include "staging.h"
+#include <cstring>
 
 namespace leon {
 
@@ -349,3 +351,403 @@ void launch_qual_smooth(hipStream_t s, ReadsDev R, BloomDev B, const uint16_t* r
 }
 
 }  // namespace leon
+
+// ---- the context's calls that end in this file's kernels, and the header decoders (ctx.h) ----
+using namespace leon;
+
+// A host batch to the device, for the entry points that take host memory: the offsets, rebased to begin at 0, in c->in_off and the
+// bytes they span in c->in_bases.  nb: how many bytes that is.  (leon_dna_encode_batch has an upload of its own, staged and threaded.)
+static int upload_host_batch(leon_dna_ctx* c, const uint8_t* bytes, const uint64_t* off, uint64_t n, uint64_t& nb) {
+    if (off[n] < off[0]) return fail(c, LEON_E_INVALID, "offsets are not monotonic");
+    HIPCHK(c, hipSetDevice(c->device));
+    nb = off[n] - off[0];
+    HIPCHK(c, c->in_bases.ensure(nb + 64)); HIPCHK(c, c->in_off.ensure((n + 1) * 8));
+    HIPCHK(c, hipMemcpy(c->in_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice));
+    if (off[0]) {
+        launch_rebase_offsets(c->stream, c->in_off.as<uint64_t>(), n + 1, off[0]);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (nb) HIPCHK(c, hipMemcpy(c->in_bases.p, bytes + off[0], nb, hipMemcpyHostToDevice));
+    return LEON_OK;
+}
+
+extern "C" {
+// ------------------------------------------------------------------------------------------------ header stream
+// Leon::startHeaderCompression: Dispatcher::iterate(bank, HeaderEncoder(this)) [RECALLED].  Records of every header
+// against the previous one in parallel (hdr_kernels.hip), then the per-block chains on k_rc_encode with the header
+// stream's model set; blocks leave through the sink in increasing id, like the DNA stream's.
+static int header_batch_impl(leon_dna_ctx* c, const uint8_t* d_hdr, const uint64_t* d_off, uint64_t n, uint64_t first_read_index,
+                             const uint8_t* first_header, uint64_t first_len, leon_block_sink sink, void* user) {
+    if (!c) return LEON_E_INVALID;
+    if (int rc = c->hdr.follows(c, first_read_index, n, "header stream")) return rc;
+    if (n == 0) return LEON_OK;
+    if (!d_hdr || !d_off || !sink || (!first_header && first_len)) return fail(c, LEON_E_INVALID, "null argument");
+    if (n > 0xFFFFFFF0ull) return fail(c, LEON_E_INVALID, "more than 2^32 reads in one batch");
+    if (first_len >= (1ull << 31)) return fail(c, LEON_E_INVALID, "first header longer than 2^31 bytes");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const uint32_t rpb = c->cfg.reads_per_block;
+    // offsets must be an offsets array before anything indexes with them (headers below 2^31 bytes each)
+    if (int rc = check_offsets(c, d_off, n, "a header is longer than 2^31 bytes", nullptr, false)) return rc;
+    const Share sh = share_of(c, n);                            // this rank's share: the same contiguous block range as the DNA stream's
+    if (sh.nl) {
+        HIPCHK(c, c->hdr_first.ensure(first_len + 16));
+        if (first_len) HIPCHK(c, hipMemcpyAsync(c->hdr_first.p, first_header, first_len, hipMemcpyHostToDevice, s));
+        auto symbols = [&](uint8_t* syms) { launch_hdr_symbols(s, d_hdr, d_off + sh.r0, sh.nl, rpb, c->hdr_first.as<uint8_t>(), (uint32_t)first_len,
+                                                                c->sym_off.as<uint64_t>(), syms); };
+        CodedBlocks out;
+        if (int rc = code_blocks(c, sh, symbols, SMALL_SIZES_HEADER, false, "header", out)) return rc;
+        if (int rc = deliver_blocks(c, out, sh, n, c->hdr.next_block, sink, user)) return rc;
+    }
+    c->hdr.advance(n, rpb);
+    return LEON_OK;
+}
+
+int leon_header_encode_batch_device(leon_dna_ctx* c, const uint8_t* d_headers, const uint64_t* d_off, uint64_t n, uint64_t first_read_index,
+                                    const uint8_t* first_header, uint64_t first_header_len, leon_block_sink sink, void* user) {
+    if (!c) return LEON_E_INVALID;
+    if (c->poisoned) return refuse_poisoned(c);
+    return note_poisoned(c, header_batch_impl(c, d_headers, d_off, n, first_read_index, first_header, first_header_len, sink, user));   // (a sink that refused a block)
+}
+
+int leon_header_encode_batch(leon_dna_ctx* c, const uint8_t* headers, const uint64_t* off, uint64_t n, uint64_t first_read_index,
+                             const uint8_t* first_header, uint64_t first_header_len, leon_block_sink sink, void* user) {
+    if (!c) return LEON_E_INVALID;
+    if (n == 0) return leon_header_encode_batch_device(c, nullptr, nullptr, 0, first_read_index, first_header, first_header_len, sink, user);
+    if (!headers || !off) return fail(c, LEON_E_INVALID, "null argument");
+    uint64_t nb = 0;
+    if (int rc = upload_host_batch(c, headers, off, n, nb)) return rc;
+    return leon_header_encode_batch_device(c, c->in_bases.as<uint8_t>(), c->in_off.as<uint64_t>(), n, first_read_index, first_header,
+                                           first_header_len, sink, user);
+}
+
+// ------------------------------------------------------------------------------------------------ quality stream (lossy)
+// DnaEncoder::smoothQuals over a batch: the reads are packed as for the encode path, then one wave per read rewrites the
+// qualities in place (hdr_kernels.hip k_qual_smooth).  Needs the file's bloom in the context.
+int leon_qual_smooth_batch_device(leon_dna_ctx* c, const uint8_t* d_bases, const uint64_t* d_off, uint64_t n, uint8_t* d_quals) {
+    if (!c) return LEON_E_INVALID;
+    if (n == 0) return LEON_OK;
+    if (!d_bases || !d_off || !d_quals) return fail(c, LEON_E_INVALID, "null argument");
+    if (n > 0xFFFFFFF0ull) return fail(c, LEON_E_INVALID, "more than 2^32 reads in one batch");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    uint64_t n_slots = 0;
+    if (int rc = check_offsets(c, d_off, n, "a read is longer than 2^31 bases", &n_slots, false)) return rc;
+    if (int rc = ensure_pack_bufs(c, n, n_slots)) return rc;
+    HIPCHK(c, hipMemsetAsync(c->packed.as<uint32_t>() + n_slots * 2, 0, 64, s));
+    launch_pack(s, d_bases, d_off, c->slot_off.as<uint64_t>(), n, c->packed.as<uint32_t>(), c->nmask.as<uint32_t>(), c->rlen.as<uint32_t>(),
+                c->ncount.as<uint32_t>());
+    // large batches: the probes shared between the reads of a locus (hdr_kernels.hip) -- a minimizer per read, one sort, one lane per
+    // read in that order, then the rewrite; small ones (and LEON_QUAL_ORDER=0, the measurement reference): every read for itself
+    const char* qo = getenv("LEON_QUAL_ORDER");
+    const bool in_file_order = qo && atoi(qo) == 0;
+    const ReadsDev R = reads_view(c, d_off, n);
+    if (!in_file_order && n >= 256) {
+        HIPCHK(c, c->sort_key.ensure(n * 4)); HIPCHK(c, c->sort_key2.ensure(n * 4));
+        HIPCHK(c, c->perm.ensure(n * 4)); HIPCHK(c, c->perm2.ensure(n * 4));
+        HIPCHK(c, c->hit_pos.ensure(n * 4));                    // (the minimizers' positions; the encode's per-read arrays are free between batches)
+        HIPCHK(c, c->events.ensure((n_slots + 4) * 4));         // (the flags)
+        HIPCHK(c, hipMemsetAsync(c->events.p, 0, (n_slots + 4) * 4, s));
+        // the reads of the batch this context encoded last (the CLI smooths a file right after its DNA stream): their ANCHORS are
+        // at hand and serve better than minimizers -- a read with a sequencing error in its minimizer lands in a cluster of its
+        // own, one with an error in an anchor k-mer simply has another anchor.  (Which k-mer a read is aligned on only decides
+        // who shares probes with whom, never a flag: stale anchors would cost time, not bytes; positions are range-checked.)
+        const bool anchors = n == c->last_n && d_bases == c->last_d_bases && d_off == c->last_d_off && c->shard_world == 1 && !c->poisoned;
+        if (anchors) launch_mpos_from_anchors(s, R, c->anchor_pos.as<int32_t>(), c->anchor_addr.as<uint32_t>(), c->flags.as<uint8_t>(),
+                                              c->sort_key.as<uint32_t>(), c->hit_pos.as<uint32_t>());
+        else launch_read_minimizer(s, R, c->sort_key.as<uint32_t>(), c->hit_pos.as<uint32_t>());
+        launch_iota(s, c->perm.as<uint32_t>(), n);
+        auto sort = [&](void* t, size_t& b) { return prim::SortPairs(t, b, c->sort_key.as<uint32_t>(), c->sort_key2.as<uint32_t>(), c->perm.as<uint32_t>(), c->perm2.as<uint32_t>(), n, 0, 32, s); };
+        if (int rc = run_prim(c, sort)) return rc;
+        launch_solid_flags(s, R, c->B, c->rv16(), c->perm2.as<uint32_t>(), c->hit_pos.as<uint32_t>(), c->events.as<uint32_t>());
+        launch_qual_rewrite(s, R, c->events.as<uint32_t>(), d_quals);
+    } else launch_qual_smooth(s, R, c->B, c->rv16(), d_quals);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s));
+    return LEON_OK;
+}
+
+int leon_qual_smooth_batch(leon_dna_ctx* c, const uint8_t* bases, const uint64_t* off, uint64_t n, uint8_t* quals) {
+    if (!c) return LEON_E_INVALID;
+    if (n == 0) return LEON_OK;
+    if (!bases || !off || !quals) return fail(c, LEON_E_INVALID, "null argument");
+    uint64_t nb = 0;
+    if (int rc = upload_host_batch(c, bases, off, n, nb)) return rc;
+    OwnBuf dq;
+    HIPCHK(c, dq.ensure(nb + 64));
+    if (nb) HIPCHK(c, hipMemcpy(dq.p, quals + off[0], nb, hipMemcpyHostToDevice));
+    if (int rc = leon_qual_smooth_batch_device(c, c->in_bases.as<uint8_t>(), c->in_off.as<uint64_t>(), n, dq.as<uint8_t>())) return rc;
+    if (nb) HIPCHK(c, hipMemcpy(quals + off[0], dq.p, nb, hipMemcpyDeviceToHost));
+    return LEON_OK;
+}
+
+// Header blocks: the symbols on the device (one wave per block, all blocks at once), the text on host threads
+extern "C++" { namespace leon {                                // (host_streams.cpp)
+int header_blocks_from_symbols(const uint8_t* syms, const uint64_t* sym_begin, const uint64_t* sym_count, const uint32_t* block_n_reads, uint64_t n_blocks,
+                               const uint8_t* first_header, uint64_t first_header_len, uint8_t* out, uint64_t out_cap, uint64_t* out_off,
+                               uint64_t* out_size, uint32_t n_threads);
+} }
+struct leon_header_symbols {
+    std::unique_ptr<uint8_t[]> syms;                             // every block's symbols, one byte each, block after block
+    std::vector<uint64_t> begin, count;                          // block b: syms[begin[b] .. + count[b])
+    bool overflowed = false;                                     // some block had more symbols than its share of the device buffer: decode the payloads on the host
+};
+
+// The front that the header decoders share: the payloads to the device, every block's share of the symbol buffer, the symbol
+// kernel on the context's stream (not waited for), and -- hdr_symbols_wait -- its verdict.
+struct HdrSymbolsDev {
+    OwnBuf pay, begin, count, syms, err;
+    BlockTableDev T;                                             // the payloads' places and reads per block
+    std::vector<uint64_t> sym_begin;                             // block b's share: syms[sym_begin[b] .. sym_begin[b + 1])
+};
+static int hdr_symbols_launch(leon_dna_ctx* c, const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads, uint64_t n_blocks, HdrSymbolsDev& D) {
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    if (int rc = block_table_to_device(c, payloads, payload_off, block_n_reads, n_blocks, D.pay, D.T)) return rc;
+    // a block's share of the symbol buffer: enough for the headers sequencers write (a dozen symbols each); a block that
+    // needs more (free text in every header) is left to the host decoder -- same result, its speed
+    D.sym_begin.assign(n_blocks + 1, 0);
+    for (uint64_t b = 0; b < n_blocks; b++)
+        D.sym_begin[b + 1] = D.sym_begin[b] + 24ull * block_n_reads[b] + 6 * (payload_off[b + 1] - payload_off[b]) + 256;   // (SRA-style headers: 12-17 symbols, ~6 bytes each)
+    const uint64_t sym_cap = D.sym_begin[n_blocks];
+    HIPCHK(c, D.begin.ensure((n_blocks + 1) * 8)); HIPCHK(c, D.count.ensure(n_blocks * 8));
+    HIPCHK(c, D.syms.ensure(sym_cap + 64)); HIPCHK(c, D.err.ensure(16));
+    HIPCHK(c, hipMemcpyAsync(D.begin.p, D.sym_begin.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(D.err.p, 0, 16, s));
+    launch_hdr_decode_symbols(s, D.pay.as<uint8_t>(), D.T.off.as<uint64_t>(), D.T.nreads.as<uint32_t>(), n_blocks, D.syms.as<uint8_t>(),
+                              D.begin.as<uint64_t>(), (unsigned long long*)D.count.p, D.err.as<int>());
+    HIPCHK(c, hipGetLastError());
+    return LEON_OK;
+}
+// the kernel's err[0]: 0, 1 some block's symbols did not fit its share (`overflowed`), 2 block err[1] is not a header stream (refused here)
+static int hdr_symbols_wait(leon_dna_ctx* c, HdrSymbolsDev& D, bool& overflowed) {
+    int err[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(err, D.err.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (err[0] == 2) return fail(c, LEON_E_INVALID, "header block " + std::to_string(err[1]) + " does not decode");
+    overflowed = err[0] == 1;
+    return LEON_OK;
+}
+
+int leon_header_decode_symbols(leon_dna_ctx* c, const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads, uint64_t n_blocks,
+                               leon_header_symbols** set) {
+    if (!c) return LEON_E_INVALID;
+    if (!set || (n_blocks && (!payloads || !payload_off || !block_n_reads))) return fail(c, LEON_E_INVALID, "null argument");
+    *set = nullptr;
+    std::unique_ptr<leon_header_symbols> H(new leon_header_symbols());
+    H->begin.assign(n_blocks + 1, 0); H->count.assign(n_blocks, 0);
+    if (!n_blocks) { *set = H.release(); return LEON_OK; }
+    HdrSymbolsDev D;
+    if (int rc = hdr_symbols_launch(c, payloads, payload_off, block_n_reads, n_blocks, D)) return rc;
+    hipStream_t s = c->stream;
+    if (int rc = hdr_symbols_wait(c, D, H->overflowed)) return rc;
+    if (H->overflowed) { *set = H.release(); return LEON_OK; }
+    HIPCHK(c, hipMemcpy(H->count.data(), D.count.p, n_blocks * 8, hipMemcpyDeviceToHost));
+    // only the symbols that were written come back (a block's share is mostly empty)
+    for (uint64_t b = 0; b < n_blocks; b++) H->begin[b + 1] = H->begin[b] + H->count[b];
+    H->syms.reset(new uint8_t[H->begin[n_blocks] + 1]);
+    for (uint64_t b = 0; b < n_blocks; b++)
+        if (H->count[b]) HIPCHK(c, hipMemcpyAsync(H->syms.get() + H->begin[b], D.syms.as<uint8_t>() + D.sym_begin[b], H->count[b], hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    *set = H.release();
+    return LEON_OK;
+}
+
+int leon_header_text_from_symbols(const leon_header_symbols* H, uint64_t first_block, uint64_t n_blocks, const uint32_t* block_n_reads,
+                                  const uint8_t* first_header, uint64_t first_header_len, uint8_t* out, uint64_t out_cap, uint64_t* out_off,
+                                  uint64_t* out_size, uint32_t n_threads) {
+    if (!H || !out_size || (n_blocks && (!block_n_reads || !out_off)) || (!first_header && first_header_len)) return dev_fail(LEON_E_INVALID, "null argument");
+    *out_size = 0;
+    if (first_block > H->count.size() || n_blocks > H->count.size() - first_block) return dev_fail(LEON_E_INVALID, "blocks beyond the symbol set");
+    if (H->overflowed) return dev_fail(LEON_E_STATE, "the set's symbols did not fit the device buffer: decode the payloads with leon_host_header_decode_blocks");
+    if (!n_blocks) return LEON_OK;
+    return leon::header_blocks_from_symbols(H->syms.get(), H->begin.data() + first_block, H->count.data() + first_block, block_n_reads, n_blocks, first_header,
+                                            first_header_len, out, out_cap, out_off, out_size, n_threads);
+}
+
+void leon_header_symbols_free(leon_header_symbols* H) { delete H; }
+
+int leon_header_decode_blocks(leon_dna_ctx* c, const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads, uint64_t n_blocks,
+                              const uint8_t* first_header, uint64_t first_header_len, uint8_t* out, uint64_t out_cap, uint64_t* out_off,
+                              uint64_t* out_size, uint32_t n_threads) {
+    if (!c) return LEON_E_INVALID;
+    if (!out_size || (n_blocks && (!payloads || !payload_off || !block_n_reads || !out_off)) || (!first_header && first_header_len))
+        return fail(c, LEON_E_INVALID, "null argument");
+    *out_size = 0;
+    if (!n_blocks) return LEON_OK;
+    leon_header_symbols* H = nullptr;
+    if (int rc = leon_header_decode_symbols(c, payloads, payload_off, block_n_reads, n_blocks, &H)) return rc;
+    std::unique_ptr<leon_header_symbols> own(H);
+    int rc;
+    if (H->overflowed)                                           // more symbols than a block's share: the host decodes the payloads itself
+        rc = leon_host_header_decode_blocks(payloads, payload_off, block_n_reads, n_blocks, first_header, first_header_len, out, out_cap, out_off, out_size, n_threads);
+    else
+        rc = leon_header_text_from_symbols(H, 0, n_blocks, block_n_reads, first_header, first_header_len, out, out_cap, out_off, out_size, n_threads);
+    if (rc != LEON_OK) c->err = leon_last_error(nullptr);
+    return rc;
+}
+
+// Header blocks, the text on the device too (k_hdr_text): what a set keeps, all of it in device memory
+struct leon_header_text {
+    int device = 0;
+    OwnBuf text, off;                                            // every block's headers back to back; off[reads + 1], counted from text's first byte
+    std::vector<uint64_t> text_begin, read0;                     // block b: text[text_begin[b] .. text_begin[b + 1]), off[read0[b] .. read0[b + 1]]
+    std::vector<uint32_t> status;                                // HT_OK, or why the kernel declined the block (kernels.h)
+    ~leon_header_text() { if (text.p || off.p) (void)hipSetDevice(device); }     // (for the members' release)
+};
+
+int leon_header_decode_text(leon_dna_ctx* c, const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads,
+                            const uint64_t* block_text_bytes, uint64_t n_blocks, const uint8_t* first_header, uint64_t first_header_len,
+                            leon_header_text** set) {
+    if (!c) return LEON_E_INVALID;
+    if (!set || (n_blocks && (!payloads || !payload_off || !block_n_reads)) || (!first_header && first_header_len)) return fail(c, LEON_E_INVALID, "null argument");
+    *set = nullptr;
+    std::unique_ptr<leon_header_text> T(new leon_header_text());
+    T->device = c->device;
+    T->text_begin.assign(n_blocks + 1, 0); T->read0.assign(n_blocks + 1, 0); T->status.assign(n_blocks, 0);
+    if (!n_blocks) { *set = T.release(); return LEON_OK; }
+    HdrSymbolsDev D;
+    if (int rc = hdr_symbols_launch(c, payloads, payload_off, block_n_reads, n_blocks, D)) return rc;
+    hipStream_t s = c->stream;
+    for (uint64_t b = 0; b < n_blocks; b++) T->read0[b + 1] = T->read0[b] + block_n_reads[b];
+    const uint64_t n_reads = T->read0[n_blocks];
+    // a first header beyond the kernel's cap is not uploaded: every block is declined by its length alone
+    const uint32_t first_len = (uint32_t)std::min<uint64_t>(first_header_len, (uint64_t)LEON_HT_HEADER_CAP + 1);
+    OwnBuf d_first, d_read0, d_tbegin, d_status, d_tsize;
+    HIPCHK(c, d_first.ensure(first_len + 64)); HIPCHK(c, d_read0.ensure((n_blocks + 1) * 8)); HIPCHK(c, d_tbegin.ensure((n_blocks + 1) * 8));
+    HIPCHK(c, d_status.ensure(n_blocks * 4)); HIPCHK(c, d_tsize.ensure(n_blocks * 8));
+    if (first_len) HIPCHK(c, hipMemcpyAsync(d_first.p, first_header, first_len, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_read0.p, T->read0.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, s));
+    auto text_kernel = [&](uint8_t* text, uint64_t* off) {
+        launch_hdr_text(s, D.syms.as<uint8_t>(), D.begin.as<uint64_t>(), (const unsigned long long*)D.count.p, D.T.nreads.as<uint32_t>(), d_read0.as<uint64_t>(),
+                        d_tbegin.as<uint64_t>(), n_blocks, d_first.as<uint8_t>(), first_len, text, off, d_status.as<uint32_t>(), d_tsize.as<uint64_t>());
+    };
+    std::vector<uint64_t> sizes;
+    if (!block_text_bytes) {                                     // the sizing pass: the same chains, nothing written but the counts
+        text_kernel(nullptr, nullptr);
+        HIPCHK(c, hipGetLastError());
+        sizes.resize(n_blocks);
+        HIPCHK(c, hipMemcpyAsync(sizes.data(), d_tsize.p, n_blocks * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        block_text_bytes = sizes.data();
+    }
+    for (uint64_t b = 0; b < n_blocks; b++) {
+        if (block_text_bytes[b] > (1ull << 48)) return fail(c, LEON_E_INVALID, "header block " + std::to_string(b) + ": text size out of range");
+        T->text_begin[b + 1] = T->text_begin[b] + block_text_bytes[b];
+    }
+    HIPCHK(c, T->text.ensure(T->text_begin[n_blocks] + 64)); HIPCHK(c, T->off.ensure((n_reads + 1) * 8));
+    HIPCHK(c, hipMemcpyAsync(d_tbegin.p, T->text_begin.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(T->off.p, 0, 8, s));
+    text_kernel(T->text.as<uint8_t>(), T->off.as<uint64_t>());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(T->status.data(), d_status.p, n_blocks * 4, hipMemcpyDeviceToHost, s));
+    bool overflowed = false;                                     // (such blocks carry their own status)
+    if (int rc = hdr_symbols_wait(c, D, overflowed)) return rc;
+    for (uint64_t b = 0; b < n_blocks; b++)
+        if (T->status[b] >= HT_INVALID) return fail(c, LEON_E_INVALID, "header block " + std::to_string(b) + " does not decode");
+    *set = T.release();
+    return LEON_OK;
+}
+
+// blocks [b0, b0 + nb) of the set into out / out_off, the offsets counted from `at` (the run's first byte in the caller's text)
+static int header_text_copy(const leon_header_text* T, uint64_t b0, uint64_t nb, uint8_t* out, uint64_t* out_off, uint64_t at) {
+    const uint64_t t0 = T->text_begin[b0], size = T->text_begin[b0 + nb] - t0, r0 = T->read0[b0], nr = T->read0[b0 + nb] - r0;
+    if (hipSetDevice(T->device) != hipSuccess) return dev_fail(LEON_E_HIP, "hipSetDevice");
+    if (staged_d2h(T->device, out, T->text.as<uint8_t>() + t0, size) != hipSuccess) return dev_fail(LEON_E_HIP, "header text: copy to the host failed");
+    if (staged_d2h(T->device, out_off, T->off.as<uint64_t>() + r0, (nr + 1) * 8) != hipSuccess) return dev_fail(LEON_E_HIP, "header offsets: copy to the host failed");
+    if (at != t0) for (uint64_t i = 0; i <= nr; i++) out_off[i] = out_off[i] - t0 + at;
+    return LEON_OK;
+}
+static int header_text_run(const leon_header_text* T, uint64_t first_block, uint64_t n_blocks) {
+    if (first_block > T->status.size() || n_blocks > T->status.size() - first_block) return dev_fail(LEON_E_INVALID, "blocks beyond the text set");
+    for (uint64_t b = first_block; b < first_block + n_blocks; b++)
+        if (T->status[b]) return dev_fail(LEON_E_STATE, "header block " + std::to_string(b) + " was not built on the device (reason " + std::to_string(T->status[b]) +
+                                      "): decode the payloads with leon_host_header_decode_blocks");
+    return LEON_OK;
+}
+
+int leon_header_text_fetch(const leon_header_text* T, uint64_t first_block, uint64_t n_blocks, uint8_t* out, uint64_t out_cap, uint64_t* out_off, uint64_t* out_size) {
+    if (!T || !out_size || (n_blocks && !out_off)) return dev_fail(LEON_E_INVALID, "null argument");
+    *out_size = 0;
+    if (int rc = header_text_run(T, first_block, n_blocks)) return rc;
+    if (!n_blocks) return LEON_OK;
+    const uint64_t size = T->text_begin[first_block + n_blocks] - T->text_begin[first_block];
+    *out_size = size;
+    if (size > out_cap || !out) return dev_fail(LEON_E_OVERFLOW, "header output needs " + std::to_string(size) + " bytes");
+    return header_text_copy(T, first_block, n_blocks, out, out_off, 0);
+}
+
+int leon_header_text_device_ptr(const leon_header_text* T, uint64_t first_block, uint64_t n_blocks, const uint8_t** d_text, const uint64_t** d_off, uint64_t* size) {
+    if (!T || !d_text || !d_off || !size) return dev_fail(LEON_E_INVALID, "null argument");
+    *d_text = nullptr; *d_off = nullptr; *size = 0;
+    if (int rc = header_text_run(T, first_block, n_blocks)) return rc;
+    if (!T->text.p) return LEON_OK;                              // a set of no blocks
+    *d_text = T->text.as<uint8_t>() + T->text_begin[first_block];
+    *d_off = T->off.as<uint64_t>() + T->read0[first_block];
+    *size = T->text_begin[first_block + n_blocks] - T->text_begin[first_block];
+    return LEON_OK;
+}
+
+void leon_header_text_free(leon_header_text* T) { delete T; }
+
+int leon_header_decode_blocks_device(leon_dna_ctx* c, const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* block_n_reads, uint64_t n_blocks,
+                                     const uint8_t* first_header, uint64_t first_header_len, uint8_t* out, uint64_t out_cap, uint64_t* out_off,
+                                     uint64_t* out_size, uint32_t n_threads, uint64_t* n_blocks_on_host) {
+    if (!c) return LEON_E_INVALID;
+    if (!out_size || (n_blocks && (!payloads || !payload_off || !block_n_reads || !out_off)) || (!first_header && first_header_len))
+        return fail(c, LEON_E_INVALID, "null argument");
+    *out_size = 0;
+    if (n_blocks_on_host) *n_blocks_on_host = 0;
+    if (!n_blocks) return LEON_OK;
+    leon_header_text* Tp = nullptr;
+    if (int rc = leon_header_decode_text(c, payloads, payload_off, block_n_reads, nullptr, n_blocks, first_header, first_header_len, &Tp)) return rc;
+    std::unique_ptr<leon_header_text> T(Tp);
+    // the blocks the kernel declined, run by run, through the host decoder from their payloads
+    struct HostRun { uint64_t b0, nb; std::vector<uint8_t> text; std::vector<uint64_t> off; uint64_t size; };
+    std::vector<HostRun> runs;
+    uint64_t on_host = 0;
+    for (uint64_t b = 0; b < n_blocks;) {
+        if (!T->status[b]) { b++; continue; }
+        HostRun R; R.b0 = b;
+        while (b < n_blocks && T->status[b]) b++;
+        R.nb = b - R.b0; on_host += R.nb;
+        R.off.assign(T->read0[R.b0 + R.nb] - T->read0[R.b0] + 1, 0);
+        R.text.resize((payload_off[R.b0 + R.nb] - payload_off[R.b0]) * 8 + 4096);
+        auto decode = [&](uint64_t b0, uint64_t nb) {
+            return leon_host_header_decode_blocks(payloads, payload_off + b0, block_n_reads + b0, nb, first_header, first_header_len, R.text.data(), R.text.size(),
+                                                  R.off.data(), &R.size, n_threads);
+        };
+        int rc = decode(R.b0, R.nb);
+        if (rc == LEON_E_OVERFLOW) { R.text.resize(R.size + 1); rc = decode(R.b0, R.nb); }
+        if (rc == LEON_E_INVALID && R.nb > 1) {                  // (the host decoder counts from the run's first block: name the block by its place in the call)
+            for (uint64_t k = 0; k < R.nb; k++)
+                if (decode(R.b0 + k, 1) == LEON_E_INVALID) return fail(c, LEON_E_INVALID, "header block " + std::to_string(R.b0 + k) + " does not decode");
+        }
+        if (rc == LEON_E_INVALID) return fail(c, LEON_E_INVALID, "header block " + std::to_string(R.b0) + " does not decode");
+        if (rc != LEON_OK) { c->err = leon_last_error(nullptr); return rc; }
+        runs.push_back(std::move(R));
+    }
+    if (n_blocks_on_host) *n_blocks_on_host = on_host;
+    uint64_t total = T->text_begin[n_blocks];
+    for (const HostRun& R : runs) total += R.size;
+    *out_size = total;
+    if (total > out_cap || !out) return fail(c, LEON_E_OVERFLOW, "header output needs " + std::to_string(total) + " bytes");
+    uint64_t at = 0, b = 0;
+    size_t next_run = 0;
+    out_off[0] = 0;
+    while (b < n_blocks) {
+        uint64_t* o = out_off + T->read0[b];
+        if (next_run < runs.size() && runs[next_run].b0 == b) {
+            const HostRun& R = runs[next_run++];
+            if (R.size) memcpy(out + at, R.text.data(), R.size);
+            for (size_t i = 0; i < R.off.size(); i++) o[i] = at + R.off[i];
+            at += R.size; b += R.nb;
+        } else {
+            const uint64_t e = next_run < runs.size() ? runs[next_run].b0 : n_blocks;
+            if (int rc = header_text_copy(T.get(), b, e - b, out + at, o, at)) { c->err = leon_last_error(nullptr); return rc; }
+            at += T->text_begin[e] - T->text_begin[b]; b = e;
+        }
+    }
+    return LEON_OK;
+}
+}  // extern "C"

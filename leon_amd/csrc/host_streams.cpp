@@ -44,7 +44,7 @@ uint32_t usable_cpus() {
     return n;
 }
 }  // namespace
-namespace leon { uint32_t usable_cpus() { return ::usable_cpus(); } }       // (capi.hip sizes its host-chain pool by it)
+namespace leon { uint32_t usable_cpus() { return ::usable_cpus(); } }       // (rc_kernels.hip sizes its host-chain pool by it)
 namespace {
 
 template <typename F> void parallel_blocks(uint64_t n_blocks, uint32_t n_threads, F&& f) {
@@ -262,7 +262,7 @@ int header_blocks_common(uint64_t n_blocks, uint8_t* out, uint64_t out_cap, uint
 }  // namespace
 
 namespace leon {
-// the text of header blocks whose symbols the device has decoded (capi.hip, leon_header_decode_blocks): block b's symbols are
+// the text of header blocks whose symbols the device has decoded (hdr_kernels.hip, leon_header_decode_blocks): block b's symbols are
 // syms[sym_begin[b] .. + sym_count[b]), one byte each, in the order the HeaderDecoder asks for them
 int header_blocks_from_symbols(const uint8_t* syms, const uint64_t* sym_begin, const uint64_t* sym_count, const uint32_t* block_n_reads, uint64_t n_blocks,
                                const uint8_t* first_header, uint64_t first_header_len, uint8_t* out, uint64_t out_cap, uint64_t* out_off,

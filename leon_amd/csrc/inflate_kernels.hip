@@ -625,7 +625,7 @@ extern "C" int leon_qual_inflate_blocks_device(int device_id, const uint8_t* pay
         cut.push_back(e); b = e;
     }
     if (max_tiles >= (1ull << 31)) return dev_fail(LEON_E_INVALID, "implausible block sizes");
-    TmpBuf d_pay, d_text, d_blk, d_status, d_adler, d_tile_nl, d_nl_before, d_sums, d_last, d_tmp, d_cnt, d_off_own;
+    OwnBuf d_pay, d_text, d_blk, d_status, d_adler, d_tile_nl, d_nl_before, d_sums, d_last, d_tmp, d_cnt, d_off_own;
     DEVCHK(d_pay.ensure(max_pay + 64)); DEVCHK(d_text.ensure(max_text + 64));
     DEVCHK(d_blk.ensure((max_blocks + 1) * sizeof(QiBlock)));
     DEVCHK(d_status.ensure(max_blocks * 4)); DEVCHK(d_adler.ensure(max_blocks * 4)); DEVCHK(d_last.ensure(max_blocks * 4));
@@ -713,7 +713,7 @@ extern "C" int leon_bgzf_inflate_device(int device_id, const uint8_t* bytes, uin
         for (uint64_t i = b0; i < b1; i++) tmp += share(i);
         max_pay = std::max(max_pay, member_off[b1] - member_off[b0]); max_tmp = std::max(max_tmp, tmp); max_nb = std::max(max_nb, b1 - b0);
     }
-    TmpBuf d_pay, d_tmp, d_blk, d_status, d_seg, d_acc, d_cnt;
+    OwnBuf d_pay, d_tmp, d_blk, d_status, d_seg, d_acc, d_cnt;
     DEVCHK(d_pay.ensure(max_pay + 64)); DEVCHK(d_tmp.ensure(max_tmp + 64));
     DEVCHK(d_blk.ensure((max_nb + 1) * sizeof(QiBlock)));
     DEVCHK(d_status.ensure(max_nb * 4)); DEVCHK(d_seg.ensure((2 * max_nb + 1) * 8)); DEVCHK(d_acc.ensure(2 * max_nb * 4));

@@ -70,6 +70,7 @@ struct ResolveDev {
     uint32_t* ins_flag;          // per read of the current window
 };
 
+void launch_iota(hipStream_t s, uint32_t* v, uint64_t n);         // v[i] = i, the permutation a sort then carries (the walk, the quality smoothing): kmer_kernels.hip
 // ---- bloom ----
 void launch_bloom_insert(hipStream_t s, BloomDev B, const uint16_t* rv16, const uint64_t* kmers, uint64_t n);
 void launch_bloom_query(hipStream_t s, BloomDev B, const uint16_t* rv16, const uint64_t* kmers, uint64_t n,
@@ -215,7 +216,7 @@ constexpr uint64_t FASTQ_MAX_GROUPS = 1024;                    // the grid's cap
 constexpr uint32_t DICT_PIECES_MAX_GROUPS = 1024;              // the grid's cap: a wave codes 64 pieces (lane = piece), then the 64 a grid further on
 // the pieces of d_kmers coded on stream s into d_dst, piece_off (host, n_pieces + 1 entries) where each begins: leon_dna_finish (capi.hip)
 // and leon_anchor_dict_encode_pieces_device share it.  LEON_OK, or the code with `why`
-struct TmpBuf;
-int dict_pieces_code(hipStream_t s, const uint64_t* d_kmers, uint64_t n_anchors, uint32_t k, uint32_t P, uint64_t* piece_off, TmpBuf& d_dst, std::string& why);
+struct OwnBuf;
+int dict_pieces_code(hipStream_t s, const uint64_t* d_kmers, uint64_t n_anchors, uint32_t k, uint32_t P, uint64_t* piece_off, OwnBuf& d_dst, std::string& why);
 
 }  // namespace leon

@@ -246,6 +246,13 @@ struct Buf {
 uint32_t grid(uint64_t n, uint32_t per = 256, uint32_t cap = 8192) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + per - 1) / per, cap)); }
 
 }  // namespace
+
+__global__ void k_iota(uint32_t* v, uint64_t n) {
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) v[i] = (uint32_t)i;
+}
+void launch_iota(hipStream_t s, uint32_t* v, uint64_t n) {
+    hipLaunchKernelGGL(k_iota, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 8192)), dim3(256), 0, s, v, n);
+}
 }  // namespace leon
 
 using namespace leon;

@@ -278,7 +278,7 @@ Tiles lt_tiles(const uint8_t* d, uint64_t n, uint32_t extra) {
 }
 
 // k_letters_count and k_letters_scan over the buffer: the totals to the host, the per-workgroup words left on the device for take
-struct Counted { TmpBuf cnt, before, base, total; Tiles T; uint64_t totals[2] = {0, 0}; };
+struct Counted { OwnBuf cnt, before, base, total; Tiles T; uint64_t totals[2] = {0, 0}; };
 int lt_count(hipStream_t s, const uint8_t* d_bases, uint64_t n_bytes, Counted& C) {
     C.T = lt_tiles(d_bases, n_bytes, 1);
     DEVCHK(C.cnt.ensure(C.T.groups * 16ull)); DEVCHK(C.before.ensure(C.T.groups * 4ull)); DEVCHK(C.base.ensure(C.T.groups * 16ull)); DEVCHK(C.total.ensure(16));
@@ -327,7 +327,7 @@ int leon_letters_take_device(int device_id, uint8_t* d_bases, uint64_t n_bytes, 
     if (const int rc = lt_count(s, d_bases, n_bytes, C)) return rc;
     if (C.totals[0] != n_runs || C.totals[1] != n_odd) return differs(C.totals[0], C.totals[1]);      // (nothing was written so far)
     if (!n_runs && !n_odd) return LEON_OK;                        // the bytes are their own folded form
-    TmpBuf d_runs, d_pos, d_byte;
+    OwnBuf d_runs, d_pos, d_byte;
     // (at least 8 bytes each: a kernel argument is never null, even for an empty table)
     DEVCHK(d_runs.ensure(std::max<uint64_t>(n_runs * 16, 8))); DEVCHK(d_pos.ensure(std::max<uint64_t>(n_odd * 8, 8))); DEVCHK(d_byte.ensure(std::max<uint64_t>(n_odd, 8)));
     hipLaunchKernelGGL(k_letters_take, dim3(C.T.groups), dim3(LT_THREADS), 0, s, d_bases, n_bytes, C.T.n_tiles, C.T.per, C.base.as<ull>(), C.before.as<uint32_t>(),
@@ -346,7 +346,7 @@ int leon_letters_apply_device(int device_id, uint8_t* d_bases, uint64_t n_bytes,
     CallStream st;
     if (const int rc = dev_open("leon_letters_apply_device", device_id, st)) return rc;
     hipStream_t s = st.s;
-    TmpBuf d_runs, d_pos, d_byte;
+    OwnBuf d_runs, d_pos, d_byte;
     if (n_runs) {
         DEVCHK(d_runs.ensure(n_runs * 16));
         DEVCHK(hipMemcpyAsync(d_runs.p, runs, n_runs * 16, hipMemcpyHostToDevice, s));

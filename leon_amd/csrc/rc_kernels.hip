@@ -7,10 +7,13 @@
 //     range /= total; low += cumLow*range; range *= freq; renormalise
 //     with one multiply-high by the precomputed reciprocal instead of a 64-bit division.
 // Counts are exactly Order0Model's cumulative counts (its rescale cannot trigger: MAX_RANGE = 2^48 total).
-#include "kernels.h"
+#include "ctx.h"
 #include "rc_model.h"
-#include <algorithm>
-#include <cstdlib>
+#include "prim.h"
+#include <atomic>
+#include <cstring>
+#include <mutex>
+#include <thread>
 
 namespace leon {
 
@@ -605,4 +608,328 @@ void launch_rc_encode(hipStream_t s, const uint8_t* syms, const uint64_t* blk_be
 #undef RC_LAUNCH
 }
 
+// ---- the context's calls that end in this file's kernels (ctx.h): the block-coding tail of a stream and the raw range coder ----
+uint32_t usable_cpus();                                          // (host_streams.cpp)
+namespace {
+constexpr uint32_t kRbHostChainsErr = 500;   // slot of the pinned read-back words (h_rb, 512 of them) the host chains' first chunk brings the modelers' error flag to
+// Launches of at most this many blocks have their chains coded on host cores (0 = never): LEON_RC_HOST_BLOCKS, default 400.
+// With 2 000 blocks (8 per CU) the device's chains all run at once and win: 126 ms for 2.3 G symbols is 18 G symbols/s, 16 host cores at ~2.3 ns do 7.
+uint64_t rc_host_blocks() {
+    if (const char* e = getenv("LEON_RC_HOST_BLOCKS")) return (uint64_t)std::max<long long>(0, atoll(e));
+    return 400;
+}
+uint32_t rc_host_threads(uint64_t n_blocks, uint32_t world) {
+    // (all but one of the process's CPUs: the dictionary chain and its helpers are busy for the first part of a small file's step only --
+    // configuration #2, 200 blocks: 88.9 ms with 12 threads and 4 chunks, 73.4 with 15 and 8, 63.9 with 15 and 16; profiles/r4_hostchains_sweep_config2.txt.
+    // A rank of a job of `world` (leon_dna_set_shard: the GPUs of ONE node) shares the host, and its CPU quota, with the others: an equal share of
+    // what rank 0's dictionary chain and its helpers leave.  Eight ranks taking 32 threads each would run the cgroup out of its quota, and the
+    // throttling that follows stops the chain -- the one thing the job's step waits for -- along with everything else.)
+    const uint32_t cpus = usable_cpus();
+    uint32_t n_thr = world > 1 ? std::max<uint32_t>(2, (cpus > 6 ? cpus - 6 : 0) / world) : (cpus > 2 ? cpus - 1 : 2);
+    n_thr = std::max<uint32_t>(2, std::min<uint32_t>(32, n_thr));
+    if (const char* e = getenv("LEON_RC_HOST_THREADS")) { const int v = atoi(e); if (v >= 1 && v <= 256) n_thr = (uint32_t)v; }
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_thr, n_blocks));
+}
+// Who codes a launch's chains.  The device's coder waves take about as long as the LONGEST block's chain whatever the number of
+// blocks (~100 ns per symbol of it, up to 8 blocks per CU); the host's way takes the slowest of three things that run side by side --
+// the modelers' pass over the longest block (four waves per block since round 5), the records' 8 bytes per symbol over PCIe, the host
+// threads' chains (two side by side per thread) -- a chunk behind one another.  10 M reads of 150 bp in 200 blocks: 116 against ~42 ms,
+// the host (measured 134 and 45); 20 M reads of 250 bp in 400 blocks of 1.9 M symbols: 190 against ~140 (measured 174 and 142): left to the device, see below.
+bool rc_on_host(uint64_t n_blocks, uint64_t n_syms, uint64_t max_block_syms, uint32_t world) {
+    if (!n_blocks || n_blocks > rc_host_blocks() || max_block_syms + 1024 >= (1ull << HB_COUNT_BITS) || n_syms * 8 > (12ull << 30)) return false;
+    if (getenv("LEON_RC_HOST_BLOCKS")) return true;              // (asked for by name: the tests, measurements)
+    const double device_ns = 100.0 * (double)max_block_syms * (double)((n_blocks + 2047) / 2048);
+    // (round 5: four modeler waves per block -- ~12 ns per symbol of the longest block --, the records' 8 bytes per symbol over PCIe at ~52 GB/s,
+    // the chains two side by side per thread at ~2.6 ns per symbol; whichever is slowest, a sixteenth later for the first chunk's way in)
+    const double thr = (double)rc_host_threads(n_blocks, world);
+    const double host_ns = 1.0625 * std::max(12.0 * (double)max_block_syms, std::max(0.16 * (double)n_syms, 2.6 * (double)n_syms / thr));
+    // (a near tie goes to the device: the host's cores have other work -- the dictionary chain, which is what a step waits for: at the k = 63 / 250 bp
+    // shape, 400 blocks of 1.9 M symbols, the host's way takes 142 ms against the device's 174 and the step 554 ms against 542)
+    return host_ns < 0.7 * device_ns;
+}
+
+// The range coder stage of a small launch: the device's modeler waves turn the symbols of every block into records, chunk of tiles
+// by chunk; a chunk crosses PCIe while the next is modelled, and host threads -- each owning every n-th block -- code it while the
+// one after that crosses.  On return c->hb.coders[b] holds block b's payload.  Bytes: exactly k_rc_encode's (the tests run both).
+int rc_blocks_on_host(leon_dna_ctx* c, const uint8_t* d_syms, const uint64_t* d_blk_begin, uint64_t nbl, uint64_t n_syms, uint32_t small_sizes,
+                      uint32_t n_small) {
+    hipStream_t s = c->stream;
+    HostChains& H = c->hb;
+    if (!H.copy_stream) {
+        // A stream of HIGH priority: the runtime maps streams onto a few hardware queues, and in a process that also holds a
+        // communicator's streams (RCCL: every rank of an N-rank job) this one landed on the queue of `s` -- every chunk's copy then
+        // waited behind all sixteen modeler launches and the chains started when the modelers had finished (a seat of 8: 110 ms for
+        // the stage instead of ~75).  Streams of another priority get queues of their own.
+        int lo = 0, hi = 0;
+        HIPCHK(c, hipDeviceGetStreamPriorityRange(&lo, &hi));
+        HIPCHK(c, hipStreamCreateWithPriority(&H.copy_stream.s, hipStreamNonBlocking, hi));
+    }
+    std::vector<uint64_t> bb(nbl + 1);
+    HIPCHK(c, hipMemcpyAsync(bb.data(), d_blk_begin, (nbl + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    uint64_t max_tiles = 0;
+    for (uint64_t b = 0; b < nbl; b++) max_tiles = std::max<uint64_t>(max_tiles, (bb[b + 1] - bb[b] + 63) / 64);
+    uint32_t n_chunks = 16;                                      // (a chunk = a pipeline stage: the first must be modelled and cross before a chain starts, the last is coded after everything)
+    if (const char* e = getenv("LEON_RC_HOST_CHUNKS")) { const int v = atoi(e); if (v >= 1 && v <= 64) n_chunks = (uint32_t)v; }
+    n_chunks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_chunks, max_tiles));
+    const uint64_t Tc = (max_tiles + n_chunks - 1) / std::max<uint32_t>(n_chunks, 1);
+    // where block b's records of chunk ch lie inside the chunk, and the chunks inside the pinned buffer
+    std::vector<uint64_t> rec_off((size_t)n_chunks * nbl), rec_cnt((size_t)n_chunks * nbl), chunk_base(n_chunks + 1, 0);
+    uint64_t chunk_max = 0;
+    for (uint32_t ch = 0; ch < n_chunks; ch++) {
+        uint64_t at = 0;
+        for (uint64_t b = 0; b < nbl; b++) {
+            const uint64_t len = bb[b + 1] - bb[b], a0 = std::min<uint64_t>(len, ch * Tc * 64), a1 = std::min<uint64_t>(len, (ch + 1) * Tc * 64);
+            rec_off[(size_t)ch * nbl + b] = at; rec_cnt[(size_t)ch * nbl + b] = a1 - a0;
+            at += a1 - a0;
+        }
+        chunk_base[ch + 1] = chunk_base[ch] + at;
+        chunk_max = std::max(chunk_max, at);
+    }
+    if (chunk_base[n_chunks] != n_syms) return fail(c, LEON_E_STATE, "block symbol ranges do not add up (internal error)");
+    // (memory this way needs and the device's coder does not: when it is not to be had, the caller takes the device's coder -- return 1)
+    auto no_room = [&](hipError_t e) { if (e == hipSuccess) return false; (void)hipGetLastError(); return true; };
+    for (auto& b : H.recs) if (no_room(b.ensure(chunk_max * 8 + 64))) return 1;
+    if (no_room(H.recoff.ensure((size_t)n_chunks * nbl * 8)) || no_room(H.state.ensure(rc_records_state_bytes(nbl)))) return 1;
+    HIPCHK(c, c->rc_scratch.ensure(rc_model_scratch_bytes(nbl)));
+    if (n_syms * 8 + 64 > H.h_recs.cap) HIPCHK(c, H.h_recs.release());       // (only the allocation may send the launch to the device's coder)
+    if (no_room(H.h_recs.ensure(n_syms * 8 + 64, n_syms * 8 + n_syms + 4096))) return 1;
+    HIPCHK(c, H.ev.ensure(2 * (size_t)n_chunks));
+    HIPCHK(c, hipMemcpyAsync(H.recoff.p, rec_off.data(), rec_off.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->errflag.p, 0, 4, s));
+    if (H.coders.size() < nbl) H.coders.resize(nbl);
+    // the host threads
+    const uint32_t n_thr = rc_host_threads(nbl, c->shard_world);
+    static const bool trace = getenv("LEON_TRACE_RC_HOST") != nullptr;     // measurement aid: when each chunk was modelled / had crossed / was coded, on stderr
+    const auto t_begin = std::chrono::steady_clock::now();
+    auto ms_now = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
+    std::vector<double> t_coded(n_chunks, 0.0), t_copied(n_chunks, 0.0);
+    std::mutex trace_mu;
+    (void)hb_recip_table();                                      // (built before the threads ask for it)
+    std::atomic<uint32_t> chunks_ready{0};
+    std::atomic<int> abort_flag{0};
+    std::vector<std::thread> workers;
+    uint64_t* const h_recs = H.h_recs.as<uint64_t>();
+    HostBlockCoder* const coders = H.coders.data();
+    for (uint32_t w = 0; w < n_thr; w++)
+        workers.emplace_back([&, w] {
+            try {
+            for (uint64_t b = w; b < nbl; b += n_thr) coders[b].start(small_sizes, n_small);
+            for (uint32_t ch = 0; ch < n_chunks; ch++) {
+                for (uint32_t spin = 0; chunks_ready.load(std::memory_order_acquire) <= ch; spin++) {
+                    if (abort_flag.load()) return;
+                    if (spin < 2000) __builtin_ia32_pause(); else std::this_thread::yield();
+                }
+                // two of the thread's blocks side by side (HostBlockCoder::code2: two dependent chains fill the core one leaves half idle)
+                static const bool pairs = [] { const char* e = getenv("LEON_RC_HOST_PAIRS"); return !(e && e[0] == '0'); }();
+                for (uint64_t b = w; b < nbl; b += 2 * (uint64_t)n_thr) {
+                    const uint64_t b2 = b + n_thr;
+                    const uint64_t* ra = h_recs + chunk_base[ch] + rec_off[(size_t)ch * nbl + b];
+                    if (b2 < nbl && pairs) HostBlockCoder::code2(coders[b], ra, rec_cnt[(size_t)ch * nbl + b], coders[b2], h_recs + chunk_base[ch] + rec_off[(size_t)ch * nbl + b2], rec_cnt[(size_t)ch * nbl + b2]);
+                    else {
+                        coders[b].code(ra, rec_cnt[(size_t)ch * nbl + b]);
+                        if (b2 < nbl) coders[b2].code(h_recs + chunk_base[ch] + rec_off[(size_t)ch * nbl + b2], rec_cnt[(size_t)ch * nbl + b2]);
+                    }
+                }
+                if (trace) { const double t = ms_now(); std::lock_guard<std::mutex> g(trace_mu); t_coded[ch] = std::max(t_coded[ch], t); }
+            }
+            for (uint64_t b = w; b < nbl; b += n_thr) coders[b].flush();
+            } catch (...) { abort_flag.store(2); }               // (an output buffer that could not grow: the call fails, nothing is thrown across threads)
+        });
+    struct Join { std::vector<std::thread>& t; std::atomic<int>& a; bool ok = false; ~Join() { if (!ok) a.store(1); for (auto& x : t) if (x.joinable()) x.join(); } } join{workers, abort_flag};
+    for (uint32_t ch = 0; ch < n_chunks; ch++) {
+        if (ch >= 2) HIPCHK(c, hipStreamWaitEvent(s, H.ev[2 * (ch - 2) + 1], 0));            // the buffer's previous chunk has left it
+        launch_rc_records(s, d_syms, d_blk_begin, nbl, (uint32_t)(ch * Tc), (uint32_t)((ch + 1) * Tc), H.recs[ch & 1].as<uint64_t>(),
+                          H.recoff.as<uint64_t>() + (size_t)ch * nbl, H.state.as<uint32_t>(), c->rc_scratch.as<uint32_t>(), c->errflag.as<int>(), small_sizes);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(H.ev[2 * ch], s));
+        HIPCHK(c, hipStreamWaitEvent(H.copy_stream, H.ev[2 * ch], 0));
+        const uint64_t bytes = (chunk_base[ch + 1] - chunk_base[ch]) * 8;
+        if (bytes) HIPCHK(c, hipMemcpyAsync(h_recs + chunk_base[ch], H.recs[ch & 1].p, bytes, hipMemcpyDeviceToHost, H.copy_stream));
+        // (the modelers' one refusal travels with the first chunk, on this stream: a blocking hipMemcpy of the flag waited for EVERY launch
+        // queued on `s` in a process that holds a communicator -- each rank of an N-rank job --, and the chains began when the modelers had finished)
+        if (ch == 0) HIPCHK(c, hipMemcpyAsync(c->rb() + kRbHostChainsErr, c->errflag.p, 4, hipMemcpyDeviceToHost, H.copy_stream));
+        HIPCHK(c, hipEventRecord(H.ev[2 * ch + 1], H.copy_stream));
+    }
+    const double t_enqueued = ms_now();
+    for (uint32_t ch = 0; ch < n_chunks; ch++) {
+        HIPCHK(c, hipEventSynchronize(H.ev[2 * ch + 1]));
+        if (ch == 0 && (int)(uint32_t)c->rb()[kRbHostChainsErr]) return fail(c, LEON_E_OVERFLOW, "a block has more symbols than the host chains' records can count");
+        chunks_ready.store(ch + 1, std::memory_order_release);
+        t_copied[ch] = ms_now();
+    }
+    for (auto& t : workers) t.join();
+    join.ok = true;
+    if (abort_flag.load() == 2) return fail(c, LEON_E_OVERFLOW, "a host chain ran out of memory for its output");
+    if (trace) {
+        fprintf(stderr, "[leon rc host] %llu blocks, %llu symbols, %u chunks, %u threads, launches enqueued at %.1f ms:", (unsigned long long)nbl, (unsigned long long)n_syms, n_chunks, n_thr, t_enqueued);
+        for (uint32_t ch = 0; ch < n_chunks; ch++) fprintf(stderr, " chunk %u in host memory at %.1f ms, coded at %.1f;", ch, t_copied[ch], t_coded[ch]);
+        fprintf(stderr, " done at %.1f ms\n", ms_now());
+    }
+    return LEON_OK;
+}
+
+}  // namespace
+int ensure_block_bufs(leon_dna_ctx* c, uint64_t nbl) {                  // the blocks' symbol ranges and payload offsets
+    HIPCHK(c, c->blk_begin.ensure((nbl + 1) * 8)); HIPCHK(c, c->out_off.ensure((nbl + 1) * 8));
+    HIPCHK(c, c->out_size.ensure(nbl * 8)); HIPCHK(c, c->dst_off.ensure((nbl + 1) * 8));
+    return LEON_OK;
+}
+int ensure_rc_bufs(leon_dna_ctx* c, uint64_t nbl, uint64_t n_syms) {     // k_rc_encode's output and models
+    HIPCHK(c, c->rc_out.ensure(3 * n_syms + 72 * (nbl + 1)));
+    HIPCHK(c, c->rc_scratch.ensure(rc_model_scratch_bytes(nbl)));
+    return LEON_OK;
+}
+
+// The block-coding tail of a stream, the DNA stream's and the header stream's: the share's symbols, counted then emitted by `symbols`
+// (nullptr: the count pass; the counts, then the offsets, in c->sym_off indexed from the share's first read), cut into blocks, the blocks'
+// chains coded on host cores or by k_rc_encode, the payloads brought to host memory.  ev[6] / [7] / [8]: symbols / range coder / D2H done.
+int code_blocks(leon_dna_ctx* c, const Share& sh, const std::function<void(uint8_t* syms)>& symbols, uint32_t small_sizes, bool counts_apart,
+                const char* unit, CodedBlocks& out) {
+    hipStream_t s = c->stream;
+    const uint64_t rpb = c->cfg.reads_per_block, nl = sh.nl, nbl = sh.nbl;
+    HIPCHK(c, c->sym_off.ensure((nl + 1) * 8));
+    uint64_t* const sym_off = c->sym_off.as<uint64_t>();
+    HIPCHK(c, hipMemsetAsync(sym_off + nl, 0, 8, s));
+    symbols(nullptr);
+    if (int rc = run_prim(c, [&](void* t, size_t& b) { return prim::ExclusiveSum(t, b, sym_off, sym_off, nl + 1, s); })) return rc;
+    uint64_t max_block_syms = 0; unsigned long long* d_max = reinterpret_cast<unsigned long long*>(c->counters.as<uint32_t>() + 8);
+    HIPCHK(c, hipMemsetAsync(d_max, 0, 8, s));
+    launch_max_block_syms(s, sym_off, nl, rpb, nbl, d_max);
+    HIPCHK(c, hipMemcpyAsync(&out.n_syms, sym_off + nl, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(&max_block_syms, d_max, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const uint64_t n_syms = out.n_syms;
+    HIPCHK(c, c->syms.ensure(n_syms * 2 + 256));
+    symbols(c->syms.as<uint8_t>());
+    if (int rc = ensure_block_bufs(c, nbl)) return rc;
+    launch_block_ranges(s, sym_off, nl, rpb, nbl, c->blk_begin.as<uint64_t>(), c->out_off.as<uint64_t>());
+    HIPCHK(c, hipEventRecord(c->ev[6], s));
+
+    // ---- range coder ----
+    out.sizes.assign(nbl, 0); out.dst.assign(nbl + 1, 0);
+    out.host_chains = rc_on_host(nbl, n_syms, max_block_syms, c->shard_world);
+    if (out.host_chains) {
+        // a small launch: the chains run on host cores, from the modelers' records (host_blocks.h)
+        const int rc = rc_blocks_on_host(c, c->syms.as<uint8_t>(), c->blk_begin.as<uint64_t>(), nbl, n_syms, small_sizes, N_SMALL_MODELS);
+        if (rc == 1) out.host_chains = false;                    // (no room for the records: the device's coder)
+        else if (rc) return rc;
+    }
+    if (out.host_chains) {
+        HIPCHK(c, hipEventRecord(c->ev[7], s));
+        for (uint64_t b = 0; b < nbl; b++) out.sizes[b] = c->hb.coders[b].size();
+    } else {
+        if (int rc = ensure_rc_bufs(c, nbl, n_syms)) return rc;
+        HIPCHK(c, hipMemsetAsync(c->errflag.p, 0, 4, s));
+        launch_rc_encode(s, c->syms.as<uint8_t>(), c->blk_begin.as<uint64_t>(), nbl, c->rc_out.as<uint8_t>(), c->out_off.as<uint64_t>(),
+                         c->out_size.as<uint64_t>(), c->rc_scratch.as<uint32_t>(), c->errflag.as<int>(), max_block_syms, small_sizes, counts_apart);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->ev[7], s));
+        int errflag = 0;
+        HIPCHK(c, hipMemcpyAsync(out.sizes.data(), c->out_size.p, nbl * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&errflag, c->errflag.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        if (errflag == 3) return fail(c, LEON_E_STATE, "a numeric value's byte count above 8 in the symbol stream (internal error)");   // (counts_apart only)
+        if (errflag) return fail(c, LEON_E_OVERFLOW, errflag == 2 ? std::string("a ") + unit + " block has 2^32 symbols or more"
+                                                                  : std::string("range coder output exceeded its 3 bytes/symbol bound"));
+    }
+    for (uint64_t b = 0; b < nbl; b++) out.dst[b + 1] = out.dst[b] + out.sizes[b];
+    const uint64_t payload_bytes = out.payload_bytes = out.dst[nbl];
+    if (!out.host_chains) {
+        // ---- gather + D2H ----
+        HIPCHK(c, c->payload.ensure(payload_bytes + 16));
+        HIPCHK(c, hipMemcpyAsync(c->dst_off.p, out.dst.data(), (nbl + 1) * 8, hipMemcpyHostToDevice, s));
+        launch_gather_payload(s, c->rc_out.as<uint8_t>(), c->out_off.as<uint64_t>(), c->dst_off.as<uint64_t>(), c->out_size.as<uint64_t>(),
+                              nbl, c->payload.as<uint8_t>());
+        HIPCHK(c, c->h_payload.ensure(payload_bytes + 16, payload_bytes + payload_bytes / 4 + 4096));
+        HIPCHK(c, hipMemcpyAsync(c->h_payload.p, c->payload.p, payload_bytes, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(c, hipEventRecord(c->ev[8], s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return LEON_OK;
+}
+
+// Leon::writeBlock, in block order, the batch's first block numbered first_block; a sink that refuses one poisons the stream
+int deliver_blocks(leon_dna_ctx* c, const CodedBlocks& out, const Share& sh, uint64_t n, uint64_t first_block, leon_block_sink sink, void* user) {
+    const uint64_t rpb = c->cfg.reads_per_block;
+    for (uint64_t b = 0; b < sh.nbl; b++) {
+        const uint32_t nr = (uint32_t)std::min<uint64_t>(rpb, n - (sh.lb0 + b) * rpb);
+        const uint8_t* pay = out.host_chains ? c->hb.coders[b].data() : c->h_payload.as<uint8_t>() + out.dst[b];
+        if (sink(user, first_block + sh.lb0 + b, pay, out.sizes[b], nr)) {
+            c->poisoned = true;                                  // the caller holds part of the batch's blocks
+            return fail(c, LEON_E_SINK, "block sink returned non-zero");
+        }
+    }
+    return LEON_OK;
+}
+
+int RcStreamsDev::code(leon_dna_ctx* c, const uint8_t* d_syms, const uint64_t* begin_host, uint64_t n_streams, uint64_t longest, const char* overflow,
+                       uint64_t* sizes) {
+    hipStream_t s = c->stream;
+    HIPCHK(c, begin.ensure((n_streams + 1) * 8)); HIPCHK(c, d_off.ensure((n_streams + 1) * 8));
+    HIPCHK(c, size.ensure(n_streams * 8)); HIPCHK(c, scr.ensure(rc_model_scratch_bytes(n_streams)));
+    off.resize(n_streams + 1);
+    for (uint64_t b = 0; b <= n_streams; b++) off[b] = ((3 * begin_host[b] + 7) & ~7ull) + 64 * b;
+    HIPCHK(c, out.ensure(off[n_streams] + 64));
+    HIPCHK(c, hipMemcpy(begin.p, begin_host, (n_streams + 1) * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_off.p, off.data(), (n_streams + 1) * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemsetAsync(c->errflag.p, 0, 4, s));
+    launch_rc_encode(s, d_syms, begin.as<uint64_t>(), n_streams, out.as<uint8_t>(), d_off.as<uint64_t>(), size.as<uint64_t>(), scr.as<uint32_t>(),
+                     c->errflag.as<int>(), longest);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s));
+    int errflag = 0;
+    HIPCHK(c, hipMemcpy(&errflag, c->errflag.p, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(sizes, size.p, n_streams * 8, hipMemcpyDeviceToHost));
+    return errflag ? fail(c, LEON_E_OVERFLOW, overflow) : LEON_OK;
+}
 }  // namespace leon
+
+using namespace leon;
+extern "C" {
+// ------------------------------------------------------------------------------------------------ raw range coder
+int leon_rc_encode_streams(leon_dna_ctx* c, const uint8_t* syms, const uint64_t* begin, uint64_t n_streams,
+                           uint8_t* out, uint64_t out_cap, uint64_t* sizes) {
+    if (!c || !begin || !sizes || (!out && out_cap)) return LEON_E_INVALID;
+    if (!n_streams) return LEON_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    uint64_t n_syms = begin[n_streams] - begin[0];
+    if (begin[0] != 0) return fail(c, LEON_E_INVALID, "begin[0] must be 0");
+    for (uint64_t i = 0; i < n_syms; i++) {
+        uint32_t m = syms[2 * i], v = syms[2 * i + 1];
+        if (m >= N_MODELS || (m < N_SMALL_MODELS && v >= small_model_size(m))) return fail(c, LEON_E_INVALID, "bad symbol");
+    }
+    OwnBuf dsyms, dbegin; RcStreamsDev D;
+    HIPCHK(c, dsyms.ensure(n_syms * 2 + 256));
+    if (n_syms) HIPCHK(c, hipMemcpy(dsyms.p, syms, n_syms * 2, hipMemcpyHostToDevice));
+    uint64_t longest = 0;
+    for (uint64_t b = 0; b < n_streams; b++) longest = std::max(longest, begin[b + 1] - begin[b]);
+    // (test hook, LEON_RC_STREAMS_ON_HOST=1: the same streams through the host chains fed by the device's modelers -- host_blocks.h --
+    // so that the tests hold the two coders against each other and against the oracle on the same symbols)
+    // (the hand-over is rc_on_host's: a longest stream of 2^22 - 1025 symbols still goes to the host chains, one more to the device; tests/rc_edges.py's pack22_host /
+    // pack22_device are of these two lengths and are held to the oracle's bytes, whichever coder takes them)
+    if (const char* e = getenv("LEON_RC_STREAMS_ON_HOST")) if (e[0] == '1' && longest + 1024 < (1ull << HB_COUNT_BITS)) {
+        HIPCHK(c, dbegin.ensure((n_streams + 1) * 8));
+        HIPCHK(c, hipMemcpy(dbegin.p, begin, (n_streams + 1) * 8, hipMemcpyHostToDevice));
+        if (int rc = rc_blocks_on_host(c, dsyms.as<uint8_t>(), dbegin.as<uint64_t>(), n_streams, n_syms, SMALL_SIZES_DNA, N_SMALL_MODELS))
+            return rc == 1 ? fail(c, LEON_E_HIP, "no memory for the host chains' records") : rc;
+        uint64_t w = 0;
+        for (uint64_t b = 0; b < n_streams; b++) {
+            sizes[b] = c->hb.coders[b].size();
+            if (w + sizes[b] > out_cap) return fail(c, LEON_E_OVERFLOW, "out_cap too small");
+            memcpy(out + w, c->hb.coders[b].data(), sizes[b]);
+            w += sizes[b];
+        }
+        return LEON_OK;
+    }
+    if (int rc = D.code(c, dsyms.as<uint8_t>(), begin, n_streams, longest, "range coder output exceeded its bound", sizes)) return rc;
+    uint64_t w = 0;
+    for (uint64_t b = 0; b < n_streams; b++) {
+        if (w + sizes[b] > out_cap) return fail(c, LEON_E_OVERFLOW, "out_cap too small");
+        hipError_t e = hipMemcpy(out + w, D.out.as<uint8_t>() + D.off[b], sizes[b], hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return fail(c, LEON_E_HIP, hipGetErrorString(e));
+        w += sizes[b];
+    }
+    return LEON_OK;
+}
+}  // extern "C"

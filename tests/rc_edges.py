@@ -29,7 +29,7 @@ N_SMALL = MB.N_SMALL
 N_MODELS = len(MODEL_SIZES)
 TOP, BOTTOM, M64 = 1 << 56, 1 << 48, (1 << 64) - 1
 
-PACK22_HOST_LEN = (1 << 22) - 1025        # the longest stream leon_rc_encode_streams / rc_on_host still give to the host chains (capi.hip)
+PACK22_HOST_LEN = (1 << 22) - 1025        # the longest stream leon_rc_encode_streams / rc_on_host still give to the host chains (rc_kernels.hip)
 PACK22_DEVICE_LEN = PACK22_HOST_LEN + 1
 LANES = (0, 1, 62, 63)                    # index % 64: a tile's first records, and the clamp of rc_coder_tile's two-ahead prefetch `jn`
 

@@ -98,7 +98,7 @@ def test_reads_are_as_stated_and_the_oracle_round_trips_the_corner_blocks():
 
 
 def _share(n_reads, payload):
-    """hdr_symbols_launch's share of the symbol buffer for one block (capi.hip): a block with more symbols goes to the host decoder"""
+    """hdr_symbols_launch's share of the symbol buffer for one block (hdr_kernels.hip): a block with more symbols goes to the host decoder"""
     return 24 * n_reads + 6 * len(payload) + 256
 
 
