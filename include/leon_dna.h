@@ -565,6 +565,67 @@ int leon_host_fastq_split(const uint8_t* text, uint64_t n_text, int last, uint64
                           uint64_t* header_off, uint8_t* bases, uint64_t* base_off, uint8_t* quals, uint64_t bytes_cap, uint64_t records_cap,
                           leon_fastq_split_result* res);
 
+/* -- FASTA text split into records --
+ * The text begins at a record start.  Lines end at '\n'; one '\r' directly in front of the '\n' is dropped, a '\r' anywhere else is
+ * kept; with last != 0 the end of the text ends a line that has no '\n' (that line keeps a '\r' at its end).  A HEADER line is a
+ * non-empty line whose first byte is '>'; every other line is a SEQUENCE line, whatever it holds.  Record r is the r-th header line
+ * and the sequence lines behind it, up to the next header line.  A record is WHOLE when the header line that follows it has its first
+ * byte inside the text (the rest of that line may be missing); with last != 0 the end of the text ends a record as well; without it
+ * the text's last record is never whole.  `wrap` says which whole records are REGULAR:
+ *   wrap = W > 0, the file's line width: the record has at least one sequence line   (else LEON_FASTA_R_NO_SEQUENCE),
+ *                 none of its lines is empty                                          (else LEON_FASTA_R_EMPTY_LINE),
+ *                 every sequence line but its last has exactly W bytes, the last one 1 .. W   (else LEON_FASTA_R_WIDTH);
+ *   wrap = 0, no width seen yet: the record has exactly one sequence line (none: LEON_FASTA_R_NO_SEQUENCE; a first line that is not
+ *                 the last: LEON_FASTA_R_MULTILINE) and that line is not empty       (else LEON_FASTA_R_EMPTY_LINE);
+ *   wrap = LEON_FASTA_ANY_WIDTH, the file's width is lost already: every whole record is regular, empty lines contribute nothing, a
+ *                 record without sequence lines has 0 bases.
+ * A text that is not empty and does not begin with '>' breaks LEON_FASTA_R_HEADER under every wrap: its record 0 is what lies in front
+ * of the first header line; no other record can break that rule.  `reason` is the one of record n_records' first offending line (a
+ * record without sequence: its header line); on one line, empty comes before width and before multi-line.
+ * The call splits the longest prefix of records that are whole, regular and at most max_records, nothing after it: the header lines
+ * without their '>' back to back, the sequence lines back to back -- a record's lines joined --, header_off[n_records + 1] and
+ * base_off[n_records + 1] beginning with 0.  There are no qualities.  `stop`:
+ *   LEON_FASTA_MAX        n_records == max_records;
+ *   LEON_FASTA_IRREGULAR  record n_records is whole and not regular: the caller's parser is its judge.  next_header is the first byte
+ *                         of the header line behind that record, n_text when the text has none: the record is text[consumed, next_header);
+ *   LEON_FASTA_END        the text ran out: what is left is no whole record, or nothing.
+ * `consumed` is the first byte of record n_records' header line (n_text when every record was split, which takes last != 0).
+ * single_max: the longest sequence among the split records that sat on ONE line (0: none did).  next_header is 0 unless the stop is
+ * LEON_FASTA_IRREGULAR.
+ * bytes_cap: the room of each blob; records_cap: the entries of each offset table.  LEON_E_OVERFLOW when header_bytes or base_bytes is
+ * above bytes_cap or n_records + 1 above records_cap (the result says what is needed; what the blobs and tables hold is not defined
+ * then, their ends are respected): a caller with bytes_cap >= n_text and records_cap >= n_text / 2 + 2 never sees it.  LEON_E_INVALID:
+ * null pointers, n_text >= 2^32.  Whatever else the text holds is data, never an error.
+ * The device form (fastq_kernels.hip: k_fq_newlines, k_fa_lines, k_fa_heads, k_fa_offsets, k_fa_split) takes every pointer but `res` in
+ * DEVICE memory, no alignment asked, works on a stream of its own and is complete on return; nothing outside the text is read, nothing
+ * behind header_bytes / base_bytes / n_records + 1 entries is written.  The host form is the same contract in plain serial code
+ * (host_fasta.h) and needs no GPU.  Errors: leon_last_error(NULL). */
+#define LEON_FASTA_ANY_WIDTH (~(uint64_t)0)
+#define LEON_FASTA_MAX 0u
+#define LEON_FASTA_END 1u
+#define LEON_FASTA_IRREGULAR 2u
+#define LEON_FASTA_R_NONE 0u
+#define LEON_FASTA_R_HEADER 1u
+#define LEON_FASTA_R_NO_SEQUENCE 2u
+#define LEON_FASTA_R_EMPTY_LINE 3u
+#define LEON_FASTA_R_WIDTH 4u
+#define LEON_FASTA_R_MULTILINE 5u
+typedef struct leon_fasta_split_result {
+    uint64_t n_records;      /* records 0 .. n_records-1 were split */
+    uint64_t consumed;       /* bytes of text they occupy: record n_records' header line begins at text[consumed] */
+    uint64_t header_bytes, base_bytes;
+    uint32_t stop;           /* LEON_FASTA_MAX, LEON_FASTA_END or LEON_FASTA_IRREGULAR */
+    uint32_t reason;         /* under LEON_FASTA_IRREGULAR: the LEON_FASTA_R_* rule record n_records broke; else LEON_FASTA_R_NONE */
+    uint64_t single_max;     /* the longest sequence among the split records that sat on one line */
+    uint64_t next_header;    /* under LEON_FASTA_IRREGULAR: where the record behind record n_records begins, or n_text */
+} leon_fasta_split_result;
+int leon_fasta_split_device(int device_id, const uint8_t* d_text, uint64_t n_text, int last, uint64_t max_records, uint64_t wrap,
+                            uint8_t* d_headers, uint64_t* d_header_off, uint8_t* d_bases, uint64_t* d_base_off, uint64_t bytes_cap,
+                            uint64_t records_cap, leon_fasta_split_result* res);
+int leon_host_fasta_split(const uint8_t* text, uint64_t n_text, int last, uint64_t max_records, uint64_t wrap, uint8_t* headers,
+                          uint64_t* header_off, uint8_t* bases, uint64_t* base_off, uint64_t bytes_cap, uint64_t records_cap,
+                          leon_fasta_split_result* res);
+
 /* -- every sequence letter kept: lower-case runs and bytes outside ACGTN --
  * For the n_bytes bases at d_bases (the reads' bases one after another): a RUN is a maximal interval [begin, end) of bytes in
  * 'a'..'z'; an ODD byte is one that, folded to upper case when it is lower-case, is none of A C G T N; the FOLDED buffer holds the

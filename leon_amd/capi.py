@@ -77,6 +77,20 @@ FASTQ_MAX, FASTQ_END, FASTQ_IRREGULAR = 0, 1, 2
 FASTQ_R_NONE, FASTQ_R_HEADER, FASTQ_R_PLUS, FASTQ_R_LENGTH, FASTQ_R_PLUS_TEXT, FASTQ_R_PARTIAL = range(6)
 FASTQ_TILE, FASTQ_MAX_GROUPS = 4096, 1024      # kernels.h: k_fq_newlines' tile and the cap of its grid
 
+
+class FastaSplitResult(C.Structure):
+    """leon_fasta_split_result"""
+    _fields_ = [("n_records", C.c_uint64), ("consumed", C.c_uint64), ("header_bytes", C.c_uint64), ("base_bytes", C.c_uint64),
+                ("stop", C.c_uint32), ("reason", C.c_uint32), ("single_max", C.c_uint64), ("next_header", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+FASTA_ANY_WIDTH = (1 << 64) - 1
+FASTA_MAX, FASTA_END, FASTA_IRREGULAR = 0, 1, 2
+FASTA_R_NONE, FASTA_R_HEADER, FASTA_R_NO_SEQUENCE, FASTA_R_EMPTY_LINE, FASTA_R_WIDTH, FASTA_R_MULTILINE = range(6)
+
 _u8p, _u32p, _i32p, _u64p = (C.POINTER(t) for t in (C.c_uint8, C.c_uint32, C.c_int32, C.c_uint64))
 
 _EXPORTS = {
@@ -160,6 +174,10 @@ _EXPORTS = {
     "leon_fastq_split_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "leon_host_fastq_split": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_uint64, C.c_uint64, C.c_void_p]),
+    "leon_fasta_split_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_uint64, C.c_uint64, C.c_void_p]),
+    "leon_host_fasta_split": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_uint64, C.c_uint64, C.c_void_p]),
     "leon_device_trim": (None, []),
     "leon_host_qual_decode_blocks": (C.c_int, [_u8p, _u64p, _u32p, _u64p, C.c_uint64, _u8p, C.c_uint64, _u64p, C.c_uint32]),
@@ -917,6 +935,44 @@ def host_fastq_split(text, last=1, max_records=1 << 62, plus_kind=-1, bytes_cap=
     n = r["n_records"]
     return (r, blobs[0][:r["header_bytes"]].tobytes(), offs[0][:n + 1].copy(), blobs[1][:r["base_bytes"]].tobytes(), offs[1][:n + 1].copy(),
             blobs[2][:r["base_bytes"]].tobytes())
+
+
+def fasta_split_device(d_text, n_text, last, max_records, wrap, d_headers, d_header_off, d_bases, d_base_off, bytes_cap, records_cap, device_id=0):
+    """leon_fasta_split_device over raw device pointers (integers); wrap: 0, the line width, or FASTA_ANY_WIDTH.  Returns the result's
+    fields as a dict; a LeonDnaError carries them as .result (LEON_E_OVERFLOW: what the call needs)"""
+    lib = load_library()
+    res = FastaSplitResult()
+    rc = lib.leon_fasta_split_device(device_id, C.c_void_p(int(d_text)), int(n_text), int(last), int(max_records), int(wrap), C.c_void_p(int(d_headers)),
+                                     C.c_void_p(int(d_header_off)), C.c_void_p(int(d_bases)), C.c_void_p(int(d_base_off)), int(bytes_cap), int(records_cap),
+                                     C.byref(res))
+    if rc:
+        err = LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+        err.result = res.as_dict()
+        raise err
+    return res.as_dict()
+
+
+def host_fasta_split(text, last=1, max_records=1 << 62, wrap=FASTA_ANY_WIDTH, bytes_cap=None, records_cap=None):
+    """leon_host_fasta_split (no GPU): text is bytes-like.  Returns (result dict, headers, header_off, bases, base_off): the blobs as bytes,
+    the offsets as uint64 arrays of n_records + 1 entries.  bytes_cap / records_cap default to what never overflows"""
+    lib = load_library()
+    buf = np.frombuffer(bytes(text) + b"\0", dtype=np.uint8)
+    n_text = len(buf) - 1
+    bytes_cap = n_text if bytes_cap is None else int(bytes_cap)
+    records_cap = n_text // 2 + 2 if records_cap is None else int(records_cap)
+    blobs = [np.zeros(bytes_cap + 1, dtype=np.uint8) for _ in range(2)]
+    offs = [np.zeros(records_cap + 1, dtype=np.uint64) for _ in range(2)]
+    res = FastaSplitResult()
+    rc = lib.leon_host_fasta_split(C.c_void_p(buf.ctypes.data), n_text, int(last), int(max_records), int(wrap), C.c_void_p(blobs[0].ctypes.data),
+                                   C.c_void_p(offs[0].ctypes.data), C.c_void_p(blobs[1].ctypes.data), C.c_void_p(offs[1].ctypes.data), bytes_cap, records_cap,
+                                   C.byref(res))
+    if rc:
+        err = LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+        err.result = res.as_dict()
+        raise err
+    r = res.as_dict()
+    n = r["n_records"]
+    return r, blobs[0][:r["header_bytes"]].tobytes(), offs[0][:n + 1].copy(), blobs[1][:r["base_bytes"]].tobytes(), offs[1][:n + 1].copy()
 
 
 def records_format_device(d_bases, d_len, n_reads, n_bases, d_text, text_cap, lead=b"@", fastq=True, plus_kind=0, wrap=0, first_read_index=0,

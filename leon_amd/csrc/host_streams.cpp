@@ -20,6 +20,7 @@
 
 #include "host_bgzf.h"
 #include "host_fastq.h"
+#include "host_fasta.h"
 
 namespace leon { void set_create_error(const std::string& msg); }
 
@@ -630,6 +631,19 @@ int leon_host_fastq_split(const uint8_t* text, uint64_t n_text, int last, uint64
     const int rc = leon::fastq_split(text, n_text, last, max_records, plus_kind, headers, header_off, bases, base_off, quals, bytes_cap, records_cap, res);
     if (rc == LEON_E_OVERFLOW)
         return fail(rc, "leon_host_fastq_split: " + std::to_string(res->n_records) + " records need " + std::to_string(res->header_bytes) + " header bytes, " +
+                            std::to_string(res->base_bytes) + " bases and " + std::to_string(res->n_records + 1) + " table entries");
+    return rc;
+}
+
+// ---- FASTA text split into records: the host form of leon_fasta_split_device, the loop itself in host_fasta.h ----
+extern "C"
+int leon_host_fasta_split(const uint8_t* text, uint64_t n_text, int last, uint64_t max_records, uint64_t wrap, uint8_t* headers, uint64_t* header_off,
+                          uint8_t* bases, uint64_t* base_off, uint64_t bytes_cap, uint64_t records_cap, leon_fasta_split_result* res) {
+    if (const char* why = leon::fasta_split_refusal(text, n_text, headers, header_off, bases, base_off, res))
+        return fail(LEON_E_INVALID, std::string("leon_host_fasta_split: ") + why);
+    const int rc = leon::fasta_split(text, n_text, last, max_records, wrap, headers, header_off, bases, base_off, bytes_cap, records_cap, res);
+    if (rc == LEON_E_OVERFLOW)
+        return fail(rc, "leon_host_fasta_split: " + std::to_string(res->n_records) + " records need " + std::to_string(res->header_bytes) + " header bytes, " +
                             std::to_string(res->base_bytes) + " bases and " + std::to_string(res->n_records + 1) + " table entries");
     return rc;
 }

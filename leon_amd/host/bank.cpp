@@ -220,7 +220,7 @@ Bank::Bank(const std::string& path, int inflate_device, bool verbose) : path_(pa
         gzbuffer((gzFile)gz_, 1 << 20);
     }
 }
-Bank::Bank(const std::string& path, Memory) : memory_(true), path_(path), decided_(true), fastq_(true) {}
+Bank::Bank(const std::string& path, Memory, bool fasta) : memory_(true), path_(path), decided_(true), fastq_(!fasta) {}
 
 BgzfDeviceText::BgzfDeviceText(const std::string& path, int device) : src_(new Bank::BgzfSource()) {
     src_->path = path; src_->device = device;

@@ -4,6 +4,7 @@
 // so the host never holds more than one batch of it.
 #pragma once
 #include <stdint.h>
+#include <algorithm>
 #include <functional>
 #include <string>
 #include <vector>
@@ -43,7 +44,12 @@ public:
     // kind -- the read counter and the '+'-line table stay what they would be had next() read those records too.
     struct Memory {};
     typedef std::function<bool(const char*&, size_t&)> More;
-    Bank(const std::string& path, Memory);
+    // fasta: a FASTA parser over such text.  fastaWrap() is the `wrap` the device split is to be called with, given what
+    // the parser has noted so far: LEON_FASTA_ANY_WIDTH once fastaLineWidth() is 0 for good, the width once one was seen, else 0;
+    // skipped(n, single_max): n regular records the caller split itself, the longest of them that sat on one line.
+    Bank(const std::string& path, Memory, bool fasta = false);
+    uint64_t fastaWrap() const { return (!wrap_ok_ || single_empty_ || (wrap_seen_ && single_max_ > wrap_)) ? ~0ull : wrap_seen_ ? wrap_ : 0; }
+    void skipped(uint64_t n, uint64_t single_max) { n_read_ += n; single_max_ = std::max(single_max_, single_max); }
     void attach(const char* p, size_t n, More more) { data_ = p; buf_pos_ = 0; buf_len_ = n; more_ = std::move(more); }
     size_t position() const { return buf_pos_; }
     void skipped(uint64_t n) { n_read_ += n; }

@@ -237,14 +237,15 @@ Compressor::Compressor(Leon& leon)
     for (int g = 0; g < n_gpus; g++) { store.emplace_back(new ResidentReads()); store.back()->device = device_for(g); }
     dev0 = store[0]->device;
     if (record_parse_on_device(o._recordParse)) {
-        const char* host_why = !fastq ? "FASTA input" : bank.isGzip() ? "gzip input that is not inflated on the device" : nullptr;
+        // (FASTA goes to the device under `-record-parse-fasta` only, DESIGN.md 4.17: `-record-parse device` alone keeps its meaning)
+        const char* host_why = !fastq && !o._recordParseFasta ? "FASTA input" : bank.isGzip() ? "gzip input that is not inflated on the device" : nullptr;
         if (!host_why) {
             const bool bgzf = bank.inflatesOnDevice();
             bank.dropSource();                                   // (it has said what the file is; the device reader reads it from its first byte)
-            dreader.reset(new FastqDeviceReader(o._inputFilename, dev0, bgzf, o._verbose));
+            dreader.reset(new FastqDeviceReader(o._inputFilename, dev0, bgzf, o._verbose, !fastq));
         }
         if (o._verbose && host_why) std::cout << "parse: records cut on the host (" << host_why << ")" << std::endl;
-        if (o._verbose && !host_why) std::cout << "parse: records split on the device (k_fq_split), spans of " << dreader->spanBytes() << " bytes" << std::endl;
+        if (o._verbose && !host_why) std::cout << "parse: records split on the device (" << (fastq ? "k_fq_split" : "k_fa_split") << "), spans of " << dreader->spanBytes() << " bytes" << std::endl;
     }
 }
 
@@ -617,7 +618,7 @@ void Compressor::write_tables() {
     params[P_VERSION_MAJOR] = 1; params[P_VERSION_MINOR] = 1; params[P_VERSION_PATCH] = 0;       // Leon 1.1.0, /root/reference/CMakeLists.txt:9-11
     params[P_KMER_SIZE] = k; params[P_READS_PER_BLOCK] = rpb; params[P_N_READS] = n_reads; params[P_N_ANCHORS] = n_anchors;
     params[P_ABUNDANCE] = abundance; params[P_BLOOM_TAI] = tai; params[P_BLOOM_N_HASH] = 7; params[P_BLOOM_BLOCK_NBITS] = 12;
-    params[P_TOTAL_BASES] = n_bases; params[P_FASTA_LINE_WIDTH] = fastq ? 0 : bank.fastaLineWidth();
+    params[P_TOTAL_BASES] = n_bases; params[P_FASTA_LINE_WIDTH] = fastq ? 0 : dreader ? dreader->parser().fastaLineWidth() : bank.fastaLineWidth();
     params[P_CONTAINER_REV] = CONTAINER_REV;
     params[P_QUAL_ENCODER] = !keep_qual ? QUAL_ENC_NONE : qual_on_device ? QUAL_ENC_DEVICE_RLE : QUAL_ENC_ZLIB;
     out->putU64(DS_PARAMS, params, PARAM_COUNT);

@@ -66,6 +66,7 @@ void Leon::run(int argc, char* argv[]) {
             else if (a == "-qual-deflate") { _qualDeflate = need("-qual-deflate"); (void)qual_encoder_choice(_qualDeflate); }
             else if (a == "-input-inflate") { _inputInflate = need("-input-inflate"); (void)parse_choice("-input-inflate", _inputInflate); }
             else if (a == "-record-parse") { _recordParse = need("-record-parse"); (void)record_parse_on_device(_recordParse); }
+            else if (a == "-record-parse-fasta") _recordParseFasta = true;
             else if (a == "-header-text") { _headerText = need("-header-text"); (void)parse_choice("-header-text", _headerText); }
             else if (a == "-record-text") { _recordText = need("-record-text"); (void)parse_choice("-record-text", _recordText); }
             else if (a == "-qual-inflate") { _qualInflate = need("-qual-inflate"); (void)parse_choice("-qual-inflate", _qualInflate); }
@@ -81,6 +82,7 @@ void Leon::run(int argc, char* argv[]) {
         if (_gzIndex && !_gz) throw Exception("option -gz-index belongs to -gz");
         if (!_inputInflate.empty() && _decompress) throw Exception("option -input-inflate belongs to -c");
         if (!_recordParse.empty() && _decompress) throw Exception("option -record-parse belongs to -c");
+        if (_recordParseFasta && (_recordParse.empty() || !record_parse_on_device(_recordParse))) throw Exception("option -record-parse-fasta belongs to -record-parse device");
         if (_dictPieces && _decompress) throw Exception("option -dict-pieces belongs to -c: -d reads the pieces whenever the container holds them");
         if (_dictPieceAnchors && !_dictPieces) throw Exception("option -dict-piece-anchors belongs to -dict-pieces");
         if (_seqOnly) _noHeader = _noQual = true;             // "same as -noheader -noqual", /root/reference/README.md:56

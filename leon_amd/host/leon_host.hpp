@@ -57,6 +57,7 @@ public:
     std::string _qualDeflate;             // -qual-deflate host|device|auto; empty = not given: zlib on the host threads (the reference's bytes)
     std::string _inputInflate;            // -c: -input-inflate host|device|auto; empty = not given: a gzip input inflated by zlib on the reader's thread
     std::string _recordParse;             // -c: -record-parse host|device; empty = not given: the FASTQ records cut by the reader's thread on the host
+    bool _recordParseFasta = false;       // -c -record-parse device: -record-parse-fasta, a FASTA input is split on the device too
     std::string _headerText;              // -d: -header-text host|device|auto; empty = not given: the header text on the host threads
     std::string _recordText;              // -d: -record-text host|device|auto; empty = not given: the records formatted on the host threads
     std::string _qualInflate;             // -d: -qual-inflate host|device|auto; empty = not given: the quality blocks inflated by zlib on the host threads
