@@ -427,6 +427,18 @@ int leon_text_bgzf_records_device(int device_id, const uint8_t* d_text, uint64_t
                                   leon_piece_sink sink, void* user,
                                   uint64_t* n_taken, uint64_t* out_bytes,
                                   uint64_t* member_out_off, uint64_t* member_text_off, uint64_t members_cap, uint64_t* n_members);
+/* leon_text_bgzf_records_device with a choice of encoder.  flags == 0: its bytes on the same arguments.
+ * LEON_BGZF_F_MATCHES: every member's block comes from k_deflate_lz_chunks -- an LZ77 search inside the member (a hash of four bytes,
+ * one candidate a position, greedy selection) with a distance code of its own, beside the runs and Huffman codes of the encoder above;
+ * what record text wants, where a header line repeats most of the one before.  A member's block is a function of its text alone.
+ * Cuts, member layout, member bound, sink, slices, carry rule and refusals are those of leon_text_bgzf_records_device; a bit of flags
+ * that is not defined here is refused with them, LEON_E_INVALID, before a device is touched.  The kernel keeps 16 MiB more per device. */
+#define LEON_BGZF_F_MATCHES 1u
+int leon_text_bgzf_device_ex(int device_id, const uint8_t* d_text, uint64_t n_head, uint64_t n_body,
+                             const uint64_t* d_rec_off, uint64_t n_records, int last,
+                             leon_piece_sink sink, void* user,
+                             uint64_t* n_taken, uint64_t* out_bytes,
+                             uint64_t* member_out_off, uint64_t* member_text_off, uint64_t members_cap, uint64_t* n_members, uint32_t flags);
 /* The same cut rule on HOST memory (no GPU): rec_off[0 .. n_records] as above (NULL with n_records == 0: a head alone), n_body =
  * rec_off[n_records].  begin / len (cap entries each; both NULL with cap == 0: count only): every member's offset in the call's text
  * (head included) and its bytes.  *n_members = the count, *n_taken as above.  LEON_E_OVERFLOW when a given table is too small

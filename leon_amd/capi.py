@@ -170,6 +170,8 @@ _EXPORTS = {
     "leon_text_bgzf_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_int, PIECE_SINK, C.c_void_p, _u64p, _u64p, _u64p]),
     "leon_text_bgzf_records_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, PIECE_SINK, C.c_void_p,
                                                  _u64p, _u64p, C.c_void_p, C.c_void_p, C.c_uint64, _u64p]),
+    "leon_text_bgzf_device_ex": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, PIECE_SINK, C.c_void_p,
+                                            _u64p, _u64p, C.c_void_p, C.c_void_p, C.c_uint64, _u64p, C.c_uint32]),
     "leon_host_bgzf_record_cuts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, _u64p, _u64p]),
     "leon_fastq_split_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
@@ -813,8 +815,17 @@ def bgzf_members_bound(n_text):
     return 3 * (int(n_text) // BGZF_MEMBER_TEXT) + 2
 
 
+BGZF_F_MATCHES = 1           # LEON_BGZF_F_MATCHES
+
+
+def text_bgzf_device_ex(d_text, n_head, n_body, d_rec_off, n_records, flags=0, **kw):
+    """leon_text_bgzf_device_ex: text_bgzf_records_device's arguments and results, with the encoder chosen by flags (BGZF_F_MATCHES:
+    k_deflate_lz_chunks; 0: the bytes of text_bgzf_records_device)."""
+    return text_bgzf_records_device(d_text, n_head, n_body, d_rec_off, n_records, _flags=int(flags), **kw)
+
+
 def text_bgzf_records_device(d_text, n_head, n_body, d_rec_off, n_records, last=1, device_id=0, sink=None, member_out=None, member_text=None,
-                             members_cap=None, tables=True, null=()):
+                             members_cap=None, tables=True, null=(), _flags=None):
     """leon_text_bgzf_records_device: n_head + n_body bytes at the device pointer d_text as BGZF with members cut at the record starts
     d_rec_off[0 .. n_records] (a device pointer; 0 = NULL, with no records and no head: the fixed cuts).  Returns (bytes of this call's
     output, n_taken, n_members, member_out_off, member_text_off); the pieces are collected as text_bgzf_device collects them.
@@ -848,11 +859,13 @@ def text_bgzf_records_device(d_text, n_head, n_body, d_rec_off, n_records, last=
         assert a is None or (a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"])
     taken, out_bytes, members = C.c_uint64(), C.c_uint64(), C.c_uint64()
     vp = lambda a: C.c_void_p(0 if a is None else a.ctypes.data)
-    rc = lib.leon_text_bgzf_records_device(device_id, C.c_void_p(int(d_text) if d_text else 0), int(n_head), int(n_body),
-                                           C.c_void_p(int(d_rec_off) if d_rec_off else 0), int(n_records), int(last),
-                                           None if "sink" in null else PIECE_SINK(thunk), None,
-                                           None if "n_taken" in null else C.byref(taken), None if "out_bytes" in null else C.byref(out_bytes),
-                                           vp(member_out), vp(member_text), int(members_cap), None if "n_members" in null else C.byref(members))
+    name = "leon_text_bgzf_records_device" if _flags is None else "leon_text_bgzf_device_ex"             # (_flags: text_bgzf_device_ex's)
+    rc = getattr(lib, name)(device_id, C.c_void_p(int(d_text) if d_text else 0), int(n_head), int(n_body),
+                            C.c_void_p(int(d_rec_off) if d_rec_off else 0), int(n_records), int(last),
+                            None if "sink" in null else PIECE_SINK(thunk), None,
+                            None if "n_taken" in null else C.byref(taken), None if "out_bytes" in null else C.byref(out_bytes),
+                            vp(member_out), vp(member_text), int(members_cap), None if "n_members" in null else C.byref(members),
+                            *(() if _flags is None else (C.c_uint32(_flags),)))
     if rc:
         err = LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
         err.n_members = members.value
@@ -863,10 +876,10 @@ def text_bgzf_records_device(d_text, n_head, n_body, d_rec_off, n_records, last=
     at = 0
     for off, data in pieces:
         if off != at:
-            raise LeonDnaError(-5, "leon_text_bgzf_records_device: the pieces do not tile the output (offset %d, expected %d)" % (off, at))
+            raise LeonDnaError(-5, "%s: the pieces do not tile the output (offset %d, expected %d)" % (name, off, at))
         at += len(data)
     if at != out_bytes.value:
-        raise LeonDnaError(-5, "leon_text_bgzf_records_device: %d bytes delivered, out_bytes = %d" % (at, out_bytes.value))
+        raise LeonDnaError(-5, "%s: %d bytes delivered, out_bytes = %d" % (name, at, out_bytes.value))
     n = members.value
     return (b"".join(d for _, d in pieces), taken.value, n, None if member_out is None else member_out[:n].copy(),
             None if member_text is None else member_text[:n].copy())

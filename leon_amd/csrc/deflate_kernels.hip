@@ -363,6 +363,279 @@ __global__ void __launch_bounds__(DF_T) k_deflate_chunks(const uint8_t* text, co
     }
 }
 
+// ---- the same block with LZ77 matches, for record text (leon_text_bgzf_device_ex with LEON_BGZF_F_MATCHES) ----
+// A header line repeats most of the one a record back, sequence fragments repeat too: text pays for a match search that qualities do
+// not.  The parse of a chunk is a function of its bytes alone (tests/deflate_lz.py restates it):
+//   candidates  in steps of DF_LZ_STEP positions, one per thread: every position with four bytes left reads table[hash of them] -- the
+//               largest position of the steps before with that hash --, and after a barrier enters itself by atomicMax (so the order
+//               does not matter).  A source inside the same step is not found; the run covers the common case of it.  The candidate
+//               is compared with the text, at most 258 bytes and not past the chunk: another 4-gram of the same hash gives 0;
+//   runs        as k_deflate_chunks: the bytes from p on equal to t[p - 1], at most 258, valid from 3, distance 1;
+//   choice      the hash candidate when it has DF_LZ_MIN bytes and two more than the run, else the run, else a literal;
+//   selection   greedy from position 0.  Every thread owns DF_PER positions and finds, backwards, for each of them the last token of
+//               its range that a parse entering there takes (7 bits beside the 9 of the length); one lane chains the 256 ranges (a
+//               token of 258 can skip two of them); every thread then walks forward from where the parse enters its range.
+// The hash table lies in the words the block is written to later (zeroed in between); the distances, 64 KiB a chunk, do not fit in
+// LDS beside text, lengths and output and lie in global memory, DF_CHUNK entries per workgroup of a grid of at most DF_LZ_MAX_GROUPS.
+constexpr uint32_t DF_LZ_STEP = DF_T;
+constexpr uint32_t DF_LZ_HASH_BITS = 13;
+constexpr uint32_t DF_LZ_MIN = 5;                               // (4: 158 374, 5: 158 081, 6: 158 489 bytes on the suite's FASTQ)
+constexpr uint32_t DF_LZ_MAX_GROUPS = 256;                      // one workgroup a CU; 16 MiB of distances
+constexpr uint32_t DF_NDIST = 30;
+constexpr uint32_t DF_LZ_NONE = 0xFFFFu;
+static_assert(DF_PER == 128 && DF_CHUNK <= 32768, "a token's length (9 bits) and the last token of a range (7 bits) share 16 bits");
+static_assert((1u << DF_LZ_HASH_BITS) <= DF_OUT_STRIDE / 4 + 4, "the hash table lies in the output words");
+
+__device__ const uint16_t df_dist_base[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193,
+                                              12289, 16385, 24577};
+__device__ inline uint32_t df_dist_code(uint32_t dist) {        // 1..32768 -> 0..29; code c has (c >> 1) - 1 extra bits from 4 on
+    const uint32_t d = dist - 1;
+    if (d < 4) return d;
+    const uint32_t b = 31 - (uint32_t)__builtin_clz(d);
+    return 2 * b + ((d >> (b - 1)) & 1u);
+}
+__device__ inline uint32_t df_dist_extra(uint32_t code) { return code < 4 ? 0u : (code >> 1) - 1; }
+
+// how many bytes from a and from b on are equal, at most cap (a < b, b + cap within the text; tb is readable 3 bytes past its end)
+__device__ inline uint32_t df_common(const uint8_t* tb, uint32_t a, uint32_t b, uint32_t cap) {
+    uint32_t k = 0;
+    while (k < cap) {
+        uint32_t x = 0;
+#pragma unroll
+        for (uint32_t u = 0; u < 4; u++) x |= (uint32_t)(tb[a + k + u] ^ tb[b + k + u]) << (8 * u);
+        if (x) { k += (uint32_t)__builtin_ctz(x) >> 3; break; }
+        k += 4;
+    }
+    return k < cap ? k : cap;
+}
+
+// the code lengths lens_at(0 .. total) as items of the code-length alphabet (16: repeat, 17 / 18: zeros); returns their number
+template <typename F> __device__ inline uint32_t df_header_items(F lens_at, uint32_t total, uint16_t* hdr_sym, uint8_t* hdr_extra) {
+    uint32_t nh = 0;
+    for (uint32_t i = 0; i < total;) {
+        const uint32_t v = lens_at(i);
+        uint32_t r = 1;
+        while (i + r < total && lens_at(i + r) == v) r++;
+        if (v == 0 && r >= 3) {
+            uint32_t left = r;
+            while (left >= 3) {
+                const uint32_t k = left > 138 ? 138 : left;
+                if (k >= 11) { hdr_sym[nh] = 18; hdr_extra[nh++] = (uint8_t)(k - 11); } else { hdr_sym[nh] = 17; hdr_extra[nh++] = (uint8_t)(k - 3); }
+                left -= k;
+            }
+            for (; left; left--) { hdr_sym[nh] = 0; hdr_extra[nh++] = 0; }
+        } else if (v != 0 && r >= 4) {
+            hdr_sym[nh] = (uint16_t)v; hdr_extra[nh++] = 0;
+            uint32_t left = r - 1;
+            while (left >= 3) { const uint32_t k = left > 6 ? 6 : left; hdr_sym[nh] = 16; hdr_extra[nh++] = (uint8_t)(k - 3); left -= k; }
+            for (; left; left--) { hdr_sym[nh] = (uint16_t)v; hdr_extra[nh++] = 0; }
+        } else {
+            for (uint32_t k = 0; k < r; k++) { hdr_sym[nh] = (uint16_t)v; hdr_extra[nh++] = 0; }
+        }
+        i += r;
+    }
+    return nh;
+}
+
+// One chunk = one deflate block, as k_deflate_chunks.  dist: DF_CHUNK entries per workgroup, gridDim.x <= DF_LZ_MAX_GROUPS of them.
+// Bounds: tb is read below n + 3 (df_common), mlen / md at [0, n), table at a 13-bit hash, outw like k_deflate_chunks (the dynamic form
+// is written only when it is smaller than n + 5 bytes; the header alone, at most 17 + 19 * 3 + 316 * 14 bits, always fits).
+__global__ void __launch_bounds__(DF_T) k_deflate_lz_chunks(const uint8_t* text, const uint64_t* chunk_begin, const uint32_t* chunk_len, uint64_t n_chunks,
+                                                             uint8_t* out, uint32_t* sizes, uint32_t* adler, uint16_t* dist) {
+    __shared__ uint32_t textw[DF_CHUNK / 4 + 2];
+    __shared__ uint32_t outw[DF_OUT_STRIDE / 4 + 4];
+    __shared__ uint16_t mlen[DF_CHUNK];                          // bits 0..8 the token's length at p (1: a literal), 9..15 see above
+    __shared__ uint32_t freq[DF_MAXSYM], dfreq[32], A[DF_MAXSYM], fr2[DF_MAXSYM], scan_sh[DF_T + 1], clfreq[DF_NCL];
+    __shared__ uint16_t code[DF_MAXSYM], dcode[32], order[DF_MAXSYM], clcode[DF_NCL], hdr_sym[DF_MAXSYM + DF_NDIST + 8], entry[DF_T];
+    __shared__ uint8_t len[DF_MAXSYM], dlen[32], cllen[DF_NCL], hdr_extra[DF_MAXSYM + DF_NDIST + 8];
+    __shared__ uint32_t sh_misc[8], ctl[2], cnt16[16], nxt16[16];                               // 0 header bits, 1 total bits, 2 n header symbols, 3 hlit, 4 hdist
+    if (blockIdx.x >= DF_LZ_MAX_GROUPS) return;
+    uint8_t* const tb = (uint8_t*)textw;
+    uint32_t* const table = outw;
+    uint16_t* const md = dist + blockIdx.x * (uint64_t)DF_CHUNK;
+    const uint32_t t = threadIdx.x;
+    for (uint64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const uint32_t n = chunk_len[c];
+        const uint8_t* src = text + chunk_begin[c];
+        __syncthreads();
+        for (uint32_t i = t; i < n; i += DF_T) tb[i] = src[i];
+        for (uint32_t i = t; i < (1u << DF_LZ_HASH_BITS); i += DF_T) table[i] = 0;                // an entry: position + 1, 0 none
+        for (uint32_t i = t; i < DF_MAXSYM; i += DF_T) freq[i] = 0;
+        if (t < 32) dfreq[t] = 0;
+        if (t < DF_NCL) clfreq[t] = 0;
+        __syncthreads();
+        const uint32_t p0 = t * DF_PER < n ? t * DF_PER : n, p1 = (t + 1) * DF_PER < n ? (t + 1) * DF_PER : n;
+        // ---- Adler-32 over the chunk, as k_deflate_chunks ----
+        {
+            uint32_t sa = 0, sb = 0;
+            for (uint32_t i = p0; i < p1; i++) { sa += tb[i]; sb += sa; }
+            uint64_t va = sa, vb = (uint64_t)sb + (uint64_t)(n - p1) * sa;
+            for (uint32_t d = 32; d; d >>= 1) { va += __shfl_down((unsigned long long)va, d); vb += __shfl_down((unsigned long long)vb, d); }
+            if ((t & 63) == 0) { scan_sh[2 * (t >> 6)] = (uint32_t)(va % 65521u); scan_sh[2 * (t >> 6) + 1] = (uint32_t)(vb % 65521u); }
+            __syncthreads();
+            if (t == 0) {
+                const uint32_t a32 = (1u + scan_sh[0] + scan_sh[2] + scan_sh[4] + scan_sh[6]) % 65521u;
+                const uint32_t b32 = (uint32_t)(((uint64_t)n + scan_sh[1] + scan_sh[3] + scan_sh[5] + scan_sh[7]) % 65521u);
+                adler[c] = (b32 << 16) | a32;
+            }
+        }
+        // ---- the candidate and the choice at every position, a step at a time ----
+        for (uint32_t s0 = 0; s0 < n; s0 += DF_LZ_STEP) {
+            const uint32_t p = s0 + t;
+            const bool hashed = p + 4 <= n;
+            uint32_t h = 0, q1 = 0;
+            if (hashed) {
+                const uint32_t v = (uint32_t)tb[p] | (uint32_t)tb[p + 1] << 8 | (uint32_t)tb[p + 2] << 16 | (uint32_t)tb[p + 3] << 24;
+                h = (v * 2654435761u) >> (32 - DF_LZ_HASH_BITS);
+                q1 = table[h];
+            }
+            __syncthreads();                                    // every look-up of the step comes before its entries
+            if (hashed) atomicMax(&table[h], p + 1);
+            if (p < n) {
+                const uint32_t cap = n - p < 258 ? n - p : 258;
+                uint32_t run = p ? df_common(tb, p - 1, p, cap) : 0;
+                if (run < 3) run = 0;
+                const uint32_t hit = q1 ? df_common(tb, q1 - 1, p, cap) : 0;
+                uint32_t L = 1, D = 0;
+                if (hit >= DF_LZ_MIN && hit >= run + 2) { L = hit; D = p - (q1 - 1); }
+                else if (run) { L = run; D = 1; }
+                mlen[p] = (uint16_t)L; md[p] = (uint16_t)D;
+            }
+            __syncthreads();
+        }
+        for (uint32_t i = t; i < DF_OUT_STRIDE / 4 + 4; i += DF_T) outw[i] = 0;                   // (the table's words)
+        // ---- selection: per position the last token of this thread's range on a parse entering there; the chain; the entries ----
+        for (uint32_t p = p1; p-- > p0;) {
+            const uint32_t L = mlen[p], nxt = p + L;
+            const uint32_t last = nxt >= p1 ? p - p0 : (uint32_t)(mlen[nxt] >> 9);
+            mlen[p] = (uint16_t)(L | (last << 9));
+        }
+        __syncthreads();
+        if (t == 0) {
+            uint32_t pos = 0;
+            for (uint32_t g = 0; g < DF_T; g++) {
+                const uint32_t a = g * DF_PER, b = (g + 1) * DF_PER < n ? (g + 1) * DF_PER : n;
+                if (pos < b) {                                   // (pos >= a: it passed the range before)
+                    entry[g] = (uint16_t)pos;
+                    const uint32_t lt = a + (mlen[pos] >> 9);
+                    pos = lt + (mlen[lt] & 511u);
+                } else entry[g] = (uint16_t)DF_LZ_NONE;
+            }
+        }
+        __syncthreads();
+        const uint32_t e0 = entry[t];
+        // every token of this thread's range: g(position, length, distance), distance 0 a literal
+        auto each_token = [&](auto g) {
+            if (e0 == DF_LZ_NONE) return;
+            for (uint32_t p = e0; p < p1;) {
+                const uint32_t L = mlen[p] & 511u;
+                g(p, L, L > 1 ? (uint32_t)md[p] : 0u);
+                p += L;
+            }
+        };
+        // ---- pass 1: symbol frequencies ----
+        each_token([&](uint32_t p, uint32_t L, uint32_t D) {
+            if (!D) atomicAdd(&freq[tb[p]], 1u);
+            else { atomicAdd(&freq[257 + df_len_code(L)], 1u); atomicAdd(&dfreq[df_dist_code(D)], 1u); }
+        });
+        if (t == 0) atomicAdd(&freq[256], 1u);
+        __syncthreads();
+        // ---- the codes (the whole workgroup) and the block header (one lane) ----
+        df_code_lengths(freq, DF_NLIT, 15, len, A, order, fr2, ctl);
+        df_codes(len, DF_NLIT, code, cnt16, nxt16);
+        df_code_lengths(dfreq, DF_NDIST, 15, dlen, A, order, fr2, ctl);
+        if (t == 0 && (ctl[1] >> 1) == 0) dlen[0] = dlen[1] = 1;    // no match in the chunk: two codes of one bit make the distance code complete
+        __syncthreads();
+        df_codes(dlen, DF_NDIST, dcode, cnt16, nxt16);
+        if (t == 0) {
+            uint32_t hlit = DF_NLIT, hdist = DF_NDIST;
+            while (hlit > 257 && len[hlit - 1] == 0) hlit--;
+            while (hdist > 1 && dlen[hdist - 1] == 0) hdist--;
+            const uint32_t nh = df_header_items([&](uint32_t i) -> uint32_t { return i < hlit ? len[i] : dlen[i - hlit]; }, hlit + hdist, hdr_sym, hdr_extra);
+            for (uint32_t i = 0; i < nh; i++) clfreq[hdr_sym[i]]++;
+            sh_misc[2] = nh; sh_misc[3] = hlit; sh_misc[4] = hdist;
+        }
+        __syncthreads();
+        df_code_lengths(clfreq, DF_NCL, 7, cllen, A, order, fr2, ctl);
+        df_codes(cllen, DF_NCL, clcode, cnt16, nxt16);
+        if (t == 0) {
+            const uint32_t nh = sh_misc[2], hlit = sh_misc[3], hdist = sh_misc[4];
+            uint32_t hclen = DF_NCL;
+            while (hclen > 4 && cllen[df_cl_order[hclen - 1]] == 0) hclen--;
+            BitW bw{outw, 0};
+            bw.put(0u, 1); bw.put(2u, 2);                         // BFINAL 0, BTYPE 10
+            bw.put(hlit - 257, 5); bw.put(hdist - 1, 5); bw.put(hclen - 4, 4);
+            for (uint32_t i = 0; i < hclen; i++) bw.put(cllen[df_cl_order[i]], 3);
+            for (uint32_t i = 0; i < nh; i++) {
+                const uint32_t s = hdr_sym[i];
+                bw.put(clcode[s], cllen[s]);
+                if (s == 16) bw.put(hdr_extra[i], 2); else if (s == 17) bw.put(hdr_extra[i], 3); else if (s == 18) bw.put(hdr_extra[i], 7);
+            }
+            sh_misc[0] = (uint32_t)bw.pos;
+        }
+        __syncthreads();
+        // ---- pass 2: bits per thread, prefix sum ----
+        uint32_t mybits = 0;
+        each_token([&](uint32_t p, uint32_t L, uint32_t D) {
+            if (!D) mybits += len[tb[p]];
+            else {
+                const uint32_t lc = df_len_code(L), dc = df_dist_code(D);
+                mybits += len[257 + lc] + df_len_extra[lc] + dlen[dc] + df_dist_extra(dc);
+            }
+        });
+        {
+            uint32_t inc = mybits;
+            for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)inc, d); if ((t & 63) >= d) inc += o; }
+            if ((t & 63) == 63) scan_sh[t >> 6] = inc;
+            __syncthreads();
+            uint32_t base = sh_misc[0];
+            for (uint32_t w = 0; w < (t >> 6); w++) base += scan_sh[w];
+            if (t == DF_T - 1) sh_misc[1] = base + inc + len[256];              // body and end-of-block
+            mybits = base + inc - mybits;                                      // this thread's first bit
+        }
+        __syncthreads();
+        const uint32_t total_bits = sh_misc[1];
+        const uint32_t dyn_bytes = (total_bits + 3 + 7) / 8 + 4;                // with the empty stored block: 3 bits, padding, 00 00 FF FF
+        const bool stored = dyn_bytes >= n + 5;
+        uint8_t* dst = out + c * (uint64_t)DF_OUT_STRIDE;
+        if (!stored) {
+            // ---- pass 3: the tokens' bits ----
+            uint64_t pos = mybits;
+            auto put = [&](uint32_t v, uint32_t nbits) {                         // other lanes write the same words: atomic OR
+                const uint32_t i = (uint32_t)(pos >> 5), s = (uint32_t)(pos & 31);
+                atomicOr(&outw[i], v << s);
+                if (s + nbits > 32) atomicOr(&outw[i + 1], v >> (32 - s));
+                pos += nbits;
+            };
+            each_token([&](uint32_t p, uint32_t L, uint32_t D) {
+                if (!D) { const uint32_t v = tb[p]; put(code[v], len[v]); return; }
+                const uint32_t lc = df_len_code(L), dc = df_dist_code(D), de = df_dist_extra(dc);
+                put(code[257 + lc], len[257 + lc]);
+                if (df_len_extra[lc]) put(L - df_len_base[lc], df_len_extra[lc]);
+                put(dcode[dc], dlen[dc]);
+                if (de) put(D - df_dist_base[dc], de);
+            });
+            __syncthreads();
+            if (t == 0) {
+                BitW bw{outw, (uint64_t)total_bits - len[256]};
+                bw.put(code[256], len[256]);
+                bw.put(0u, 3);                                                   // BFINAL 0, BTYPE 00: the empty stored block
+                bw.pos = (bw.pos + 7) & ~7ull;
+                bw.put(0xFFFF0000u, 32);
+                sizes[c] = (uint32_t)(bw.pos >> 3);
+            }
+            __syncthreads();
+            for (uint32_t i = t; i < (dyn_bytes + 3) / 4; i += DF_T) ((uint32_t*)dst)[i] = outw[i];
+        } else {
+            if (t == 0) {
+                dst[0] = 0; dst[1] = (uint8_t)n; dst[2] = (uint8_t)(n >> 8); dst[3] = (uint8_t)~n; dst[4] = (uint8_t)(~n >> 8);
+                sizes[c] = n + 5;
+            }
+            for (uint32_t i = t; i < n; i += DF_T) dst[5 + i] = tb[i];
+        }
+    }
+}
+
 // the read blocks' streams, contiguous: 78 01, the chunks, the final empty stored block; the Adler-32 is added on the host
 __global__ void k_deflate_gather(const uint8_t* chunks, const uint32_t* sizes, const uint64_t* chunk_dst, uint64_t n_chunks, uint8_t* dst) {
     for (uint64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
@@ -683,9 +956,9 @@ int deflate_slice(DeflateScratch& S, int device_id, const uint8_t* d_quals, cons
 struct BgzfScratch {
     std::mutex mu;
     int device = -1;
-    Grow begin, len, out, sizes, adler, crc, msize, moff, tmp, framed, idx, state;
+    Grow begin, len, out, sizes, adler, crc, msize, moff, tmp, framed, idx, state, lzdist;     // lzdist: k_deflate_lz_chunks' distances
     std::vector<uint64_t> h_idx;
-    void drop() { for (Grow* g : {&begin, &len, &out, &sizes, &adler, &crc, &msize, &moff, &tmp, &framed, &idx, &state}) g->release(); }
+    void drop() { for (Grow* g : {&begin, &len, &out, &sizes, &adler, &crc, &msize, &moff, &tmp, &framed, &idx, &state, &lzdist}) g->release(); }
 };
 // the member tables of a call (host memory), filled slice by slice; out == NULL: none asked for
 struct BgzfIndex { uint64_t* out = nullptr; uint64_t* text = nullptr; uint64_t at = 0; };
@@ -702,8 +975,9 @@ uint64_t bgzf_slice_text() {
 // The n members of S.begin / S.len -- offsets into d_text, member c = [begin[c], begin[c + 1]), [lo, hi) in all, as k_bgzf_table or
 // k_bgzf_cuts left them on stream s -- compressed, framed and delivered at `base` of the call's output; *out_size = their bytes.
 // ix (may be NULL): the call's member tables, which receive base + the members' offsets and text_base + begin[c].
+// flags: LEON_BGZF_F_MATCHES has k_deflate_lz_chunks write the members' blocks instead of k_deflate_chunks.
 int bgzf_members_out(BgzfScratch& S, int device_id, hipStream_t s, const uint8_t* d_text, uint64_t n, uint64_t lo, uint64_t hi, uint64_t base, uint64_t text_base,
-                     leon_piece_sink sink, void* user, BgzfIndex* ix, const std::string& who, uint64_t* out_size) {
+                     leon_piece_sink sink, void* user, BgzfIndex* ix, const std::string& who, uint32_t flags, uint64_t* out_size) {
     DEVCHK(S.sizes.ensure(n * 4)); DEVCHK(S.adler.ensure(n * 4)); DEVCHK(S.crc.ensure(n * 4));
     DEVCHK(S.msize.ensure((n + 1) * 8)); DEVCHK(S.moff.ensure((n + 1) * 8));
     DEVCHK(S.out.ensure(n * (uint64_t)DF_OUT_STRIDE)); DEVCHK(S.framed.ensure(n * (uint64_t)BGZF_MEMBER_MAX));
@@ -711,8 +985,13 @@ int bgzf_members_out(BgzfScratch& S, int device_id, hipStream_t s, const uint8_t
     DEVCHK(prim::ExclusiveSum(nullptr, tmp_bytes, S.msize.as<uint64_t>(), S.moff.as<uint64_t>(), n + 1, s));
     DEVCHK(S.tmp.ensure(tmp_bytes));
     const uint32_t tgrid = (uint32_t)((n + 1 + 255) / 256);
-    hipLaunchKernelGGL(k_deflate_chunks, dim3((uint32_t)std::min<uint64_t>(n, 1u << 20)), dim3(DF_T), 0, s, d_text, S.begin.as<uint64_t>(), S.len.as<uint32_t>(), n,
-                       S.out.as<uint8_t>(), S.sizes.as<uint32_t>(), S.adler.as<uint32_t>());
+    if (flags & LEON_BGZF_F_MATCHES) {
+        DEVCHK(S.lzdist.ensure((uint64_t)DF_LZ_MAX_GROUPS * DF_CHUNK * sizeof(uint16_t)));
+        hipLaunchKernelGGL(k_deflate_lz_chunks, dim3((uint32_t)std::min<uint64_t>(n, DF_LZ_MAX_GROUPS)), dim3(DF_T), 0, s, d_text, S.begin.as<uint64_t>(),
+                           S.len.as<uint32_t>(), n, S.out.as<uint8_t>(), S.sizes.as<uint32_t>(), S.adler.as<uint32_t>(), S.lzdist.as<uint16_t>());
+    } else
+        hipLaunchKernelGGL(k_deflate_chunks, dim3((uint32_t)std::min<uint64_t>(n, 1u << 20)), dim3(DF_T), 0, s, d_text, S.begin.as<uint64_t>(), S.len.as<uint32_t>(), n,
+                           S.out.as<uint8_t>(), S.sizes.as<uint32_t>(), S.adler.as<uint32_t>());
     DEVCHK(hipGetLastError());
     DEVCHK(hipMemsetAsync(S.crc.p, 0, n * 4, s));
     launch_crc32_segments(s, d_text, S.begin.as<uint64_t>(), n, crc32_tile_count(d_text, lo, hi), S.crc.as<uint32_t>());
@@ -747,15 +1026,16 @@ int bgzf_members_out(BgzfScratch& S, int device_id, hipStream_t s, const uint8_t
 
 // the n_text bytes at d_text as ceil(n_text / DF_CHUNK) members, delivered at `base` of the call's output; *out_size = their bytes
 int bgzf_slice(BgzfScratch& S, int device_id, hipStream_t s, const uint8_t* d_text, uint64_t n_text, uint64_t base, uint64_t text_base, leon_piece_sink sink, void* user,
-               BgzfIndex* ix, const std::string& who, uint64_t* out_size) {
+               BgzfIndex* ix, const std::string& who, uint32_t flags, uint64_t* out_size) {
     const uint64_t n = (n_text + DF_CHUNK - 1) / DF_CHUNK;
     DEVCHK(S.begin.ensure((n + 1) * 8)); DEVCHK(S.len.ensure(n * 4));
     hipLaunchKernelGGL(k_bgzf_table, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, s, n_text, n, S.begin.as<uint64_t>(), S.len.as<uint32_t>());
-    return bgzf_members_out(S, device_id, s, d_text, n, 0, n_text, base, text_base, sink, user, ix, who, out_size);
+    return bgzf_members_out(S, device_id, s, d_text, n, 0, n_text, base, text_base, sink, user, ix, who, flags, out_size);
 }
 
 // the fixed cuts of leon_text_bgzf_device and of leon_text_bgzf_records_device without records: `taken` bytes of d_text in slices
-int bgzf_fixed(int device_id, const uint8_t* d_text, uint64_t taken, leon_piece_sink sink, void* user, BgzfIndex* ix, const std::string& who, uint64_t* at, uint64_t* members) {
+int bgzf_fixed(int device_id, const uint8_t* d_text, uint64_t taken, leon_piece_sink sink, void* user, BgzfIndex* ix, const std::string& who, uint32_t flags, uint64_t* at,
+               uint64_t* members) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) { (void)hipGetLastError(); return dev_fail(LEON_E_NO_DEVICE, who + ": no such HIP device"); }
     if (device_id >= DF_MAX_DEVICES) return dev_fail(LEON_E_INVALID, who + ": device ordinal beyond the scratch table");
@@ -769,7 +1049,7 @@ int bgzf_fixed(int device_id, const uint8_t* d_text, uint64_t taken, leon_piece_
     for (uint64_t a = 0; a < taken; a += slice) {                 // sequential: a slice's base is the sum of the sizes before it
         const uint64_t m = std::min(slice, taken - a);
         uint64_t size = 0;
-        const int rc = bgzf_slice(S, device_id, st.s, d_text + a, m, *at, a, sink, user, ix, who, &size);
+        const int rc = bgzf_slice(S, device_id, st.s, d_text + a, m, *at, a, sink, user, ix, who, flags, &size);
         if (rc) return rc;
         *at += size; *members += (m + DF_CHUNK - 1) / DF_CHUNK;
     }
@@ -821,7 +1101,7 @@ extern "C" int leon_text_bgzf_device(int device_id, const uint8_t* d_text, uint6
     if (n_members) *n_members = 0;
     uint64_t at = 0, members = 0;
     if (taken) {
-        const int rc = bgzf_fixed(device_id, d_text, taken, sink, user, nullptr, "leon_text_bgzf_device", &at, &members);
+        const int rc = bgzf_fixed(device_id, d_text, taken, sink, user, nullptr, "leon_text_bgzf_device", 0, &at, &members);
         if (rc) return rc;
     }
     if (last) {
@@ -833,11 +1113,10 @@ extern "C" int leon_text_bgzf_device(int device_id, const uint8_t* d_text, uint6
     return LEON_OK;
 }
 
-/* the same with members cut at record starts and the members' places */
-extern "C" int leon_text_bgzf_records_device(int device_id, const uint8_t* d_text, uint64_t n_head, uint64_t n_body, const uint64_t* d_rec_off, uint64_t n_records, int last,
-                                             leon_piece_sink sink, void* user, uint64_t* n_taken, uint64_t* out_bytes, uint64_t* member_out_off,
-                                             uint64_t* member_text_off, uint64_t members_cap, uint64_t* n_members) {
-    const std::string who = "leon_text_bgzf_records_device";
+/* the same with members cut at record starts and the members' places; flags: which encoder */
+static int bgzf_records_call(const std::string& who, int device_id, const uint8_t* d_text, uint64_t n_head, uint64_t n_body, const uint64_t* d_rec_off, uint64_t n_records,
+                             int last, leon_piece_sink sink, void* user, uint64_t* n_taken, uint64_t* out_bytes, uint64_t* member_out_off, uint64_t* member_text_off,
+                             uint64_t members_cap, uint64_t* n_members, uint32_t flags) {
     auto fail = [&](int code, const std::string& why) { return dev_fail(code, who + ": " + why); };
     constexpr uint64_t W = DF_CHUNK;
     if (!d_text && (n_head || n_body)) return fail(LEON_E_INVALID, "d_text is NULL with text given");
@@ -845,6 +1124,7 @@ extern "C" int leon_text_bgzf_records_device(int device_id, const uint8_t* d_tex
     if (!n_taken) return fail(LEON_E_INVALID, "n_taken is NULL");
     if (!out_bytes) return fail(LEON_E_INVALID, "out_bytes is NULL");
     if (!n_members) return fail(LEON_E_INVALID, "n_members is NULL");
+    if (flags & ~(uint32_t)LEON_BGZF_F_MATCHES) return fail(LEON_E_INVALID, "unknown bits in flags");
     if ((member_out_off == nullptr) != (member_text_off == nullptr) || (!member_out_off && members_cap)) return fail(LEON_E_INVALID, "bgzf records: a half-given member table");
     if (const char* why = bgzf_records_refusal(d_rec_off != nullptr, n_records, n_head, n_body, last)) return fail(LEON_E_INVALID, why);
     *n_taken = 0; *out_bytes = 0; *n_members = 0;
@@ -858,7 +1138,7 @@ extern "C" int leon_text_bgzf_records_device(int device_id, const uint8_t* d_tex
         const uint64_t need = (taken + W - 1) / W;
         if (ix.out && need > members_cap) { *n_members = need; return fail(LEON_E_OVERFLOW, "the member table needs " + std::to_string(need) + " entries"); }
         if (taken) {
-            const int rc = bgzf_fixed(device_id, d_text, taken, sink, user, &ix, who, &at, &members);
+            const int rc = bgzf_fixed(device_id, d_text, taken, sink, user, &ix, who, flags, &at, &members);
             if (rc) return rc;
         }
     } else if (d_rec_off || n_text) {
@@ -907,7 +1187,7 @@ extern "C" int leon_text_bgzf_records_device(int device_id, const uint8_t* d_tex
                 return fail(LEON_E_OVERFLOW, "the cut table does not add up");
             if (n) {
                 uint64_t size = 0;
-                const int rc = bgzf_members_out(S, device_id, s, d_text, n, taken, end, at, 0, sink, user, &ix, who, &size);
+                const int rc = bgzf_members_out(S, device_id, s, d_text, n, taken, end, at, 0, sink, user, &ix, who, flags, &size);
                 if (rc) return rc;
                 at += size; members += n;
             }
@@ -923,6 +1203,19 @@ extern "C" int leon_text_bgzf_records_device(int device_id, const uint8_t* d_tex
     }
     *n_taken = taken; *out_bytes = at; *n_members = members;
     return LEON_OK;
+}
+
+extern "C" int leon_text_bgzf_records_device(int device_id, const uint8_t* d_text, uint64_t n_head, uint64_t n_body, const uint64_t* d_rec_off, uint64_t n_records, int last,
+                                             leon_piece_sink sink, void* user, uint64_t* n_taken, uint64_t* out_bytes, uint64_t* member_out_off,
+                                             uint64_t* member_text_off, uint64_t members_cap, uint64_t* n_members) {
+    return bgzf_records_call("leon_text_bgzf_records_device", device_id, d_text, n_head, n_body, d_rec_off, n_records, last, sink, user, n_taken, out_bytes, member_out_off,
+                             member_text_off, members_cap, n_members, 0);
+}
+extern "C" int leon_text_bgzf_device_ex(int device_id, const uint8_t* d_text, uint64_t n_head, uint64_t n_body, const uint64_t* d_rec_off, uint64_t n_records, int last,
+                                        leon_piece_sink sink, void* user, uint64_t* n_taken, uint64_t* out_bytes, uint64_t* member_out_off, uint64_t* member_text_off,
+                                        uint64_t members_cap, uint64_t* n_members, uint32_t flags) {
+    return bgzf_records_call("leon_text_bgzf_device_ex", device_id, d_text, n_head, n_body, d_rec_off, n_records, last, sink, user, n_taken, out_bytes, member_out_off,
+                             member_text_off, members_cap, n_members, flags);
 }
 
 /* the device buffers leon_qual_deflate_blocks_device keeps from call to call (about 1.5 GB after a large call) */

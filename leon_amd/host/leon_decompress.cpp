@@ -154,14 +154,15 @@ Metadata read_metadata(Container& in, const std::string& file) {
 // the same bytes however the text was cut into rounds and whoever formatted them.  All of it is stage C's (one round at a time).
 // `-gz-records`: the members are cut at record starts (leon_text_bgzf_records_device with the records' offsets), and
 // the carry -- whole records, at most one member's text -- is the next call's head.  `-gz-index`: every member's place in the file and
-// in the text is kept for X.d.gz.gzi.
+// in the text is kept for X.d.gz.gzi.  `-gz-matches`: the members' blocks come from k_deflate_lz_chunks
+// (leon_text_bgzf_device_ex with LEON_BGZF_F_MATCHES); cuts, carry and index are the same.
 struct BgzfWriter {
     static constexpr uint64_t HEAD = LEON_BGZF_MEMBER_TEXT;  // room in front of a round's text for the carry (at most one member's text)
     int fd = -1, device = 0;
     const std::string* out_name = nullptr;
     std::vector<uint8_t> carry;
     uint64_t file_at = 0, members = 0, text = 0;
-    bool closed = false, records = false, index = false;
+    bool closed = false, records = false, index = false, matches = false;
     std::vector<uint64_t> gzi;                               // `-gz-index`: per data member, its offset in the file and in the text
     std::vector<uint64_t> m_out, m_text;
     // n_head + n_body bytes of device memory (the carry and a text behind it) through the call; returns the bytes it took.  The body's
@@ -170,7 +171,7 @@ struct BgzfWriter {
         FileSink sink{fd, file_at};
         uint64_t taken = 0, out_bytes = 0, n_members = 0;
         const uint64_t n_all = n_head + n_body;
-        if (!records && !index) {
+        if (!records && !index && !matches) {
             const int rc = leon_text_bgzf_device(device, d_all, n_all, last ? 1 : 0, FileSink::piece, &sink, &taken, &out_bytes, &n_members);
             if (rc == LEON_E_SINK) throw Exception("cannot write " + *out_name);
             check(nullptr, rc, "leon_text_bgzf_device");
@@ -178,10 +179,13 @@ struct BgzfWriter {
             if (!records) { n_head = 0; n_body = n_all; d_rec_off = nullptr; n_records = 0; }      // fixed cuts, with the members' places
             const uint64_t cap = !index ? 0 : records ? 3 * (n_all / HEAD) + 2 : n_all / HEAD + 1;
             if (m_out.size() < cap) { m_out.resize(cap); m_text.resize(cap); }
-            const int rc = leon_text_bgzf_records_device(device, d_all, n_head, n_body, d_rec_off, n_records, last ? 1 : 0, FileSink::piece, &sink, &taken, &out_bytes,
-                                                         index ? m_out.data() : nullptr, index ? m_text.data() : nullptr, cap, &n_members);
+            uint64_t* const t_out = index ? m_out.data() : nullptr, * const t_text = index ? m_text.data() : nullptr;
+            const int rc = matches ? leon_text_bgzf_device_ex(device, d_all, n_head, n_body, d_rec_off, n_records, last ? 1 : 0, FileSink::piece, &sink, &taken, &out_bytes,
+                                                              t_out, t_text, cap, &n_members, LEON_BGZF_F_MATCHES)
+                                   : leon_text_bgzf_records_device(device, d_all, n_head, n_body, d_rec_off, n_records, last ? 1 : 0, FileSink::piece, &sink, &taken,
+                                                                   &out_bytes, t_out, t_text, cap, &n_members);
             if (rc == LEON_E_SINK) throw Exception("cannot write " + *out_name);
-            check(nullptr, rc, "leon_text_bgzf_records_device");
+            check(nullptr, rc, matches ? "leon_text_bgzf_device_ex" : "leon_text_bgzf_records_device");
             if (index) for (uint64_t c = 0; c < n_members; c++) { gzi.push_back(file_at + m_out[c]); gzi.push_back(text + m_text[c]); }
         }
         file_at += out_bytes; members += n_members; text += taken;
@@ -400,7 +404,7 @@ void Decoder::open_output() {
     if (ofd.fd < 0) throw Exception("cannot write " + o._outputFilename);
     ofd.path = out_path;
     gz.fd = ofd.fd; gz.device = dev; gz.out_name = &o._outputFilename;
-    gz.records = o._gzRecords; gz.index = o._gzIndex;
+    gz.records = o._gzRecords; gz.index = o._gzIndex; gz.matches = o._gzMatches;
     if (o._gzIndex) {                                        // X.fastq.d.gz.gzi, under a temporary name like the file it belongs to
         gzi_fd.fd = ::open((o._outputFilename + ".gzi.tmp").c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (gzi_fd.fd < 0) throw Exception("cannot write " + o._outputFilename + ".gzi");
@@ -988,7 +992,7 @@ void Decoder::report() {
     if (m.fastq_out)
         std::cout << "quality blocks: " << (qi_device ? rounds_text("k_qual_inflate", qi_rounds_on_device.load(), qi_rounds_no_memory.load()) : std::string("host threads")) << std::endl;
     if (o._gz)
-        std::cout << "output: BGZF on the device (k_deflate_chunks, k_bgzf_members), " << gz.members << " member(s), " << gz.text << " -> " << gz.file_at << " bytes"
+        std::cout << "output: BGZF on the device (" << (o._gzMatches ? "k_deflate_lz_chunks" : "k_deflate_chunks") << ", k_bgzf_members), " << gz.members << " member(s), " << gz.text << " -> " << gz.file_at << " bytes"
                   << (o._gzRecords ? ", record-aligned" : "")
                   << (o._gzIndex ? ", index " + o._outputFilename + ".gzi (" + std::to_string(gz.members ? gz.members - 1 : 0) + " entries)" : std::string()) << std::endl;
 }

@@ -57,6 +57,7 @@ void Leon::run(int argc, char* argv[]) {
             else if (a == "-gz") _gz = true;
             else if (a == "-gz-records") _gzRecords = true;
             else if (a == "-gz-index") _gzIndex = true;
+            else if (a == "-gz-matches") _gzMatches = true;
             else if (a == "-dict-pieces") _dictPieces = true;
             else if (a == "-dict-piece-anchors") {
                 const long v = number("-dict-piece-anchors");
@@ -80,6 +81,7 @@ void Leon::run(int argc, char* argv[]) {
         if (_gz && _compress) throw Exception("option -gz belongs to -d");
         if (_gzRecords && !_gz) throw Exception("option -gz-records belongs to -gz");
         if (_gzIndex && !_gz) throw Exception("option -gz-index belongs to -gz");
+        if (_gzMatches && !_gz) throw Exception("option -gz-matches belongs to -gz");
         if (!_inputInflate.empty() && _decompress) throw Exception("option -input-inflate belongs to -c");
         if (!_recordParse.empty() && _decompress) throw Exception("option -record-parse belongs to -c");
         if (_recordParseFasta && (_recordParse.empty() || !record_parse_on_device(_recordParse))) throw Exception("option -record-parse-fasta belongs to -record-parse device");

@@ -53,6 +53,7 @@ public:
     bool _gzRecords = false;              // -d -gz: -gz-records: the members cut at record starts
     bool _dictPieces = false;             // -c -dict-pieces: the anchor dictionary written as independently coded pieces, coded on the device
     uint32_t _dictPieceAnchors = 0;       // -c -dict-pieces -dict-piece-anchors N: anchors per piece (0: the library's default, 1024)
+    bool _gzMatches = false;              // -d -gz: -gz-matches: LZ77 matches in the members, k_deflate_lz_chunks
     bool _gzIndex = false;                // -d -gz: -gz-index: X.d.gz.gzi beside the file, every member's offset in the file and in the text
     std::string _qualDeflate;             // -qual-deflate host|device|auto; empty = not given: zlib on the host threads (the reference's bytes)
     std::string _inputInflate;            // -c: -input-inflate host|device|auto; empty = not given: a gzip input inflated by zlib on the reader's thread

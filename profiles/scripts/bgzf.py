@@ -11,6 +11,9 @@
                                        record's offset (found on the device: every fourth newline), one warm-up call on the first records
                                        and TWO whole calls, with member tables; the JSON line gains the calls' wall times, members and
                                        bytes.  Under `rocprofv3 --kernel-trace --stats`: k_bgzf_cuts beside k_deflate_chunks
+  bgzf.py --kernel [N] --matches       the same calls through leon_text_bgzf_device_ex with LEON_BGZF_F_MATCHES (fixed cuts, no member table;
+                                       DESIGN.md 4.18): k_deflate_lz_chunks in the place of k_deflate_chunks, on the same text; the JSON line's
+                                       keys keep their names and gain "matches": true.  (--records keeps the encoder without matches.)
   bgzf.py --cli N --parent LEON        `leon -d`, `leon -d -gz` and the parent commit's `leon -d` on the lossless container of an N-read
                                        150 bp FASTQ in a RAM-backed directory, alternating, three each, -header-text device -record-text
                                        device -qual-inflate device on every side; the output sizes and the `time:` and `output:` lines of
@@ -38,6 +41,7 @@ from leon_amd import capi  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--kernel", type=int, nargs="?", const=10_000_000, default=0)
 ap.add_argument("--records", action="store_true")
+ap.add_argument("--matches", action="store_true")
 ap.add_argument("--cli", type=int, default=0)
 ap.add_argument("--parent", default="")
 ap.add_argument("--dir", default="/dev/shm/leon_bgzf")
@@ -72,7 +76,11 @@ def kernel():
 
     def call(n_text):
         counted[0] = 0
-        rc = lib.leon_text_bgzf_device(0, C.c_void_p(d.data_ptr()), n_text, 1, sink, None, C.byref(taken), C.byref(out_bytes), C.byref(members))
+        if args.matches:
+            rc = lib.leon_text_bgzf_device_ex(0, C.c_void_p(d.data_ptr()), 0, n_text, None, 0, 1, sink, None, C.byref(taken), C.byref(out_bytes), None, None, 0,
+                                              C.byref(members), capi.BGZF_F_MATCHES)
+        else:
+            rc = lib.leon_text_bgzf_device(0, C.c_void_p(d.data_ptr()), n_text, 1, sink, None, C.byref(taken), C.byref(out_bytes), C.byref(members))
         assert rc == 0, lib.leon_last_error(None)
         assert counted[0] == out_bytes.value and taken.value == n_text
     call(capi.BGZF_MEMBER_TEXT)                                   # (code objects loaded, scratch for one member)
@@ -84,7 +92,7 @@ def kernel():
     whole = {"members": members.value, "out_bytes": out_bytes.value}
     m = min(n, SAMPLE)
     sample = text[:m].tobytes()
-    got, _, _ = capi.text_bgzf_device(d.data_ptr(), m)
+    got = capi.text_bgzf_device_ex(d.data_ptr(), 0, m, 0, 0, flags=capi.BGZF_F_MATCHES, tables=False)[0] if args.matches else capi.text_bgzf_device(d.data_ptr(), m)[0]
     t0 = time.perf_counter()
     z6 = len(zlib.compress(sample, 6))
     z6_s = time.perf_counter() - t0
@@ -116,7 +124,7 @@ def kernel():
         assert m_text[0] == 0 and (np.diff(m_text[:members.value].astype(np.int64)) <= capi.BGZF_MEMBER_TEXT).all()
         rec = {"leon_text_bgzf_records_device_ms": rms, "records_members": members.value, "records_out_bytes": out_bytes.value,
                "records_out_per_fixed_out": round(out_bytes.value / whole["out_bytes"], 6)}
-    print(json.dumps({"reads": N, "text_bytes": n, "leon_text_bgzf_device_ms": ms, **whole, **rec, "text_per_out": round(n / whole["out_bytes"], 4),
+    print(json.dumps({"reads": N, "text_bytes": n, "matches": args.matches, "leon_text_bgzf_device_ms": ms, **whole, **rec, "text_per_out": round(n / whole["out_bytes"], 4),
                       "sample_bytes": m, "sample_out_bytes": len(got), "sample_reads_back": gzip.decompress(got) == sample,
                       "sample_zlib6_bytes": z6, "sample_zlib6_one_thread_gb_s": round(m / z6_s / 1e9, 4), "sample_zlib_rle_bytes": zrle,
                       "float4_copy_tb_s": COPY_TBS,
