@@ -354,6 +354,31 @@ typedef struct leon_record_layout {
 int leon_records_format_device(int device_id, const leon_record_layout* lay, const uint8_t* d_bases, const uint32_t* d_len, uint64_t n_reads,
                                uint64_t n_bases, const uint8_t* d_hdr_text, const uint64_t* d_hdr_off, const uint8_t* d_quals, uint8_t* d_text,
                                uint64_t text_cap, uint64_t* d_rec_off, uint64_t* text_size);
+/* -- the same reads as unaligned BAM records (k_bam_sizes, k_bam_records: DESIGN.md 4.19) --
+ * The uncompressed content of a BAM file is leon_bam_header's bytes ("BAM\1", l_text, the text "@HD\tVN:1.6\tSO:unsorted\n", n_ref = 0)
+ * and then one record per read, little-endian:
+ *     block_size (the bytes that follow)  refID -1  pos -1  l_read_name (counting its NUL)  mapq 0  bin 4680  n_cigar_op 0  flag 4
+ *     l_seq  next_refID -1  next_pos -1  tlen 0  |  the name, NUL  |  (l_seq + 1) / 2 bytes, two bases a byte, the first in the high
+ *     nybble, codes from "=ACMGRSVTWYHKDBN" whatever the case, any other byte 15  |  l_seq quality bytes, the FASTQ byte - 33  |
+ *     'C' 'O' 'Z' the comment, NUL -- when there is a comment
+ * The name is header r up to its first space or tab ("*" when empty; the decimal read index without a header stream), the comment what
+ * follows that one byte.  [RECALLED from the SAM/BAM specification; parity with htslib's reader is unpinned.]
+ * Arguments as leon_records_format_device's; lead, wrap and plus_kind of the layout are ignored; fastq == 0 or d_quals == NULL: every
+ * quality byte is 0xFF.  d_out needs no alignment.  d_rec_off (may be NULL): n_reads + 1 record offsets ([0] = 0 also with no read).
+ * LEON_E_OVERFLOW when out_cap is smaller (or d_out NULL): *out_size = the bytes needed, nothing written.  LEON_E_INVALID, nothing
+ * written: lengths that do not add up to n_bases, header offsets that run backwards or do not end at hdr_bytes, an unknown struct_size,
+ * a name of more than 254 bytes ("read N: its name has M bytes, BAM allows 254").  LEON_E_INVALID after the records were written (they
+ * are to be discarded): "read N: a quality byte below 33".  N is the smallest such read of the call, counted from first_read_index.
+ * leon_host_records_bam: the same bytes and verdicts from host memory, on n_threads threads (0: all usable), no GPU.
+ * leon_bam_header: *size = the header's bytes; LEON_E_OVERFLOW when cap is smaller (or out NULL).  A file is these bytes and the records
+ * through leon_text_bgzf_device (or _records_device / _ex, the header as the first call's head) with its EOF marker. */
+int leon_records_bam_device(int device_id, const leon_record_layout* lay, const uint8_t* d_bases, const uint32_t* d_len, uint64_t n_reads,
+                            uint64_t n_bases, const uint8_t* d_hdr_text, const uint64_t* d_hdr_off, const uint8_t* d_quals, uint8_t* d_out,
+                            uint64_t out_cap, uint64_t* d_rec_off, uint64_t* out_size);
+int leon_host_records_bam(const leon_record_layout* lay, const uint8_t* bases, const uint32_t* len, uint64_t n_reads, uint64_t n_bases,
+                          const uint8_t* hdr_text, const uint64_t* hdr_off, const uint8_t* quals, uint8_t* out, uint64_t out_cap,
+                          uint64_t* rec_off, uint64_t* out_size, uint32_t n_threads);
+int leon_bam_header(uint8_t* out, uint64_t cap, uint64_t* size);
 /* Device memory to a sink, in the pinned pieces the copy lands in (no second copy into pageable memory): the sink receives pieces of at
  * most 16 MiB, every byte of [0, bytes) exactly once, disjoint, IN NO PARTICULAR ORDER AND FROM UP TO LEON_UPLOAD_THREADS (default 3)
  * THREADS AT ONCE; a piece is valid until the sink returns.  Non-zero from the sink stops the call with LEON_E_SINK (pieces already

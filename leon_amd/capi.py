@@ -118,6 +118,11 @@ _EXPORTS = {
                                                  C.c_void_p, _u32p]),
     "leon_records_format_device": (C.c_int, [C.c_int, C.POINTER(RecordLayout), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, _u64p]),
+    "leon_records_bam_device": (C.c_int, [C.c_int, C.POINTER(RecordLayout), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, _u64p]),
+    "leon_host_records_bam": (C.c_int, [C.POINTER(RecordLayout), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_uint64, C.c_void_p, _u64p, C.c_uint32]),
+    "leon_bam_header": (C.c_int, [C.c_void_p, C.c_uint64, _u64p]),
     "leon_device_download_pieces": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, PIECE_SINK, C.c_void_p]),
     "leon_host_anchor_dict_decode": (C.c_int, [_u8p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p]),
     "leon_dna_finish": (C.c_int, [C.c_void_p, C.POINTER(_u8p), _u64p, _u64p]),
@@ -1006,6 +1011,84 @@ def records_format_device(d_bases, d_len, n_reads, n_bases, d_text, text_cap, le
         err.text_size = int(size.value)
         raise err
     return int(size.value)
+
+
+def _bam_layout(fastq, first_read_index, hdr_bytes, struct_size):
+    lay = RecordLayout()
+    lay.struct_size = C.sizeof(RecordLayout) if struct_size is None else struct_size
+    lay.lead, lay.fastq = (b"@" if fastq else b">")[0], 1 if fastq else 0
+    lay.first_read_index, lay.hdr_bytes = int(first_read_index), int(hdr_bytes)
+    return lay
+
+
+def records_bam_device(d_bases, d_len, n_reads, n_bases, d_out, out_cap, fastq=True, first_read_index=0, d_hdr_text=None, d_hdr_off=None,
+                       hdr_bytes=0, d_quals=None, d_rec_off=None, device_id=0, struct_size=None):
+    """leon_records_bam_device over raw device pointers: the reads as unaligned BAM records into d_out.  Returns the records' size;
+    a LeonDnaError carries .out_size (the bytes needed) when the capacity was too small"""
+    lib = load_library()
+    lay = _bam_layout(fastq, first_read_index, hdr_bytes, struct_size)
+    size = C.c_uint64()
+    vp = lambda p: C.c_void_p(int(p)) if p else None
+    rc = lib.leon_records_bam_device(device_id, C.byref(lay), vp(d_bases), vp(d_len), int(n_reads), int(n_bases), vp(d_hdr_text), vp(d_hdr_off),
+                                     vp(d_quals), vp(d_out), int(out_cap), vp(d_rec_off), C.byref(size))
+    if rc:
+        err = LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+        err.out_size = int(size.value)
+        raise err
+    return int(size.value)
+
+
+def host_records_bam(bases, lens, n_bases=None, fastq=True, first_read_index=0, hdr_text=None, hdr_off=None, hdr_bytes=None, quals=None, out_cap=None,
+                     n_threads=1, struct_size=None):
+    """leon_host_records_bam (no GPU): bases / hdr_text / quals bytes-like (hdr_text, quals may be None), lens the reads' lengths, hdr_off
+    n_reads + 1 offsets whose first entry is hdr_text's first byte.  out_cap None: sized by a first call.  Returns (records as bytes,
+    rec_off as a uint64 array of n_reads + 1 entries); a LeonDnaError carries .out_size"""
+    lib = load_library()
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    n = len(lens)
+    lens_buf = np.concatenate([lens, np.zeros(1, dtype=np.uint32)])
+    b = np.frombuffer(bytes(bases) + b"\0", dtype=np.uint8)
+    h = None if hdr_text is None else np.frombuffer(bytes(hdr_text) + b"\0", dtype=np.uint8)
+    ho = None if hdr_off is None else np.ascontiguousarray(hdr_off, dtype=np.uint64)
+    q = None if quals is None else np.frombuffer(bytes(quals) + b"\0", dtype=np.uint8)
+    if hdr_bytes is None:
+        hdr_bytes = 0 if h is None else len(h) - 1
+    lay = _bam_layout(fastq, first_read_index, hdr_bytes, struct_size)
+    n_bases = len(b) - 1 if n_bases is None else int(n_bases)
+    vp = lambda a: C.c_void_p(0 if a is None else a.ctypes.data)
+    size = C.c_uint64()
+
+    def call(out, cap, rec):
+        rc = lib.leon_host_records_bam(C.byref(lay), vp(b), vp(lens_buf), n, n_bases, vp(h), vp(ho), vp(q), vp(out), int(cap), vp(rec), C.byref(size),
+                                       int(n_threads))
+        if rc:
+            err = LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+            err.out_size = int(size.value)
+            raise err
+    if out_cap is None:
+        try:
+            call(None, 0, None)
+            out_cap = 0
+        except LeonDnaError as e:
+            if e.code != -5:
+                raise
+            out_cap = e.out_size
+    out = np.full(int(out_cap) + 1, 0xA5, dtype=np.uint8)
+    rec = np.zeros(n + 1, dtype=np.uint64)
+    call(out, out_cap, rec)
+    assert out[size.value:].tobytes() == b"\xa5" * (len(out) - size.value), "leon_host_records_bam wrote past the size it reports"
+    return out[:size.value].tobytes(), rec
+
+
+def bam_header():
+    """leon_bam_header: the bytes a BAM file's uncompressed content begins with"""
+    lib = load_library()
+    size = C.c_uint64()
+    out = np.zeros(256, dtype=np.uint8)
+    rc = lib.leon_bam_header(C.c_void_p(out.ctypes.data), len(out), C.byref(size))
+    if rc:
+        raise LeonDnaError(rc, (lib.leon_last_error(None) or b"").decode())
+    return out[:size.value].tobytes()
 
 
 class DnaEncodeContext:

@@ -9,6 +9,7 @@
 // writes the text OUTPUT-driven: a lane per 16 aligned output bytes, the way k_pack writes its slots.
 #include "kernels.h"
 #include "prim.h"
+#include "fmt_shared.h"
 #include "device_call.h"
 
 #include <algorithm>
@@ -16,36 +17,10 @@
 namespace leon {
 
 struct FmtLayout { uint64_t first_read_index, hdr_bytes; uint32_t wrap; uint8_t lead, fastq, plus_kind; };
-struct FmtPair {                                               // what the scan carries: a record's text offset and its first base
-    uint64_t rec, base;
-    FmtPair() = default;
-    __host__ __device__ FmtPair(int v) : rec((uint64_t)v), base((uint64_t)v) {}
-    __host__ __device__ FmtPair(uint64_t r, uint64_t b) : rec(r), base(b) {}
-    __host__ __device__ FmtPair operator+(const FmtPair& o) const { return FmtPair(rec + o.rec, base + o.base); }
-};
-
 namespace {
 
-constexpr uint32_t FMT_THREADS = 256;
-constexpr uint32_t FMT_TILE = FMT_THREADS * 16;                 // output bytes a workgroup owns
-constexpr uint32_t FMT_STAGE = 256;                             // records whose offsets one pass holds in LDS
 constexpr uint32_t FMT_MIN_RECORD = 3;                          // lead, '\n', '\n': an empty header and an empty FASTA read
 constexpr uint32_t FMT_MAX_PASSES = FMT_TILE / FMT_MIN_RECORD / FMT_STAGE + 2;
-
-__constant__ uint64_t kPow10[20] = {1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull, 100000000ull, 1000000000ull,
-                                    10000000000ull, 100000000000ull, 1000000000000ull, 10000000000000ull, 100000000000000ull,
-                                    1000000000000000ull, 10000000000000000ull, 100000000000000000ull, 1000000000000000000ull,
-                                    10000000000000000000ull};
-
-__device__ __forceinline__ uint32_t dec_digits(uint64_t v) {
-    uint32_t n = 1;
-#pragma unroll
-    for (uint32_t k = 1; k < 20; k++) n += v >= kPow10[k];
-    return n;
-}
-
-__device__ __forceinline__ uint64_t min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
-__device__ __forceinline__ uint64_t max64(uint64_t a, uint64_t b) { return a > b ? a : b; }
 
 __device__ __forceinline__ uint64_t seq_text_len(uint64_t len, uint32_t wrap) {
     return wrap && len > wrap ? len + (len + wrap - 1) / wrap : len + 1;
@@ -73,11 +48,6 @@ __global__ __launch_bounds__(256) void k_fmt_sizes(FmtLayout L, const uint32_t* 
     in[r].base = l;
 }
 
-__global__ __launch_bounds__(256) void k_fmt_rec_off(const FmtPair* __restrict__ off, uint64_t n, uint64_t* __restrict__ rec_off) {
-    const uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (r <= n) rec_off[r] = off[r].rec;
-}
-
 // what a lane keeps of the record it is in
 struct FmtRec {
     uint64_t rec0, rec1;            // the record's text [rec0, rec1)
@@ -85,27 +55,6 @@ struct FmtRec {
     uint64_t hbase, bbase;          // first header byte / first base (and quality) of the record
     uint64_t index;                 // its read index (no header stream)
 };
-
-// The record text byte t lies in: the r with off[r].rec <= t < off[r + 1].rec (off[0].rec == 0, off[n_reads].rec == text_size > t).
-// The search starts from a guess g < n_reads, brackets the answer by doubling steps away from it and bisects inside the bracket: a
-// handful of dependent loads for a good guess where a bisection of all of off[] takes log2(n_reads) of them.
-__device__ __forceinline__ uint64_t fmt_record_of(const FmtPair* __restrict__ off, uint64_t n_reads, uint64_t t, uint64_t g) {
-    uint64_t lo, hi;
-    if (off[g].rec <= t) {
-        lo = g; hi = n_reads;
-        for (uint64_t step = 1; lo + step < n_reads; step <<= 1) {
-            if (off[lo + step].rec <= t) lo += step; else { hi = lo + step; break; }
-        }
-    } else {
-        lo = 0; hi = g;
-        for (uint64_t step = 1; hi > step; step <<= 1) {
-            if (off[hi - step].rec <= t) { lo = hi - step; break; }
-            hi -= step;
-        }
-    }
-    while (hi - lo > 1) { const uint64_t mid = lo + ((hi - lo) >> 1); if (off[mid].rec <= t) lo = mid; else hi = mid; }
-    return lo;
-}
 
 // The run of record R that byte o begins: its bytes either lie back to back in one of the sources (the pointer to byte o's source,
 // the run ending before record offset `end`) or are one byte the record's shape gives (nullptr, the byte in lit, end = o + 1)
@@ -176,11 +125,7 @@ __global__ __launch_bounds__(256) void k_fmt_records(FmtLayout L, const FmtPair*
     for (uint32_t pass = 0; pass < FMT_MAX_PASSES; pass++) {
         if (first > last) break;
         const uint32_t cnt = (uint32_t)min64(FMT_STAGE, last + 1 - first);
-        for (uint32_t i = threadIdx.x; i <= cnt; i += FMT_THREADS) {
-            const FmtPair p = off[first + i];
-            s_rec[i] = p.rec; s_base[i] = p.base;
-            s_hdr[i] = hdr_off ? hdr_off[first + i] - hdr0 : 0;
-        }
+        fmt_stage(off, hdr_off, hdr0, first, cnt, s_rec, s_base, s_hdr);
         __syncthreads();
         const uint64_t p_end = s_rec[cnt];
         const uint64_t t = max64(c_lo, s_rec[0]);
@@ -236,16 +181,6 @@ void launch_fmt_sizes(hipStream_t s, const FmtLayout& L, const uint32_t* len, co
     hipLaunchKernelGGL(k_fmt_sizes, dim3((uint32_t)blocks), dim3(256), 0, s, L, len, hdr_off, n_reads, in, flags);
 }
 
-// exclusive, n_reads + 1 entries: out[n_reads] = the totals
-hipError_t fmt_scan(void* tmp, size_t& bytes, const FmtPair* in, FmtPair* out, uint64_t n_reads, hipStream_t s) {
-    return prim::ExclusiveSum(tmp, bytes, in, out, n_reads + 1, s);
-}
-
-void launch_fmt_rec_off(hipStream_t s, const FmtPair* off, uint64_t n_reads, uint64_t* rec_off) {
-    const uint64_t blocks = (n_reads + 1 + 255) / 256;
-    hipLaunchKernelGGL(k_fmt_rec_off, dim3((uint32_t)blocks), dim3(256), 0, s, off, n_reads, rec_off);
-}
-
 // the text itself; the caller has verified off[n_reads] == (text_size, the bases given) and both flags of launch_fmt_sizes
 void launch_fmt_records(hipStream_t s, const FmtLayout& L, const FmtPair* off, const uint64_t* hdr_off, uint64_t n_reads, const uint8_t* bases,
                         const uint8_t* hdr, const uint8_t* quals, uint8_t* text, uint64_t text_size) {
@@ -256,6 +191,23 @@ void launch_fmt_records(hipStream_t s, const FmtLayout& L, const FmtPair* off, c
 }
 
 }  // namespace
+
+// (both shared with bam_kernels.hip: fmt_shared.h)
+__global__ __launch_bounds__(256) void k_fmt_rec_off(const FmtPair* __restrict__ off, uint64_t n, uint64_t* __restrict__ rec_off) {
+    const uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (r <= n) rec_off[r] = off[r].rec;
+}
+
+// exclusive, n_reads + 1 entries: out[n_reads] = the totals
+hipError_t fmt_scan(void* tmp, size_t& bytes, const FmtPair* in, FmtPair* out, uint64_t n_reads, hipStream_t s) {
+    return prim::ExclusiveSum(tmp, bytes, in, out, n_reads + 1, s);
+}
+
+void launch_fmt_rec_off(hipStream_t s, const FmtPair* off, uint64_t n_reads, uint64_t* rec_off) {
+    const uint64_t blocks = (n_reads + 1 + 255) / 256;
+    hipLaunchKernelGGL(k_fmt_rec_off, dim3((uint32_t)blocks), dim3(256), 0, s, off, n_reads, rec_off);
+}
+
 }  // namespace leon
 
 using namespace leon;

@@ -21,6 +21,7 @@
 #include "host_bgzf.h"
 #include "host_fastq.h"
 #include "host_fasta.h"
+#include "host_bam.h"
 
 namespace leon { void set_create_error(const std::string& msg); }
 
@@ -646,4 +647,27 @@ int leon_host_fasta_split(const uint8_t* text, uint64_t n_text, int last, uint64
         return fail(rc, "leon_host_fasta_split: " + std::to_string(res->n_records) + " records need " + std::to_string(res->header_bytes) + " header bytes, " +
                             std::to_string(res->base_bytes) + " bases and " + std::to_string(res->n_records + 1) + " table entries");
     return rc;
+}
+
+extern "C"
+int leon_host_records_bam(const leon_record_layout* lay, const uint8_t* bases, const uint32_t* len, uint64_t n_reads, uint64_t n_bases, const uint8_t* hdr_text,
+                          const uint64_t* hdr_off, const uint8_t* quals, uint8_t* out, uint64_t out_cap, uint64_t* rec_off, uint64_t* out_size,
+                          uint32_t n_threads) {
+    static const char* const who = "leon_host_records_bam";
+    if (out_size) *out_size = 0;
+    std::string why = leon::bam_args_refusal(who, lay, bases, len, n_reads, n_bases, hdr_text, hdr_off, out_size);
+    if (!why.empty()) return fail(LEON_E_INVALID, why);
+    const int rc = leon::bam_records_host(who, lay, bases, len, n_reads, n_bases, hdr_text, hdr_off, quals, out, out_cap, rec_off, out_size,
+                                          n_threads ? n_threads : usable_cpus(), why);
+    return rc ? fail(rc, why) : LEON_OK;
+}
+
+extern "C"
+int leon_bam_header(uint8_t* out, uint64_t cap, uint64_t* size) {
+    if (!size) return fail(LEON_E_INVALID, "leon_bam_header: size is NULL");
+    const std::string h = leon::bam_header_bytes();
+    *size = h.size();
+    if (h.size() > cap || !out) return fail(LEON_E_OVERFLOW, "leon_bam_header: the header needs " + std::to_string(h.size()) + " bytes");
+    memcpy(out, h.data(), h.size());
+    return LEON_OK;
 }

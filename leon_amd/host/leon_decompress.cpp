@@ -156,6 +156,8 @@ Metadata read_metadata(Container& in, const std::string& file) {
 // the carry -- whole records, at most one member's text -- is the next call's head.  `-gz-index`: every member's place in the file and
 // in the text is kept for X.d.gz.gzi.  `-gz-matches`: the members' blocks come from k_deflate_lz_chunks
 // (leon_text_bgzf_device_ex with LEON_BGZF_F_MATCHES); cuts, carry and index are the same.
+// `-bam`: the same writer over unaligned BAM records (leon_records_bam_device / leon_host_records_bam) where `-gz` has
+// the records' text; the BAM header is the carry the writer begins with, the head of its first call (one record start of its own).
 struct BgzfWriter {
     static constexpr uint64_t HEAD = LEON_BGZF_MEMBER_TEXT;  // room in front of a round's text for the carry (at most one member's text)
     int fd = -1, device = 0;
@@ -334,6 +336,9 @@ struct Decoder {
     void write_round(Round& R);
     void format_records(const Round& R, const std::vector<uint64_t>& rec_off, const std::vector<uint64_t>& base_at, char* tbase, uint64_t ra, uint64_t rb) const;
     bool write_round_device(Round& R);
+    uint64_t bam_bound(const Round& R) const;
+    void bam_check(int rc, const char* what) const;
+    void write_round_bam_host(Round& R);
     void download_text(const Round& R, const uint8_t* d_txt);
     void round_to_host(Round& R);
     void finish();
@@ -398,13 +403,19 @@ void Decoder::open_output() {
     std::string stem = file;
     if (ends_with(stem, ".leon")) stem.resize(stem.size() - 5);
     // `-gz`: X.fastq.d.gz, BGZF written under a temporary name and renamed at the very end
-    o._outputFilename = stem + (o._gz ? ".d.gz" : ".d");
+    o._outputFilename = stem + (o._bam ? ".d.bam" : o._gz ? ".d.gz" : ".d");
     out_path = o._gz ? o._outputFilename + ".tmp" : o._outputFilename;
     ofd.fd = ::open(out_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
     if (ofd.fd < 0) throw Exception("cannot write " + o._outputFilename);
     ofd.path = out_path;
     gz.fd = ofd.fd; gz.device = dev; gz.out_name = &o._outputFilename;
     gz.records = o._gzRecords; gz.index = o._gzIndex; gz.matches = o._gzMatches;
+    if (o._bam) {                                            // the BAM header: what the first call finds in front of its records
+        uint64_t n = 0;
+        gz.carry.resize(64);
+        check(nullptr, leon_bam_header(gz.carry.data(), gz.carry.size(), &n), "leon_bam_header");
+        gz.carry.resize(n);
+    }
     if (o._gzIndex) {                                        // X.fastq.d.gz.gzi, under a temporary name like the file it belongs to
         gzi_fd.fd = ::open((o._outputFilename + ".gzi.tmp").c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (gzi_fd.fd < 0) throw Exception("cannot write " + o._outputFilename + ".gzi");
@@ -422,7 +433,7 @@ void Decoder::choose_ways() {
     const uint64_t n_blocks = m.p.n_blocks;
     // `-record-text`: the records formatted on the device, where every '+' line is of one kind
     rt_asked = n_blocks > 0 && device_chosen(parse_choice("-record-text", o._recordText), n_blocks, kRecordTextAutoBlocks);
-    if (rt_asked && (!m.plus.exc.empty() || m.plus.def > 1)) rt_reason = "the '+' lines are mixed: exception records in the pluslines table";
+    if (rt_asked && !o._bam && (!m.plus.exc.empty() || m.plus.def > 1)) rt_reason = "the '+' lines are mixed: exception records in the pluslines table";
     rt_device = rt_asked && rt_reason.empty();
     // `-qual-inflate`: the quality blocks inflated on the device
     qi_device = m.fastq_out && n_blocks > 0 && device_chosen(parse_choice("-qual-inflate", o._qualInflate), n_blocks, kQualInflateAutoBlocks);
@@ -767,11 +778,13 @@ void Decoder::stage_c(RoundPtr Rp) {
     struct Left { DnaGroup* g; ~Left() { if (g && --g->rounds_left == 0) g->release_device(); } } left{R.on_device ? R.dna.get() : nullptr};
     if (m.has_letters) restore_letters(R);
     if (m.has_sums) verify_checksums(R);
-    R.n_text = text_size(R); R.file_off = next_file_off;
-    next_file_off += R.n_text;
+    if (!o._bam) {                                           // (BAM records are sized by their formatter, and BGZF has no file offsets to plan)
+        R.n_text = text_size(R); R.file_off = next_file_off;
+        next_file_off += R.n_text;
+    }
     if (R.on_device && write_round_device(R)) return;
     if (R.on_device) round_to_host(R);
-    write_round(R);
+    if (o._bam) write_round_bam_host(R); else write_round(R);
 }
 
 // reads [ra, rb) of the round as records at tbase + rec_off[r]
@@ -843,7 +856,7 @@ void Decoder::write_round(Round& R) {
 // false: no device memory for the round's buffers (nothing written): the caller formats it on the host.
 bool Decoder::write_round_device(Round& R) {
     auto tl = std::chrono::steady_clock::now();
-    const uint64_t g_reads = R.g_reads, g_bases = R.g_bases, n_text = R.n_text;
+    const uint64_t g_reads = R.g_reads, g_bases = R.g_bases, n_text = o._bam ? bam_bound(R) : R.n_text;   // (`-bam`: room enough; the call says what it took)
     check_qual_lengths(R);
     DeviceMem d_text, d_qual, d_hdr, d_hoff, d_rec;
     auto upload = [&](void* d, const void* src, uint64_t n) { check(nullptr, leon_device_upload(dev, d, src, n), "leon_device_upload"); };
@@ -870,16 +883,59 @@ bool Decoder::write_round_device(Round& R) {
     lay.struct_size = (uint32_t)sizeof(lay); lay.lead = (uint8_t)m.lead; lay.fastq = m.fastq_out ? 1 : 0; lay.plus_kind = m.fastq_out && m.plus.def == 1 ? 1 : 0;
     lay.wrap = (uint32_t)std::min<uint64_t>(m.wrap, 0xFFFFFFFFull); lay.first_read_index = R.read_index; lay.hdr_bytes = hb;
     uint64_t size = 0;
-    const int rc = leon_records_format_device(dev, &lay, R.d_bases(), R.dna->d_lens.as<uint32_t>() + R.read0, g_reads, g_bases, hp, ho, quals, d_txt, n_text,
-                                              o._gzRecords ? d_rec.as<uint64_t>() : nullptr, &size);
-    if (rc == LEON_E_OVERFLOW || (rc == LEON_OK && size != n_text)) throw Exception(file + ": the decoded reads do not add up to their blocks' sizes");
-    check(nullptr, rc, "leon_records_format_device");
+    if (o._bam) {
+        bam_check(leon_records_bam_device(dev, &lay, R.d_bases(), R.dna->d_lens.as<uint32_t>() + R.read0, g_reads, g_bases, hp, ho, m.fastq_out ? quals : nullptr, d_txt,
+                                          n_text, o._gzRecords ? d_rec.as<uint64_t>() : nullptr, &size), "leon_records_bam_device");
+    } else {
+        const int rc = leon_records_format_device(dev, &lay, R.d_bases(), R.dna->d_lens.as<uint32_t>() + R.read0, g_reads, g_bases, hp, ho, quals, d_txt, n_text,
+                                                  o._gzRecords ? d_rec.as<uint64_t>() : nullptr, &size);
+        if (rc == LEON_E_OVERFLOW || (rc == LEON_OK && size != n_text)) throw Exception(file + ": the decoded reads do not add up to their blocks' sizes");
+        check(nullptr, rc, "leon_records_format_device");
+    }
     R.d_qual.reset();
-    if (o._gz) gz.from_device(d_txt, n_text, o._gzRecords ? d_rec.as<uint64_t>() : nullptr, g_reads, R.last);    // one call instead of the downloads
+    if (o._gz) gz.from_device(d_txt, size, o._gzRecords ? d_rec.as<uint64_t>() : nullptr, g_reads, R.last);    // one call instead of the downloads
     else download_text(R, d_txt);
     rt_rounds_on_device++;
     lap(tl, t_text);
     return true;
+}
+
+// `-bam`: room for the round's records without looking at the names: a record is 36 bytes, its header's bytes and at most 5 more (a
+// "*", two NULs, the tag of a comment -- its separator is not written), a nybble and a quality byte per base
+uint64_t Decoder::bam_bound(const Round& R) const {
+    const uint64_t g = R.g_reads;
+    const uint64_t hdr_total = !m.has_header ? 20 * g : R.hdr_in_set ? R.d_hdr_size : R.hdr_off[g] - R.hdr_off[0];
+    return 41 * g + hdr_total + R.g_bases + (R.g_bases + g) / 2 + 1;
+}
+
+// a read that BAM cannot hold ends the run in the formatter's words: "<file>: -bam: read N: ..."
+void Decoder::bam_check(int rc, const char* what) const {
+    if (rc == LEON_E_INVALID) {
+        const std::string why = leon_last_error(nullptr);
+        const size_t at = why.find(": read ");
+        if (at != std::string::npos) throw Exception(file + ": -bam: " + why.substr(at + 2));
+    }
+    if (rc == LEON_E_OVERFLOW) throw Exception(file + ": the decoded reads do not add up to their blocks' sizes");
+    check(nullptr, rc, what);
+}
+
+// the writing stage of `-bam` on the host: the records of leon_host_records_bam, compressed where `-gz` compresses the text
+void Decoder::write_round_bam_host(Round& R) {
+    auto tl = std::chrono::steady_clock::now();
+    const uint64_t g_reads = R.g_reads, head = BgzfWriter::HEAD, cap = bam_bound(R);
+    check_qual_lengths(R);
+    if (head + cap > text_cap) { text.reset(); text_cap = head + cap + cap / 16; text.reset(new char[text_cap]); }
+    uint8_t* const tbase = reinterpret_cast<uint8_t*>(text.get()) + head;
+    leon_record_layout lay{};
+    lay.struct_size = (uint32_t)sizeof(lay); lay.lead = (uint8_t)m.lead; lay.fastq = m.fastq_out ? 1 : 0;
+    lay.first_read_index = R.read_index; lay.hdr_bytes = m.has_header ? R.hdr_off[g_reads] - R.hdr_off[0] : 0;
+    std::vector<uint64_t> rec_off(g_reads + 1, 0);
+    uint64_t size = 0;
+    bam_check(leon_host_records_bam(&lay, R.bases(), R.lens(), g_reads, R.g_bases, m.has_header ? R.hdr.data() + R.hdr_off[0] : nullptr,
+                                    m.has_header ? R.hdr_off.data() : nullptr, m.fastq_out ? R.qual.data() + R.qual_off[0] : nullptr, tbase, cap, rec_off.data(), &size,
+                                    n_cpu), "leon_host_records_bam");
+    gz.from_host(tbase, size, rec_off, R.last);
+    lap(tl, t_text);
 }
 
 // the text comes back in pinned pieces, each written where it landed; a download keeps up to three copies in flight (PCIe's
@@ -932,7 +988,10 @@ void Decoder::finish() {
         while (!pending.empty()) { pending.front().get(); pending.pop_front(); }
         lap(tl, t_write);
     }
-    if (o._gz && !gz.closed) {                                // (a file without a round: the EOF marker alone)
+    if (o._bam && !gz.closed) {                               // (a file without a round: the BAM header and the EOF marker)
+        std::vector<uint8_t> room(BgzfWriter::HEAD + 64);
+        gz.from_host(room.data() + BgzfWriter::HEAD, 0, std::vector<uint64_t>(1, 0), true);
+    } else if (o._gz && !gz.closed) {                         // (a file without a round: the EOF marker alone)
         if (!gz.carry.empty()) throw Exception("-gz: text was left over behind the last round");
         (void)gz.compress(nullptr, 0, 0, nullptr, 0, true);
     }
@@ -986,21 +1045,26 @@ void Decoder::report() {
         std::cout << "header text: " << (hdr_text_device ? "device (k_hdr_text), " + std::to_string(hdr_blocks_fell_back.load()) + " of " + std::to_string(n_blocks) + " blocks fell back to the host decoder"
                                                          : hdr_on_device ? std::string("host threads, from symbols decoded on the device") : std::string("host threads"))
                   << std::endl;
-    std::cout << "record text: " << (rt_device ? rounds_text("k_fmt_records", rt_rounds_on_device.load(), rt_rounds_no_memory.load())
-                                               : rt_asked ? "host threads (" + rt_reason + ")" : std::string("host threads"))
-              << std::endl;
+    if (!o._bam)
+        std::cout << "record text: " << (rt_device ? rounds_text("k_fmt_records", rt_rounds_on_device.load(), rt_rounds_no_memory.load())
+                                                   : rt_asked ? "host threads (" + rt_reason + ")" : std::string("host threads"))
+                  << std::endl;
     if (m.fastq_out)
         std::cout << "quality blocks: " << (qi_device ? rounds_text("k_qual_inflate", qi_rounds_on_device.load(), qi_rounds_no_memory.load()) : std::string("host threads")) << std::endl;
     if (o._gz)
         std::cout << "output: BGZF on the device (" << (o._gzMatches ? "k_deflate_lz_chunks" : "k_deflate_chunks") << ", k_bgzf_members), " << gz.members << " member(s), " << gz.text << " -> " << gz.file_at << " bytes"
                   << (o._gzRecords ? ", record-aligned" : "")
-                  << (o._gzIndex ? ", index " + o._outputFilename + ".gzi (" + std::to_string(gz.members ? gz.members - 1 : 0) + " entries)" : std::string()) << std::endl;
+                  << (o._gzIndex ? ", index " + o._outputFilename + ".gzi (" + std::to_string(gz.members ? gz.members - 1 : 0) + " entries)" : std::string())
+                  << (o._bam ? ", records: BAM (" + (rt_device ? rounds_text("k_bam_records", rt_rounds_on_device.load(), rt_rounds_no_memory.load()) : std::string("host threads")) + ")"
+                             : std::string())
+                  << std::endl;
 }
 
 }  // namespace
 
 void Leon::executeDecompression() {
     {
+        if (_bam) _gz = true;                                 // -bam turns the BGZF writer on exactly as -gz does
         Decoder d(*this);
         d.run();
     }

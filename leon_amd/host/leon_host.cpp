@@ -58,6 +58,7 @@ void Leon::run(int argc, char* argv[]) {
             else if (a == "-gz-records") _gzRecords = true;
             else if (a == "-gz-index") _gzIndex = true;
             else if (a == "-gz-matches") _gzMatches = true;
+            else if (a == "-bam") _bam = true;
             else if (a == "-dict-pieces") _dictPieces = true;
             else if (a == "-dict-piece-anchors") {
                 const long v = number("-dict-piece-anchors");
@@ -79,9 +80,13 @@ void Leon::run(int argc, char* argv[]) {
         if (_ignoreChecksum && _compress) throw Exception("option -ignore-checksum belongs to -d");
         if (_letters && _decompress) throw Exception("option -letters belongs to -c: -d restores the letters whenever the container holds them");
         if (_gz && _compress) throw Exception("option -gz belongs to -d");
-        if (_gzRecords && !_gz) throw Exception("option -gz-records belongs to -gz");
-        if (_gzIndex && !_gz) throw Exception("option -gz-index belongs to -gz");
-        if (_gzMatches && !_gz) throw Exception("option -gz-matches belongs to -gz");
+        if (_bam && _compress) throw Exception("option -bam belongs to -d");
+        if (_gz && _bam) throw Exception("options -gz and -bam name two output formats");
+        // (-bam takes the three -gz-* options as -gz does; the words of their refusal are as they were)
+        if (_gzRecords && !_gz && !_bam) throw Exception("option -gz-records belongs to -gz");
+        if (_gzIndex && !_gz && !_bam) throw Exception("option -gz-index belongs to -gz");
+        if (_gzMatches && !_gz && !_bam) throw Exception("option -gz-matches belongs to -gz");
+        if (_testFile && _bam) throw Exception("option -test-file compares text: not with -bam");
         if (!_inputInflate.empty() && _decompress) throw Exception("option -input-inflate belongs to -c");
         if (!_recordParse.empty() && _decompress) throw Exception("option -record-parse belongs to -c");
         if (_recordParseFasta && (_recordParse.empty() || !record_parse_on_device(_recordParse))) throw Exception("option -record-parse-fasta belongs to -record-parse device");

@@ -55,6 +55,7 @@ public:
     uint32_t _dictPieceAnchors = 0;       // -c -dict-pieces -dict-piece-anchors N: anchors per piece (0: the library's default, 1024)
     bool _gzMatches = false;              // -d -gz: -gz-matches: LZ77 matches in the members, k_deflate_lz_chunks
     bool _gzIndex = false;                // -d -gz: -gz-index: X.d.gz.gzi beside the file, every member's offset in the file and in the text
+    bool _bam = false;                    // -d: -bam: the restored reads as unaligned BAM (X.d.bam), records and BGZF written on the device
     std::string _qualDeflate;             // -qual-deflate host|device|auto; empty = not given: zlib on the host threads (the reference's bytes)
     std::string _inputInflate;            // -c: -input-inflate host|device|auto; empty = not given: a gzip input inflated by zlib on the reader's thread
     std::string _recordParse;             // -c: -record-parse host|device; empty = not given: the FASTQ records cut by the reader's thread on the host
