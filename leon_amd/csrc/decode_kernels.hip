@@ -257,19 +257,22 @@ __global__ void k_pc_init(uint64_t* slots, uint64_t n_words, uint32_t words_per_
     }
 }
 
-// err[0]: 0 ok; otherwise 1 + the first failing block in err[1] (code: 1 address/position out of range, 2 output
-// overflow, 3 too many N / error positions in one read)
+// err[0]: ~0 ok; otherwise the SMALLEST (block << 3 | code) over the blocks that failed -- the smallest failing block with its own
+// code, whichever wave got there first (code: 1 address/position out of range, 2 output overflow, 3 too many N / error positions
+// in one read, 4 the payload ended).  err[2]: nonzero when a block found the pool exhausted (the caller decodes again with a pool
+// no call can exhaust, and says so in pool_cursor[1]: see pool_list below).
 // NH: the bloom's number of hash functions when the instantiation is for it (Leon's 7), 0 = at run time (leon_device.h bloom_keys)
 template <typename K, bool DEEP, uint32_t NH>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) k_decode_blocks(BloomDev B, PathCache PCc, const uint16_t* rv16g, const uint64_t* anchors, uint64_t n_anchors,
                                                      const uint8_t* payloads, const uint64_t* pay_off, const uint32_t* blk_reads,
                                                      const uint64_t* blk_read0, const uint64_t* blk_out0, uint64_t n_blocks,
                                                      uint8_t* out, uint32_t* out_len, uint32_t* scratch, uint32_t* pool,
-                                                     unsigned long long* pool_cursor, uint64_t pool_words, int* err, unsigned long long* stats) {
+                                                     unsigned long long* pool_cursor, uint64_t pool_words, unsigned long long* err, unsigned long long* stats) {
     __shared__ uint16_t rv16[256];
     __shared__ uint32_t models[RC_SMALL_WORDS + DC_NSLOT * RC_STRIDE];
     __shared__ uint8_t slotmap[RC_NNUM];
     __shared__ uint32_t lstN_[DC_LIST_LDS], lstE_[DC_LIST_LDS];  // the first entries of the read's N / error positions (the usual read has a few)
+    __shared__ unsigned long long plst_[4];                    // the block's pool allocations: list l at pool + [l], [2 + l] words (0: none yet)
     load_rv16(rv16, rv16g, NH ? B.block_mask : 0xFFFFu);
     volatile lds_u32* const lstN = (volatile lds_u32*)lstN_;
     volatile lds_u32* const lstE = (volatile lds_u32*)lstE_;
@@ -289,6 +292,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         __syncthreads();
         for (uint32_t m = 0; m < N_SMALL_MODELS; m++) model_init(&models[m * RC_SSTRIDE], lane, true);   // AbstractDnaCoder::startBlock
         for (uint32_t i = lane; i < RC_NNUM; i += 64) slotmap[i] = 255;
+        if (lane < 4) plst_[lane] = 0;
         __syncthreads();
         win_load(d);
         for (int i = 0; i < 8; i++) d.code = (d.code << 8) | next_byte(d);
@@ -300,12 +304,28 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         Pend<K> P;
         uint32_t n_fast = 0, n_miss = 0, n_slow = 0, n_slowjump = 0, n_jumped = 0, n_hybrid = 0, n_childhit = 0, n_short = 0, n_unclean = 0;
         unsigned long long t_head = 0, t_walk = 0, t_mark = stats ? wall_clock64() : 0;   // rounds by kind (stats != nullptr: measurement)
-        auto pool_alloc = [&](uint64_t cnt) -> uint32_t* {           // wave-uniform; never freed (rare, bounded by pool_words)
-            unsigned long long base = 0;
-            if (lane == 0) base = atomicAdd(pool_cursor, (unsigned long long)cnt);
-            base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
-                   (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-            return base + cnt <= pool_words ? pool + base : nullptr;
+        // A block uses its two lists for one read at a time: it keeps ONE pool allocation per list and uses it again from read to
+        // read (where and how large: plst_, in LDS -- looked at by long lists only, and no register is held for it on the chain).
+        // A list longer than the allocation takes a new one of max(entries, twice the old) words, never more than the bases the
+        // block has left (no later list of this block can be longer: cntv <= len <= wcap - w); with pool_full the first one is
+        // that bound itself, so a block takes at most 2 * (its bases) words and a pool of that sum over the blocks cannot run out.
+        auto pool_list = [&](uint32_t l, uint64_t cntv, uint64_t left) -> uint32_t* {   // wave-uniform; nullptr: the pool ran out
+            volatile unsigned long long* ps = plst_;
+            const uint64_t cap = ps[2 + l];
+            if (cntv > cap) {
+                const bool pool_full = __hip_atomic_load(pool_cursor + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;   // (the host's word: kept out of the arguments, which live in registers all along the chain)
+                uint64_t want = pool_full ? left : (cntv > 2 * cap ? cntv : 2 * cap);
+                if (want > left) want = left;                  // >= len >= cntv
+                unsigned long long base = 0;
+                if (lane == 0) base = atomicAdd(pool_cursor, (unsigned long long)want);       // given back only with the call
+                base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
+                       (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+                if (base + want > pool_words) { if (lane == 0) atomicOr(err + 2, 1ull); return nullptr; }
+                if (lane == 0) { ps[l] = base; ps[2 + l] = want; }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_wave_barrier();
+            }
+            return pool + ps[l];
         };
         for (uint32_t r = 0; r < blk_reads[b] && !fail; r++) {
             if (d.bad) { fail = 4; break; }
@@ -351,15 +371,25 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             for (uint32_t l = 0; l < 2 && !fail; l++) {
                 const uint64_t cntv = decode_numeric(d, l == 0 ? G_NUMERIC : G_LEFT_ERROR);
                 if (cntv > len) { fail = 3; break; }
-                uint32_t* gl = cntv > DC_LIST_CAP ? pool_alloc(cntv) : (l == 0 ? Nblk : Eblk);
-                if (!gl) { fail = 3; break; }
+                uint32_t* gl = l == 0 ? Nblk : Eblk;
+                if (cntv > DC_LIST_CAP) {
+                    gl = pool_list(l, cntv, wcap - w);
+                    if (!gl) { fail = 3; break; }
+                }
                 volatile lds_u32* ll = l == 0 ? lstN : lstE;
-                uint64_t pv = 0;
+                // A list may hold the same position more than once (a difference of 0: no decoder refuses it, and membership is what
+                // a list means).  An entry equal to the one before it says nothing new and is NOT KEPT: the walks' cursors, which step
+                // by one entry per position met, only ever see neighbours that differ.
+                uint64_t pv = 0, kept = 0;
+                uint32_t last = 0;
                 for (uint64_t i = 0; i < cntv; i++) {
                     pv += decode_numeric(d, l == 0 ? G_NPOS : G_ERRPOS);
-                    if (lane == 0) { gl[i] = (uint32_t)pv; if (i < DC_LIST_LDS) ll[i] = (uint32_t)pv; }
+                    const uint32_t q = (uint32_t)pv;
+                    if (i != 0 && q == last) continue;
+                    if (lane == 0) { gl[kept] = q; if (kept < DC_LIST_LDS) ll[kept] = q; }
+                    kept++; last = q;
                 }
-                if (l == 0) { nN = cntv; Npos = gl; } else { nErr = cntv; Epos = gl; }
+                if (l == 0) { nN = kept; Npos = gl; } else { nErr = kept; Epos = gl; }
             }
             if (fail) break;
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -407,7 +437,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
                     bool clean = false;
                     if (pos == nextN) {                       // an N: 'A' in the k-mer, no probe, no symbol
                         ni += step; nextN = cur(Npos, lstN, ni, (int64_t)nN);
-                        if (pos == nextE) { ei += step; nextE = cur(Epos, lstE, ei, (int64_t)nErr); }   // (never both, kept in step)
+                        if (pos == nextE) { ei += step; nextE = cur(Epos, lstE, ei, (int64_t)nErr); }   // (both only outside the conforming set: the N wins, as membership has it)
                         nt_out = 4; nt_seed = 0;
                     } else {
                         const uint32_t cnt = (uint32_t)__popc(res4);
@@ -555,7 +585,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         }
         if (!fail && d.bad) fail = 4;
         if (!fail && w != wcap) fail = 2;                    // the block table promised exactly wcap - blk_out0[b] bases
-        if (fail && lane == 0) { if (atomicCAS(err, 0, fail) == 0) err[1] = (int)b; }
+        // A writer's flush is the 8 bytes of `low`: the decoder has then read exactly the payload when its last symbol
+        // is out.  One that needed a byte more decoded its last symbols against zeros that nobody wrote -- a payload cut by a byte
+        // or two gives every symbol but the last ones right, and no other guard sees it.
+        if (!fail && blk_reads[b] && d.i > d.n) fail = 4;
+        if (fail && lane == 0) atomicMin(err, ((unsigned long long)b << 3) | (unsigned long long)fail);
         if (stats && lane == 0) {
             atomicAdd(stats + 0, n_fast); atomicAdd(stats + 1, n_miss); atomicAdd(stats + 2, n_slow); atomicAdd(stats + 3, n_slowjump);
             atomicAdd(stats + 4, n_jumped); atomicAdd(stats + 5, (unsigned long long)blk_reads[b]); atomicAdd(stats + 6, n_hybrid);
@@ -1021,7 +1055,7 @@ void launch_path_cache_init(hipStream_t s, PathCache C, uint32_t k) {
 void launch_decode_blocks(hipStream_t s, BloomDev B, PathCache C, const uint16_t* rv16, const uint64_t* anchors, uint64_t n_anchors,
                           const uint8_t* payloads, const uint64_t* pay_off, const uint32_t* blk_reads, const uint64_t* blk_read0,
                           const uint64_t* blk_out0, uint64_t n_blocks, uint8_t* out, uint32_t* out_len, uint32_t* scratch,
-                          uint32_t* pool, unsigned long long* pool_cursor, uint64_t pool_words, int* err, unsigned long long* stats) {
+                          uint32_t* pool, unsigned long long* pool_cursor, uint64_t pool_words, unsigned long long* err, unsigned long long* stats) {
     if (!n_blocks) return;
     // (grid cap 256 * 8 blocks: tests/many_blocks.py's N_BLOCKS must stay above twice that, so that a wave takes a second trip)
     const uint32_t g = (uint32_t)(n_blocks > 256 * 8 ? 256 * 8 : n_blocks);   // 8 waves per CU: the kernel's registers allow two per SIMD
@@ -1130,8 +1164,15 @@ static int decode_blocks_impl(leon_dna_ctx* c, const uint64_t* anchors, uint64_t
     HIPCHK(c, d_read0.ensure((n_blocks + 1) * 8)); HIPCHK(c, d_out0.ensure((n_blocks + 1) * 8));
     HIPCHK(c, d_out.ensure(out0[n_blocks] + 64)); HIPCHK(c, d_len.ensure(std::max<uint64_t>(read0[n_blocks], 1) * 4));
     HIPCHK(c, d_scr.ensure(decode_scratch_bytes(n_blocks))); HIPCHK(c, d_err.ensure(256));
-    // position lists longer than a block's own scratch (8192 N or error positions in ONE read) come from this pool
-    const uint64_t pool_words = std::min<uint64_t>(std::max<uint64_t>(out0[n_blocks] / 2, 1ull << 20), 1ull << 28);
+    // Position lists longer than a block's own scratch (8192 N or error positions in ONE read) come from this pool.  A block keeps one
+    // allocation per list and uses it again from read to read (k_decode_blocks), so the pool a call starts with is enough unless
+    // many blocks hold such reads at once.  pool_sure is what no call can exhaust: 2 words (one per list) per base of every block that
+    // can hold a list that long.  A call whose blocks do exhaust the first pool is decoded once more with pool_sure (pool_full: a
+    // block then takes its bound at once): what a conforming file decodes to does not depend on how much of it is N.
+    uint64_t pool_words = std::min<uint64_t>(std::max<uint64_t>(out0[n_blocks] / 2, 1ull << 20), 1ull << 28);
+    uint64_t pool_sure = 0;
+    for (uint64_t b = 0; b < n_blocks; b++) if (block_n_bases[b] > DC_LIST_CAP) pool_sure += 2 * block_n_bases[b];
+    uint32_t pool_full = pool_sure <= pool_words;
     HIPCHK(c, d_pool.ensure(pool_words * 4 + 16));
     lap("buffers and payloads");
     bool cache_is_new = false;
@@ -1140,8 +1181,6 @@ static int decode_blocks_impl(leon_dna_ctx* c, const uint64_t* anchors, uint64_t
     if (n_anchors) HIPCHK(c, hipMemcpyAsync(d_anchors.p, anchors, n_anchors * W * 8, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(d_read0.p, read0.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(d_out0.p, out0.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemsetAsync(d_err.p, 0, 256, s));
-    HIPCHK(c, hipMemsetAsync((uint8_t*)d_pool.p + pool_words * 4, 0, 16, s));           // the pool's cursor lives behind it
     lap("tables to the device");
     if (cache_is_new) {                                       // what the bloom says around every anchor, before the blocks ask (decode_kernels.hip)
         static const char* pw = getenv("LEON_DC_PREWALK");    // measurement override: steps per anchor and orientation, 0 = none
@@ -1152,12 +1191,20 @@ static int decode_blocks_impl(leon_dna_ctx* c, const uint64_t* anchors, uint64_t
         if (steps) launch_path_cache_prewalk(s, c->B, c->dc.pc, c->rv16(), d_anchors.as<uint64_t>(), n_anchors, steps);
         lap("path cache: walks from the anchors");
     }
-    launch_decode_blocks(s, c->B, c->dc.pc, c->rv16(), d_anchors.as<uint64_t>(), n_anchors, d_pay.as<uint8_t>(), T.off.as<uint64_t>(),
-                         T.nreads.as<uint32_t>(), d_read0.as<uint64_t>(), d_out0.as<uint64_t>(), n_blocks, d_out.as<uint8_t>(),
-                         d_len.as<uint32_t>(), d_scr.as<uint32_t>(), d_pool.as<uint32_t>(),
-                         (unsigned long long*)((uint8_t*)d_pool.p + pool_words * 4), pool_words, d_err.as<int>(),
-                         trace ? (unsigned long long*)((uint8_t*)d_err.p + 64) : nullptr);
-    HIPCHK(c, hipGetLastError());
+    auto launch = [&]() -> int {                              // d_err: [0] the smallest failing (block << 3 | code), [2] the pool ran out
+        HIPCHK(c, hipMemsetAsync(d_err.p, 0, 256, s));
+        HIPCHK(c, hipMemsetAsync(d_err.p, 0xFF, 8, s));
+        HIPCHK(c, hipMemsetAsync((uint8_t*)d_pool.p + pool_words * 4, 0, 16, s));       // the pool's cursor lives behind it, and behind that ...
+        if (pool_full) HIPCHK(c, hipMemsetAsync((uint8_t*)d_pool.p + pool_words * 4 + 8, 1, 1, s));   // ... the word that says "this pool cannot run out"
+        launch_decode_blocks(s, c->B, c->dc.pc, c->rv16(), d_anchors.as<uint64_t>(), n_anchors, d_pay.as<uint8_t>(), T.off.as<uint64_t>(),
+                             T.nreads.as<uint32_t>(), d_read0.as<uint64_t>(), d_out0.as<uint64_t>(), n_blocks, d_out.as<uint8_t>(),
+                             d_len.as<uint32_t>(), d_scr.as<uint32_t>(), d_pool.as<uint32_t>(),
+                             (unsigned long long*)((uint8_t*)d_pool.p + pool_words * 4), pool_words, d_err.as<unsigned long long>(),
+                             trace ? (unsigned long long*)((uint8_t*)d_err.p + 64) : nullptr);
+        HIPCHK(c, hipGetLastError());
+        return LEON_OK;
+    };
+    if (int rc = launch()) return rc;
     // While the blocks decode (seconds), the caller's output buffer is touched page by page: fresh memory is mapped on first
     // write, which would otherwise happen inside the copy back -- 3.7 M page faults for a 100 M-read file, on the critical path.
     // Each page's first byte is written back as it was read, so the buffer's contents survive a call that then fails (a corrupt
@@ -1173,11 +1220,19 @@ static int decode_blocks_impl(leon_dna_ctx* c, const uint64_t* anchors, uint64_t
             });
     }
     struct Join { std::vector<std::thread>& t; ~Join() { for (auto& x : t) if (x.joinable()) x.join(); } } join_touchers{toucher};
-    int err[2] = {0, 0};
-    HIPCHK(c, hipMemcpyAsync(err, d_err.p, 8, hipMemcpyDeviceToHost, s));
+    unsigned long long err[3] = {0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(err, d_err.p, 24, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     for (auto& x : toucher) x.join();
     toucher.clear();
+    if (err[2] && !pool_full) {                               // the first pool ran out: once more, with the pool that cannot
+        pool_words = pool_sure; pool_full = 1;
+        HIPCHK(c, d_pool.ensure(pool_words * 4 + 16));
+        if (int rc = launch()) return rc;
+        HIPCHK(c, hipMemcpyAsync(err, d_err.p, 24, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        lap("k_decode_blocks, first pool exhausted");
+    }
     lap("k_decode_blocks");
     if (trace) {
         unsigned long long st[16] = {0};
@@ -1188,10 +1243,11 @@ static int decode_blocks_impl(leon_dna_ctx* c, const uint64_t* anchors, uint64_t
         fprintf(stderr, "[leon decode] per read: %.2f entries taken to their end before the last base, one-k-mer rounds: %.2f on a branching k-mer, %.2f found the successor in the table\n", st[10] / nr, st[11] / nr, st[9] / nr);
         fprintf(stderr, "[leon decode] per read: %.2f us in its fields, %.2f us in its walks (100 MHz clock, the wave's own time)\n", st[7] / nr / 100.0, st[8] / nr / 100.0);
     }
-    if (err[0]) {
-        const char* what = err[0] == 1 ? "anchor address or position out of range" : err[0] == 2 ? "more or fewer bases than the block table says"
-                         : err[0] == 4 ? "the payload ends before its reads do" : "too many N / error positions in one read";
-        return fail(c, LEON_E_INVALID, std::string("block ") + std::to_string(err[1]) + " does not decode: " + what);
+    if (err[0] != ~0ull) {                                    // the smallest block that fails, with that block's own reason
+        const unsigned code = (unsigned)(err[0] & 7u);
+        const char* what = code == 1 ? "anchor address or position out of range" : code == 2 ? "more or fewer bases than the block table says"
+                         : code == 4 ? "the payload ends before its reads do" : "too many N / error positions in one read";
+        return fail(c, LEON_E_INVALID, std::string("block ") + std::to_string(err[0] >> 3) + " does not decode: " + what);
     }
     if (to_device) {                                          // the bases stay in HBM: into the caller's buffers, complete on return
         if (out0[n_blocks]) HIPCHK(c, hipMemcpyAsync(d_user_bases, d_out.p, out0[n_blocks], hipMemcpyDeviceToDevice, s));

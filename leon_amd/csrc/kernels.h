@@ -195,7 +195,8 @@ void launch_hdr_text(hipStream_t s, const uint8_t* syms, const uint64_t* sym_beg
 void launch_decode_blocks(hipStream_t s, BloomDev B, PathCache C, const uint16_t* rv16, const uint64_t* anchors, uint64_t n_anchors,
                           const uint8_t* payloads, const uint64_t* pay_off, const uint32_t* blk_reads, const uint64_t* blk_read0,
                           const uint64_t* blk_out0, uint64_t n_blocks, uint8_t* out, uint32_t* out_len, uint32_t* scratch,
-                          uint32_t* pool, unsigned long long* pool_cursor, uint64_t pool_words, int* err,
+                          uint32_t* pool, unsigned long long* pool_cursor, uint64_t pool_words /* pool_cursor[1] != 0: a pool that cannot run out */,
+                          unsigned long long* err /* [0] smallest (block << 3 | code), ~0 = none; [2] the pool ran out */,
                           unsigned long long* stats /* nullptr, or 16 counters: rounds by kind, time by part (LEON_TRACE_DECODE) */);
 
 // ---- zlib's CRC-32 of segments of a device buffer (crc_kernels.hip), DESIGN.md 4.11 ----

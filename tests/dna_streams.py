@@ -58,6 +58,20 @@ class Policy:
     err_at: Optional[Callable] = None                    # (len, apos, k) -> positions to list by design
 
 
+@dataclass
+class Tamper:
+    """tests/dna_bad_streams.py's hook: what one chosen read of a block is written with INSTEAD of what the writer would write.  Every
+    callable gets the conforming value(s) and returns what goes into the stream; nothing here is looked at when `tamper` is None."""
+    read: int                                            # index of the read in the block
+    fields: dict = field(default_factory=dict)           # "size" | "pos" | "addr" | "nasize" -> f(value, prev) = (delta type, coded number, bytes or None)
+    entries: dict = field(default_factory=dict)          # "n" | "err" -> f(conforming list) = the entries as written (coded as differences)
+    count: dict = field(default_factory=dict)            # "n" | "err" -> f(len of the written list, read length) = the declared size
+    err_at: Sequence = ()                                # walked positions of this read to list as errors by design
+    cut: Optional[str] = None                            # the symbol list ends behind: "fields" (size, pos, addr) | "nasize" | "n_count" | "err_count"
+    syms: Optional[list] = None                          # out: the block's (model, symbol) list as coded ...
+    bad_at: Optional[int] = None                         # ... and the index of the chosen read's first symbol
+
+
 def _minimal_bytes(v):
     bc = 1
     while bc < 8 and (v >> (8 * bc)):
@@ -117,9 +131,10 @@ def candidates(seq, k, index):
     return out
 
 
-def build_block(reads, k, bloom, anchors, rnd, policy, probe_cache=None):
+def build_block(reads, k, bloom, anchors, rnd, policy, probe_cache=None, tamper=None):
     """reads: list of bytes; bloom: oracle_lib.Bloom; anchors: python-int k-mers (the dictionary, any order); rnd: random.Random.
-    Returns (payload, facts).  probe_cache: a dict shared between calls with the same bloom (its answers are a function of the k-mer)."""
+    Returns (payload, facts).  probe_cache: a dict shared between calls with the same bloom (its answers are a function of the k-mer).
+    tamper: a Tamper, for streams that leave the conforming set on purpose (None: the payload is what it always was)."""
     index = {}
     for a, x in enumerate(anchors):
         index.setdefault(x, []).append(a)
@@ -136,17 +151,23 @@ def build_block(reads, k, bloom, anchors, rnd, policy, probe_cache=None):
             r = probe_cache[key] = bloom.contains4(km, right)
         return r
 
-    def numeric(g, v):
+    def numeric(g, v, forced=None):
         bc = _minimal_bytes(v)
         if policy.pad:
             bc = rnd.randint(bc, 8)
+        if forced is not None:
+            bc = forced
         syms.append((group_model(g), bc))
         facts["models"].add(group_model(g))
         for i in range(bc):
             syms.append((group_model(g, 1 + i), (v >> (8 * i)) & 255))
             facts["models"].add(group_model(g, 1 + i))
 
-    def delta(mt, g, value, prev):
+    def delta(mt, g, value, prev, forced=None):
+        if forced is not None:                               # (delta type, coded number, bytes)
+            syms.append((mt, forced[0]))
+            numeric(g, forced[1], forced[2])
+            return
         rule = delta_rule(value, prev)
         t = rule
         if policy.free_delta:
@@ -163,6 +184,9 @@ def build_block(reads, k, bloom, anchors, rnd, policy, probe_cache=None):
         npos = [i for i, c in enumerate(read) if c not in _CODE]
         nset = set(npos)
         facts["reads"] += 1
+        tam = tamper if tamper is not None and tamper.read == ri else None
+        if tam:
+            tam.bad_at = len(syms)
         if policy.anchor == "given":
             choice = policy.given[ri]
             cands = [choice] if choice is not None else []
@@ -184,7 +208,13 @@ def build_block(reads, k, bloom, anchors, rnd, policy, probe_cache=None):
         if choice is None:                                   # a read without an anchor: its letters, one by one
             facts["noanchor"] += 1
             syms.append((M_TYPE, 1))
-            numeric(G_NASIZE, L)
+            if tam and "nasize" in tam.fields:
+                f = tam.fields["nasize"](L, 0)
+                numeric(G_NASIZE, f[1], f[2])
+            else:
+                numeric(G_NASIZE, L)
+            if tam and tam.cut == "nasize":
+                break
             syms.extend((M_NOANCHOR, _CODE.get(c, 4)) for c in read)
             continue
         apos, addr, rev = choice
@@ -205,11 +235,17 @@ def build_block(reads, k, bloom, anchors, rnd, policy, probe_cache=None):
             here = (here << 2) | c
         assert 0 <= apos <= L - k and here == anchor, "not an anchor of this read"
         syms.append((M_TYPE, 0))
-        delta(M_SIZE_DT, G_SIZE, L, prev_size); prev_size = L
-        delta(M_POS_DT, G_POS, apos, prev_pos); prev_pos = apos
-        delta(M_ADDR_DT, G_ADDR, addr, prev_addr); prev_addr = addr
+        forced = {name: f(value, prev) for name, f in tam.fields.items() for value, prev in
+                  [dict(size=(L, prev_size), pos=(apos, prev_pos), addr=(addr, prev_addr)).get(name, (0, 0))]} if tam else {}
+        delta(M_SIZE_DT, G_SIZE, L, prev_size, forced.get("size")); prev_size = L
+        delta(M_POS_DT, G_POS, apos, prev_pos, forced.get("pos")); prev_pos = apos
+        delta(M_ADDR_DT, G_ADDR, addr, prev_addr, forced.get("addr")); prev_addr = addr
+        if tam and tam.cut == "fields":
+            break
         syms.append((M_REV, rev))
         wanted = set(policy.err_at(L, apos, k)) if policy.err_at else set()
+        if tam:
+            wanted |= set(tam.err_at)
         bifs, errs = [], []
         for right in (0, 1):
             km = anchor
@@ -239,15 +275,23 @@ def build_block(reads, k, bloom, anchors, rnd, policy, probe_cache=None):
         assert all(0 <= p < L and not apos <= p < apos + k for p in errs), "left the conforming set"
         facts["n_err"] += len(errs)
         facts["longest_err_list"] = max(facts["longest_err_list"], len(errs))
-        numeric(G_NUM, len(npos))
+        n_written = tam.entries["n"](npos) if tam and "n" in tam.entries else npos
+        numeric(G_NUM, tam.count["n"](len(n_written), L) if tam and "n" in tam.count else len(n_written))
+        if tam and tam.cut == "n_count":
+            break
         p = 0
-        for x in npos:
+        for x in n_written:
             numeric(G_NPOS, x - p); p = x
-        numeric(G_NERR, len(errs))
+        e_written = tam.entries["err"](errs) if tam and "err" in tam.entries else errs
+        numeric(G_NERR, tam.count["err"](len(e_written), L) if tam and "err" in tam.count else len(e_written))
+        if tam and tam.cut == "err_count":
+            break
         p = 0
-        for x in errs:
+        for x in e_written:
             numeric(G_ERRPOS, x - p); p = x
         syms.extend(bifs)
+    if tamper is not None:
+        tamper.syms = list(syms)
     a = np.array(syms, dtype=np.uint8).reshape(-1, 2)
     facts["models_most_in_a_block"] = len(facts["models"])
     return O.rc_encode_stream(a[:, 0], a[:, 1], SIZES), facts
