@@ -1265,8 +1265,9 @@ class DnaEncodeContext:
         self._chk(self.lib.leon_header_decode_symbols(self.h, _ptr(pay, _u8p), _ptr(off, _u64p), _ptr(nr, _u32p), len(blocks), C.byref(h)))
 
         class Set:
-            def text(self, first_block, n_blocks, first_header, n_threads=0):
-                counts = np.ascontiguousarray(nr[first_block:first_block + n_blocks], dtype=np.uint32)
+            def text(self, first_block, n_blocks, first_header, n_threads=0, n_reads=None):
+                """n_reads: the reads of each of the blocks, where the caller's table says otherwise than the set was decoded with"""
+                counts = np.ascontiguousarray(nr[first_block:first_block + n_blocks] if n_reads is None else n_reads, dtype=np.uint32)
                 total = int(counts.sum())
                 out_off = np.zeros(total + 1, dtype=np.uint64)
                 need = C.c_uint64()

@@ -628,7 +628,13 @@ int leon_header_decode_text(leon_dna_ctx* c, const uint8_t* payloads, const uint
         HIPCHK(c, hipGetLastError());
         sizes.resize(n_blocks);
         HIPCHK(c, hipMemcpyAsync(sizes.data(), d_tsize.p, n_blocks * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
+        HIPCHK(c, hipMemcpyAsync(T->status.data(), d_status.p, n_blocks * 4, hipMemcpyDeviceToHost, s));
+        // what this pass refuses is refused here: in the pass that writes, a refused block has no share of the text, and a valid
+        // header before its bad record would have it declined for that (HT_SHARE) before the record is reached
+        bool overflowed = false;
+        if (int rc = hdr_symbols_wait(c, D, overflowed)) return rc;
+        for (uint64_t b = 0; b < n_blocks; b++)
+            if (T->status[b] >= HT_INVALID) return fail(c, LEON_E_INVALID, "header block " + std::to_string(b) + " does not decode");
         block_text_bytes = sizes.data();
     }
     for (uint64_t b = 0; b < n_blocks; b++) {

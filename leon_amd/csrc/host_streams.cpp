@@ -87,7 +87,7 @@ struct RangeDecoder {
     uint32_t past = 0;
     bool bad = false;                                         // the payload is not a stream this coder wrote (checked by the caller per header)
     RangeDecoder(const uint8_t* p_, uint64_t n_) : p(p_), n(n_) { for (int k = 0; k < 8; k++) code = (code << 8) | byte(); }
-    uint8_t byte() { return i < n ? p[i++] : 0; }
+    uint8_t byte() { if (i < n) return p[i++]; past++; return 0; }   // bytes beyond the end read as 0 and are counted, the constructor's included
     uint32_t next(Model256& m) {
         range /= m.total();
         if (range == 0 || bad) { bad = true; return 0; }
@@ -98,7 +98,7 @@ struct RangeDecoder {
             code = (code << 8) | byte();
             range <<= 8;
             low <<= 8;
-            if (i >= n && ++past > 16) { bad = true; return 0; }   // far past the end (a range of 0 would spin here)
+            if (past > 16) { bad = true; return 0; }         // the 17th byte beyond the end, as the device's Dec (a range of 0 would spin here)
         }
         m.update(c);
         return c;
@@ -289,7 +289,7 @@ int leon_host_header_decode_blocks(const uint8_t* payloads, const uint64_t* payl
         if (payload_off[b + 1] < payload_off[b]) return fail(LEON_E_INVALID, "payload offsets are not monotonic");
     return header_blocks_common(n_blocks, out, out_cap, out_off, out_size, n_threads, [&](uint64_t b, std::string& text, std::vector<uint64_t>& off) {
         RangeSource src(payloads + payload_off[b], payload_off[b + 1] - payload_off[b]);
-        return decode_header_block(src, block_n_reads[b], first_header, first_header_len, text, off);
+        return decode_header_block(src, block_n_reads[b], first_header, first_header_len, text, off) && !src.bad();   // (a block's last symbols are checked here)
     });
 }
 

@@ -3,7 +3,7 @@ rules rather than from oracle/leon_oracle.c: fields by regular expression, recor
 tests/py_leon.py.  tests/test_oracle_cpu.py checks the C oracle against it byte for byte (small inputs only)."""
 import re
 
-from py_leon import Model, RangeEncoder
+import header_streams as S
 
 END, END_MATCH, ASCII, NUMERIC, DELTA, DELTA_2, ZERO_ONLY, ZERO_AND_NUMERIC = 1, 2, 3, 4, 5, 6, 7, 8
 _FIELD = re.compile(rb"[0-9A-Za-z]*(?:[^0-9A-Za-z]|$)", re.S)
@@ -65,48 +65,12 @@ def records(cur, prev):
 
 
 def encode_block(headers, first):
-    """list of bytes -> payload bytes"""
-    rc = RangeEncoder()
-    M = {"type": Model(9), "idx": Model(256), "col": Model(256), "size": Model(256), "ascii": Model(256), "zero": Model(256),
-         "num": [Model(256) for _ in range(9)]}
-
-    def numeric(v):
-        bc = 1
-        while bc < 8 and (v >> (8 * bc)):
-            bc += 1
-        rc.encode(M["num"][0], bc)
-        for i in range(bc):
-            rc.encode(M["num"][i + 1], (v >> (8 * i)) & 255)
-
-    def count(m, x):
-        if x < 255:
-            rc.encode(M[m], x)
-        else:
-            rc.encode(M[m], 255)
-            numeric(x - 255)
-
-    def sep(s):
-        rc.encode(M["ascii"], s[0] if s else 0)
-
-    prev = first
+    """list of bytes -> payload bytes, through the symbol-level writer of tests/header_streams.py"""
+    make = {DELTA: S.delta, DELTA_2: S.delta2, NUMERIC: S.numeric, ZERO_ONLY: S.zero_only, ZERO_AND_NUMERIC: S.zero_numeric, ASCII: S.ascii,
+            END: S.end, END_MATCH: S.end_match}
+    pairs, prev = [], first
     for h in headers:
         for r in records(h, prev):
-            rc.encode(M["type"], r[0])
-            if r[0] == END_MATCH:
-                continue
-            count("idx", r[1])
-            if r[0] in (DELTA, DELTA_2):
-                numeric(r[2])
-            elif r[0] == NUMERIC:
-                numeric(r[2]); sep(r[3])
-            elif r[0] == ZERO_ONLY:
-                count("zero", r[2]); sep(r[3])
-            elif r[0] == ZERO_AND_NUMERIC:
-                count("zero", r[2]); numeric(r[3]); sep(r[4])
-            elif r[0] == ASCII:
-                count("col", r[2]); count("size", len(r[3]))
-                for b in r[3]:
-                    rc.encode(M["ascii"], b)
+            pairs += make[r[0]](*r[1:])
         prev = h
-    rc.flush()
-    return bytes(rc.out)
+    return S.write(pairs)
